@@ -23,9 +23,15 @@ Workloads (BASELINE.json configs):
           D = 1280, row-sharded re-ranking, fp16-MFMA distance mode checked against the exact fp32 mode.  Strong.
 
 One "step" = one full pass over the workload; inputs are resident in HBM before the timed region.  Rank 0 prints ONE
-JSON line with `roofline` (dominant kernel of the step, hipEvents on the launch stream), `roofline_all` (every stage
-of the metric incl. the 20k x 20k feat-GEMM and the re-rank stages, N = 1 only) and `cpu_baseline` (the CPU oracle
-on a bounded sample, N = 1 only).
+JSON line.  A plain run sets up, warms up, times the --steps steps and prints the line (`value`, `ms_per_step`, ...);
+nothing else runs.  With --full the line also carries `roofline` (dominant kernel of the step, hipEvents on the launch
+stream) and `cpu_baseline` (the CPU oracle on a bounded sample, N = 1 only), and the extras file `roofline_all` (every
+stage of the metric incl. the 20k x 20k feat-GEMM and the re-rank stages, N = 1 only), the parity sample and the
+secondary legs; --no-cpu-baseline / --no-extras / --no-live-traffic trim a --full run.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed (the arrays a caller of the
+step receives; a fixed, seeded row sample of the large ones) as DIR/<name>.npy, float32 / float64, <= 64 MB in all.
+The inputs are seeded: the same arguments give the same inputs in every run, so two builds compare output for output.
 """
 import argparse
 import json
@@ -158,6 +164,12 @@ def parse():
     ap.add_argument("--batch", type=int, default=508,
                     help="images per encoder call; 508*129 tokens = 256 row tiles of 256 rows = whole waves of "
                          "tiles on 256 CUs (reference yml: 64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: roofline / per-kernel figures, "
+                         "cpu_baseline and parity sample, the extras legs, the distance-mode tolerance check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (rank 0; seeded row samples of the large "
+                         "arrays, <= 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--no-live-traffic", action="store_true",
@@ -190,7 +202,10 @@ def parse():
     ap.add_argument("--streams", type=int, default=2,
                     help="HIP streams the encoder batches alternate on (HBM-bound phases of one batch overlap "
                          "MFMA phases of the other)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -294,6 +309,42 @@ def timed_ms(fn, reps, warm=1):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
+
+
+DUMP_MAX_BYTES = 64 << 20                       # --dump-outputs: all files together
+DUMP_MAX_ROW_ELEMS = 4_000_000                  # per 2-D array (16 MB of float32); larger ones: a seeded row sample
+DUMP_SEED = 20240601
+
+
+def dump_rows(x, seed=DUMP_SEED):
+    """a 2-D output (device tensor or host array) as a float32 host array: every row, or -- beyond DUMP_MAX_ROW_ELEMS --
+    a fixed sample of rows (seeded, ascending), so that two runs with the same arguments dump the same rows"""
+    import numpy as np
+    n, m = int(x.shape[0]), int(x.shape[1])
+    k = max(1, min(n, DUMP_MAX_ROW_ELEMS // max(m, 1)))
+    if k < n:
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+        if isinstance(x, np.ndarray):
+            x = x[idx]
+        else:
+            import torch
+            x = x[torch.as_tensor(idx, device=x.device)]
+    if not isinstance(x, np.ndarray):
+        x = x.detach().float().cpu().numpy()
+    return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def write_dump(out_dir, arrays):
+    """arrays: {name: float32 / float64 array} -> out_dir/<name>.npy; refuses to write more than DUMP_MAX_BYTES"""
+    import numpy as np
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    assert all(v.dtype in (np.float32, np.float64) for v in arrays.values()), {k: v.dtype for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return total
 
 
 def cpu_baseline(n_img):
@@ -581,10 +632,25 @@ def run_rank(a):
     pipe_env = f"streams={nstreams}" + (f",group={a.group}" if a.group > 0 else "")
     os.environ["MPREID_PIPELINE"] = pipe_env
 
+    # --dump-outputs (market): do_inference returns Rank-1 / Rank-5 only; the evaluator's compute() result of the step
+    # (cmc, mAP, distmat, pids, camids, qf, gf) of the LAST timed step is kept as the caller of compute() receives it (only
+    # that one: held results of earlier steps would keep their pinned host buffers from being reused by the next step)
+    compute_out = {}
+    if market is not None and a.dump_outputs:
+        from utils.metrics import R1_mAP_eval
+        compute_orig = R1_mAP_eval.compute
+
+        def compute_kept(self):
+            out = compute_orig(self)
+            if compute_out.get("keep"):
+                compute_out["last"] = out
+            return out
+        R1_mAP_eval.compute = compute_kept
+
     def step():
         if market is not None:
-            r1, _ = quiet_do_inference(market["cfg"], market["model"], market["loader"], nq)
-            rr_holder["rank1"] = float(r1)
+            r1, r5 = quiet_do_inference(market["cfg"], market["model"], market["loader"], nq)
+            rr_holder["rank1"], rr_holder["rank5"] = float(r1), float(r5)
             return
         if wl == "synth":
             fq, fg = fq_local, fg_local
@@ -619,17 +685,36 @@ def run_rank(a):
             dist.barrier()
         torch.cuda.synchronize()
 
+    def dump_last_step(out_dir):
+        """--dump-outputs: what the last timed step computed, as its caller receives it (this rank's share when N > 1)"""
+        if market is not None:
+            # do_inference's return value, then the evaluator's compute() result (pids / camids are inputs)
+            cmc, mAP, distmat, _, _, qf, gf = compute_out["last"]
+            arrays = {"rank1_rank5": np.array([rr_holder["rank1"], rr_holder["rank5"]], np.float64),
+                      "cmc": np.asarray(cmc, np.float64), "mAP": np.array([mAP], np.float64),
+                      "distmat": dump_rows(distmat), "query_feats": dump_rows(qf), "gallery_feats": dump_rows(gf)}
+        else:
+            arrays = {"distmat": dump_rows(block)}        # this rank's [nq, ng / N] distance block
+            if a.rerank:
+                arrays["rerank_distmat"] = dump_rows(rr_holder["rr"])
+            if wl == "msmt17":
+                arrays["feats"] = dump_rows(feats)       # encoder output of this rank's images
+        total = write_dump(out_dir, arrays)
+        print(f"bench.py: --dump-outputs wrote {len(arrays)} arrays ({total / 2**20:.1f} MB) to {out_dir}", file=sys.stderr)
+
     for _ in range(a.warmup):
         step()
     fence()
     comm.update(host_ms=0.0)
     D.comm_stats_reset(timing=True)
-    instrument_live = nstreams == 1 or enc is None   # event pairs on one stream also span other streams' kernels
+    # (--full only) event pairs on one stream also span other streams' kernels
+    instrument_live = a.full and (nstreams == 1 or enc is None)
     L.mpreid_profile_reset()
     if instrument_live:
         L.mpreid_profile_enable(1)
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    for i in range(a.steps):
+        compute_out["keep"] = i == a.steps - 1
         step()
     fence()
     dt = time.perf_counter() - t0
@@ -638,7 +723,12 @@ def run_rank(a):
     comm_bytes, comm_calls = D.comm_stats["bytes"], D.comm_stats["calls"]
     D.comm_stats_reset()
     host_concat_ms = comm.get("host_ms", 0.0) / max(a.steps, 1)
-    if not instrument_live:
+    if a.dump_outputs and rank == 0:
+        dump_last_step(a.dump_outputs)
+    if market is not None and a.dump_outputs:
+        R1_mAP_eval.compute = compute_orig      # the --full legs below keep nothing
+        compute_out.clear()
+    if a.full and not instrument_live:
         # roofline leg: one more pass of the same work on ONE stream with per-launch hipEvents
         saved = (list(side), list(encs))
         side[:], encs[:] = [], [enc]
@@ -660,7 +750,7 @@ def run_rank(a):
 
     if rank == 0:
         ents = (_lib.ProfileEntry * 48)()
-        n_ent = L.mpreid_profile_query(ents, 48)
+        n_ent = L.mpreid_profile_query(ents, 48) if a.full else 0   # per-kernel figures: --full
         classes, other = [], []
         for i in range(min(n_ent, 48)):
             e = ents[i]
@@ -818,7 +908,7 @@ def run_rank(a):
                                  "gb_per_s": round(comm_bytes / max(comm_ms, 1e-9) / 1e6, 2),
                                  "note": "bytes = gathered output per rank (RCCL all_gather_into_tensor over xGMI); "
                                          "hipEvents on the launch stream of rank 0"}
-        if wl == "msmt17" or (wl == "synth" and a.dist_mode == "exact"):
+        if a.full and (wl == "msmt17" or (wl == "synth" and a.dist_mode == "exact")):
             # fp16-MFMA distance mode against the exact fp32 mode on this rank's first 2048 x 8192 block
             qf_s = (ops.l2_normalize(feats)[:min(nq_local, 2048)] if wl != "synth" else fq_local[:2048])
             gf_s = (ops.l2_normalize(feats)[nq_local:nq_local + 8192] if wl != "synth" else fg_local[:8192])
@@ -830,7 +920,7 @@ def run_rank(a):
                 chk["fp16_split3_max_abs_err"] = float((ex - s3).abs().max())
             res["tolerance_check_vs_exact_fp32"] = chk
         parity = {}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"], sample = cpu_baseline(a.cpu_images)
             parity = parity_deltas(ops, sample, a.encoder_precision if enc is not None else "split")
             res["parity_sample"] = dict(parity, note="oracle (CPU checker) vs HIP on the cpu_baseline leg's identity images, "
@@ -842,7 +932,7 @@ def run_rank(a):
             res["drop_in"] = {"call": "processor.do_inference(cfg, model.make_model.make_model(cfg, ...), val_loader, num_query)",
                               "loader_batch": 64, "rank1": rr_holder.get("rank1"),
                               "pipeline": dict(getattr(_di, "last_pipeline_stats", {}))}
-        if world == 1 and not a.no_extras and not a.small:
+        if a.full and world == 1 and not a.no_extras and not a.small:
             drop = {}
             if market is not None:
                 drop = BX.drop_in_extras(a, market["cfg"], market["model"], nq, ng_total, pids_all, cams_all, dev)

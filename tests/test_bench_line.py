@@ -98,12 +98,46 @@ def test_gpus_beyond_visible_devices_exit_2_with_a_message():
     assert r.returncode == 2 and r.stdout.strip() == "" and r.stderr.strip() == ""   # only local rank 0 speaks
 
 
+def test_plain_run_options(monkeypatch):
+    """a plain run measures the headline only: --full is off unless given; --steps sets the timed steps (>= 1)"""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_rows_and_write_dump(tmp_path):
+    """--dump-outputs: small outputs whole, large ones as the same seeded row sample in every run, float32 / float64
+    files only, never more than 64 MB in all"""
+    import numpy as np
+    small = np.arange(50, dtype=np.float64).reshape(10, 5)
+    assert np.array_equal(bench.dump_rows(small), small) and bench.dump_rows(small).dtype == np.float32
+    big = np.random.default_rng(1).standard_normal((5000, 1000), dtype=np.float32)
+    s1, s2 = bench.dump_rows(big), bench.dump_rows(big.copy())
+    assert s1.shape == (bench.DUMP_MAX_ROW_ELEMS // 1000, 1000) and np.array_equal(s1, s2)
+    rows = [int(np.flatnonzero((big == r).all(axis=1))[0]) for r in s1[:50]]
+    assert rows == sorted(set(rows))                     # distinct input rows, ascending
+    total = bench.write_dump(str(tmp_path / "d"), {"a": s1, "m": np.array([0.5])})
+    assert total == s1.nbytes + 8 <= bench.DUMP_MAX_BYTES
+    assert np.array_equal(np.load(tmp_path / "d" / "a.npy"), s1) and np.load(tmp_path / "d" / "m.npy").dtype == np.float64
+    with pytest.raises(AssertionError):
+        bench.write_dump(str(tmp_path / "e"), {"i": np.arange(3)})                   # integers: not an output format
+    with pytest.raises(AssertionError):
+        bench.write_dump(str(tmp_path / "f"), {k: s1 for k in "abcde"})               # 80 MB
+    assert not os.path.exists(tmp_path / "f")
+
+
 @pytest.mark.gpu
 def test_bench_on_the_gpu_prints_one_small_line_and_a_quiet_stderr(tmp_path):
     """the driver's view of `python bench.py --gpus 1 ...` (a 1/16 workload): stdout is ONE line that parses and obeys the size
     contract, stderr is a handful of lines (round 4: ~90 evaluator lines), the extras file lands in the current directory"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--small", "--steps", "2", "--warmup", "1",
-                        "--cpu-images", "8"], cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
+                        "--full", "--cpu-images", "8"], cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and len(lines[0].encode()) <= bench.MAX_LINE_BYTES
@@ -128,3 +162,28 @@ def test_bench_on_the_gpu_prints_one_small_line_and_a_quiet_stderr(tmp_path):
     assert len([ln for ln in r.stderr.splitlines() if ln.strip()]) <= 12, r.stderr[-1500:]
     extras = json.load(open(tmp_path / "bench_extras.json"))
     assert "gemm_classes" in extras and "drop_in" in extras
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the line carries the headline and
+    ms_per_step but no roofline / cpu_baseline / metric_20k legs, and DIR holds what the last timed step computed:
+    do_inference's Rank-1 / Rank-5, the evaluator's CMC, mAP, distance matrix and features"""
+    import numpy as np
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--small", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(out)], cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and len(lines[0].encode()) <= bench.MAX_LINE_BYTES
+    j = json.loads(lines[0])
+    assert j["steps"] == 2 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0 and j["unit"] == "images/s"
+    assert j["higher_is_better"] is True and j["dtype"].startswith("f16 pairs")
+    assert j["roofline"] is None and j["cpu_baseline"] is None and "metric_20k" not in j
+    nq, ng = bench.NQ // 16, bench.NG // 16
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert set(got) == {"rank1_rank5", "cmc", "mAP", "distmat", "query_feats", "gallery_feats"}
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= bench.DUMP_MAX_BYTES
+    assert got["distmat"].shape == (nq, ng) and got["query_feats"].shape[0] == nq and got["gallery_feats"].shape[0] == ng
+    assert got["rank1_rank5"].tolist() == [got["cmc"][0], got["cmc"][4]] and 0 < got["mAP"][0] <= 1

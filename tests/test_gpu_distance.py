@@ -151,7 +151,7 @@ def test_full_size_properties(ops):
 
 
 @pytest.mark.parametrize("epi", [1, 2, 3])
-def test_gemm_kernels_agree_across_variants(epi):
+def test_gemm_kernels_agree_across_variants(epi, tmp_path):
     """the three fp16 GEMM kernels (128x128, 256x256 ring, persistent 256x128) must give identical
     results for the fused epilogues (same k order inside every MFMA chain => bit identical)"""
     import os, subprocess, sys, textwrap
@@ -174,7 +174,7 @@ def test_gemm_kernels_agree_across_variants(epi):
     """)
     outs = []
     for mode in ("0", "2", "3"):
-        path = f"/tmp/gemm_variant_{epi}_{mode}.npy"
+        path = str(tmp_path / f"gemm_variant_{epi}_{mode}.npy")
         r = subprocess.run([sys.executable, "-c", code, path], env=dict(os.environ, MPREID_TUNE="gemm_big=" + mode),
                            capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout + r.stderr

@@ -11,7 +11,7 @@ N=${2:-3}
 STEPS=${3:-5}
 run() {  # label, env...
   local label=$1; shift
-  env "$@" python3 $R/bench.py --gpus 1 --steps $STEPS --warmup 2 --no-extras --no-cpu-baseline 2>/dev/null |
+  env "$@" python3 $R/bench.py --gpus 1 --steps $STEPS --warmup 2 --full --no-extras --no-cpu-baseline 2>/dev/null |
     python3 -c "import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=j['roofline']; print('$label', j['value'], 'img/s', j['ms_per_step'], 'ms/step | dominant', r['kernel'], r['avg_launch_ms'], 'ms')"
   python3 -c "
 import json

@@ -10,14 +10,14 @@ cd /tmp && export TMPDIR=/tmp
 # every bench.py run leaves bench_extras.json in the current directory (/tmp here): keep the ones that are cited
 keep_extras() { cp /tmp/bench_extras.json $OUT/$1 2>/dev/null; }
 # 1. the bench line EXACTLY as the driver runs it (N = 1: --gpus 1 --steps 20 --warmup 5), and the other workloads
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/bench.err
+python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/bench.err
 keep_extras ${TAG}_bench_extras.json
-python3 $R/bench.py --encoder-precision fp16 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_fp16_encoder.json 2>> $OUT/bench.err
-python3 $R/bench.py --workload synth --rerank --steps 2 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_synth_rerank.json 2>> $OUT/bench.err
-python3 $R/bench.py --workload synth --dist-mode split3 --steps 3 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_synth_split3.json 2>> $OUT/bench.err
-python3 $R/bench.py --workload synth --rerank --rerank-algo split3 --dist-mode split3 --steps 2 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_synth_rerank_split3.json 2>> $OUT/bench.err
-python3 $R/bench.py --workload msmt17 --rerank --steps 1 --warmup 1 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_msmt17_rerank.json 2>> $OUT/bench.err
-python3 $R/bench.py --rerank --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_market_rerank.json 2>> $OUT/bench.err
+python3 $R/bench.py --full --encoder-precision fp16 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_fp16_encoder.json 2>> $OUT/bench.err
+python3 $R/bench.py --full --workload synth --rerank --steps 2 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_synth_rerank.json 2>> $OUT/bench.err
+python3 $R/bench.py --full --workload synth --dist-mode split3 --steps 3 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_synth_split3.json 2>> $OUT/bench.err
+python3 $R/bench.py --full --workload synth --rerank --rerank-algo split3 --dist-mode split3 --steps 2 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_synth_rerank_split3.json 2>> $OUT/bench.err
+python3 $R/bench.py --full --workload msmt17 --rerank --steps 1 --warmup 1 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_msmt17_rerank.json 2>> $OUT/bench.err
+python3 $R/bench.py --full --rerank --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_market_rerank.json 2>> $OUT/bench.err
 keep_extras ${TAG}_bench_market_rerank_extras.json
 # 2. kernel trace + stats of the same bench command (--streams 1 is honoured by every leg, also the host-loader ones of
 #    `extras`: no two kernels of the process overlap, so a kernel's average duration here is its launch duration)
@@ -28,7 +28,7 @@ keep_extras ${TAG}_bench_market_rerank_extras.json
 #    (faster: tools/evalrank_bench.py), but rocprofv3 serialises the two queues and then books the blit kernels the ranking
 #    kernel waited for into ITS interval (round 5's 5.4 ms average); ordered this way the trace shows the kernel's own time.
 export MPREID_EVAL_D2H=behind
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_bench -o b -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --streams 1 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_bench -o b -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --streams 1 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_under_rocprof.json 2>/dev/null
 unset MPREID_EVAL_D2H
 keep_extras ${TAG}_bench_under_rocprof_extras.json
 cp $OUT/kt_bench/b_kernel_stats.csv $OUT/${TAG}_bench_kernel_stats.csv
