@@ -298,6 +298,12 @@ typedef struct {
  * 2e-5 of the float64 graph and within a few times plain fp32's own error; test_split_mode_input_scale_edges). */
 #define MPREID_VIT_F16 0
 #define MPREID_VIT_SPLIT 1
+/* Limits: tokens L = h_res * w_res + 1 <= MPREID_VIT_MAX_TOKENS (1025 = a 512 x 512 input at stride 16) in all three modes ->
+ * MPREID_ERR_UNSUPPORTED above that.  L <= 256 (256 x 128 at stride 16 or 12): K / V of a head resident in LDS, one workgroup
+ * per (image, head); 256 < L <= 1025 (256 x 256: L = 257 at stride 16, 442 at stride 12): the fp16 / split attention streams
+ * K / V through LDS in 64-key blocks with an online softmax (same operands and product terms per mode), and the fp32 mode
+ * keeps K / V resident up to L = 320 and streams them in 128-key chunks above.  Rows do not depend on the batch either way. */
+#define MPREID_VIT_MAX_TOKENS 1025
 /* (precision 2 was MPREID_VIT_SPLIT_LNFOLD in round 3: the LayerNorms folded into the linear layers behind them.  Removed in
  * round 4 -- measured 0.5 % SLOWER than MPREID_VIT_SPLIT, and tools/ws_poison_check.py found its 128 x 128-kernel form not
  * reproducible run to run at small batches; mpreid_vit_forward returns MPREID_ERR_UNSUPPORTED for it.  The in_proj_c / fc_c
@@ -414,6 +420,11 @@ typedef struct {
     int32_t n_blocks;       /* sum of the layers tuple (3+4+6+3 = 16) */
     int32_t heads, out_dim; /* attention pool: embed dim = 32*width, heads, output_dim (1024) */
 } mpreid_rn50_cfg;
+/* Limits: attention-pool tokens T = (img_h / 16) * (img_w / 16) + 1 <= MPREID_RN50_MAX_TOKENS (1025, 512 x 512) for
+ * mpreid_rn50_forward (the fp16 tower) -> MPREID_ERR_UNSUPPORTED above that.  Its pool keeps the [T][heads] score table in
+ * LDS beside the u vectors while that fits (T <= 252 at width 64), and passes it through the workspace above.  The split
+ * and fp32 towers (one-query pool with T floats of LDS per (image, head)) take any T up to 40 960. */
+#define MPREID_RN50_MAX_TOKENS 1025
 
 typedef struct { /* device pointers unless noted */
     const float *stem1_w;   /* conv1+bn1 folded, fp32 [width/2][3][3][3] = [cout][c][kh][kw] */

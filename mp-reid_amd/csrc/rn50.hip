@@ -174,13 +174,19 @@ typedef float pf32x2 __attribute__((ext_vector_type(2)));
 //   z       z_h = sum_t p[h][t] tok_t: the contraction runs over the SLOW index of tok, which the MFMA operand
 //           layout cannot read without a transpose, so this part is packed fp32 FMAs: a thread owns 8 columns and 8
 //           heads at a time, token rows prefetched four ahead
+// SCG (T too large for the score table beside the u rows: T > 252 at E = 2048, H = 32): the scores go to the workspace
+// scg [B][T][H16] instead, and after the score phase -- the u rows no longer needed -- they are copied into the LDS the u rows
+// occupied; the softmax and z phases then run exactly as in the resident form (same arithmetic, same bits).
+template <bool SCG>
 __global__ __launch_bounds__(512) void rn50_pool_core_kernel(const _Float16 *__restrict__ U, const _Float16 *__restrict__ tok,
-                                                             int T, int E, int H, _Float16 *__restrict__ Z) {
+                                                             int T, int E, int H, _Float16 *__restrict__ Z,
+                                                             float *__restrict__ scg) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int ES = E + 8;
     const int H16 = (H + 15) & ~15;
     _Float16 *Us = reinterpret_cast<_Float16 *>(lds);                  // [H16][ES], rows >= H zero
-    float *sc = reinterpret_cast<float *>(lds + (size_t)H16 * ES * 2);  // [T][H16] (token-major: a token's H weights are one vector)
+    // [T][H16] (token-major: a token's H weights are one vector)
+    float *sc = SCG ? scg + (int64_t)blockIdx.x * T * H16 : reinterpret_cast<float *>(lds + (size_t)H16 * ES * 2);
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const _Float16 *Ub = U + (int64_t)b * H * E;
     const _Float16 *tb = tok + (int64_t)b * T * E;
@@ -238,6 +244,13 @@ __global__ __launch_bounds__(512) void rn50_pool_core_kernel(const _Float16 *__r
         }
     }
     __syncthreads();
+    if constexpr (SCG) {   // workspace -> the LDS of the u rows (every wave is past the score phase)
+        float *sl = reinterpret_cast<float *>(lds);
+        for (int i = tid * 4; i < T * H16; i += 512 * 4)   // (H16 % 16 == 0: whole float4s)
+            *reinterpret_cast<pf32x4 *>(sl + i) = *reinterpret_cast<const pf32x4 *>(sc + i);
+        sc = sl;
+        __syncthreads();
+    }
     // softmax over the T tokens of each head: a wave per head (lanes over the tokens); padding heads get zero weights
     for (int h = wave; h < H16; h += 8) {
         float *r = sc + h;
@@ -343,8 +356,16 @@ struct Rn50Layout {
     int S, T, E, out_pad;
     int64_t tok_rows, b_pad, q_rows;
     size_t act_elems;   // elements of one activation buffer
-    size_t zero, act[5], mean, tok, tok0, aexp, uvec, zvec, ofull, zbias, q, att, proj, total;
+    size_t zero, act[5], mean, tok, tok0, aexp, uvec, zvec, ofull, zbias, q, att, proj, scg, total;
+    bool pool_scg;   // the pool's score table goes through the workspace (rn50_pool_core_kernel<true>)
 };
+
+// LDS of rn50_pool_core_kernel: the u rows [H16][E + 8] fp16, and beside them (resident form) or after them (SCG) the
+// [T][H16] fp32 score table
+static size_t pool_lds_resident(int T, int E, int heads) {
+    const int H16 = (heads + 15) & ~15;
+    return (size_t)H16 * (E + 8) * 2 + (size_t)H16 * T * 4;
+}
 
 Rn50Layout rn50_layout(const mpreid_rn50_cfg *cfg, int B) {
     Rn50Layout v{};
@@ -379,6 +400,8 @@ Rn50Layout rn50_layout(const mpreid_rn50_cfg *cfg, int B) {
     v.q = take((size_t)v.b_pad * v.E * 2);
     v.att = take((size_t)v.b_pad * v.E * 2);
     v.proj = take((size_t)v.b_pad * v.out_pad * 4);
+    v.pool_scg = pool_lds_resident(v.T, v.E, cfg->heads) > 160 * 1024;
+    v.scg = v.pool_scg ? take((size_t)B * v.T * ((cfg->heads + 15) & ~15) * 4) : 0;
     v.total = off;
     return v;
 }
@@ -388,7 +411,12 @@ int rn50_check_cfg(const mpreid_rn50_cfg *c) {
     ARG_CHECK(c->img_h > 0 && c->img_w > 0 && c->img_h % 32 == 0 && c->img_w % 32 == 0);
     ARG_CHECK(c->width >= 16 && c->width % 16 == 0 && c->width <= 64 && c->n_blocks >= 4);
     ARG_CHECK(c->heads > 0 && (c->width * 32) % c->heads == 0 && (c->width * 32) / c->heads == 64);
-    ARG_CHECK(c->out_dim > 0 && c->out_dim % 8 == 0 && (c->img_h / 16) * (c->img_w / 16) + 1 <= 256);
+    ARG_CHECK(c->out_dim > 0 && c->out_dim % 8 == 0);
+    if ((c->img_h / 16) * (c->img_w / 16) + 1 > MPREID_RN50_MAX_TOKENS) {
+        mpreid_set_error("rn50 attention pool: token count %d > %d (MPREID_RN50_MAX_TOKENS, 512 x 512) not supported",
+                         (c->img_h / 16) * (c->img_w / 16) + 1, MPREID_RN50_MAX_TOKENS);
+        return MPREID_ERR_UNSUPPORTED;
+    }
     return 0;
 }
 
@@ -558,15 +586,30 @@ extern "C" int mpreid_rn50_forward(const mpreid_rn50_cfg *cfg, const mpreid_rn50
     }
     {
         const int H16 = (Hh + 15) & ~15;
-        const size_t lds = (size_t)H16 * (v.E + 8) * 2 + (size_t)H16 * v.T * 4;
-        ARG_CHECK(lds <= 160 * 1024 && v.E % 32 == 0 && H16 % 4 == 0);
-        static size_t lds_set = 0;
-        if (lds > 48 * 1024 && lds > lds_set) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(rn50_pool_core_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            lds_set = lds;
+        if (!v.pool_scg) {
+            const size_t lds = pool_lds_resident(v.T, v.E, Hh);
+            ARG_CHECK(lds <= 160 * 1024 && v.E % 32 == 0 && H16 % 4 == 0);
+            static size_t lds_set = 0;
+            if (lds > 48 * 1024 && lds > lds_set) {
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(rn50_pool_core_kernel<false>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                lds_set = lds;
+            }
+            hipLaunchKernelGGL(rn50_pool_core_kernel<false>, dim3(B), dim3(512), lds, stream, uvec, tok, v.T, v.E, Hh, zvec,
+                               nullptr);
+        } else {
+            const size_t lu = (size_t)H16 * (v.E + 8) * 2, ls = (size_t)H16 * v.T * 4;
+            const size_t lds = lu > ls ? lu : ls;
+            ARG_CHECK(lds <= 160 * 1024 && v.E % 32 == 0 && H16 % 4 == 0);
+            static size_t lds_set = 0;
+            if (lds > 48 * 1024 && lds > lds_set) {
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(rn50_pool_core_kernel<true>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                lds_set = lds;
+            }
+            hipLaunchKernelGGL(rn50_pool_core_kernel<true>, dim3(B), dim3(512), lds, stream, uvec, tok, v.T, v.E, Hh, zvec,
+                               (float *)(base + v.scg));
         }
-        hipLaunchKernelGGL(rn50_pool_core_kernel, dim3(B), dim3(512), lds, stream, uvec, tok, v.T, v.E, Hh, zvec);
         LAUNCH_CHECK();
         GemmArgs g{};   // out_h = Wv_h z_h + bv_h (all heads' rows against all of Wv; the gather keeps the diagonal blocks)
         g.A = zvec;

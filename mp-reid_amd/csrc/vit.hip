@@ -14,9 +14,10 @@
 //   qkv     fp16 [M pad][3W]        in_proj output, q | k | v column blocks, head h = cols [64h, 64h+64)
 //   hbuf    fp16 [M pad][4W]        MLP hidden after QuickGELU
 // Kernels: im2col (HBM), GEMM+epilogues (MFMA, gemm_f16.hip), LayerNorm (HBM), attention (MFMA +
-// LDS; L = 129 keys fit one workgroup), head (L2).
+// LDS; L = 129 keys fit one workgroup; 256 < L <= MPREID_VIT_MAX_TOKENS streams K / V through LDS), head (L2).
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 
 #include "gemm_f16.h"
 
@@ -889,6 +890,263 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8 || XKEY) ? 2 : 1) void attention_
 }
 
 // ---------------------------------------------------------------------------------------------
+// attention for long sequences (256 < L <= MPREID_VIT_MAX_TOKENS), fp16 and split modes: the "key on the lane" scheme of
+// the two kernels above, with K / V streamed through LDS in blocks of ATL_KB keys instead of resident for the whole head.
+//   grid (B * heads, groups): workgroup (pair, g) owns the query tiles g * tpg .. g * tpg + tpg - 1, one per wave (tpg <= 8;
+//   the other waves only stage).  A tile's arithmetic does not depend on g, tpg or the batch: rows are batch-independent.
+//   Per key block (two LDS buffers, one barrier per block; block j + 1 is requested into registers before block j is
+//   computed and written to the other buffer after it, cdna_hip_programming.md T14):
+//     S^T = K Q^T for the block's 16-key tiles, block max over the keys (in-lane + xor 16 / 32)
+//     m' = max(m, block max); O^T and the lane's partial row sum *= exp2((m - m') c)   (every block, no deferred max)
+//     P^T = exp2(S^T c - m' c) straight from the accumulators into O^T += V^T P^T
+//   The rescale precedes the exponentiation of the block's P and follows the previous block's complete P V, so nothing at
+//   the old scale is missed and nothing at the new one is scaled twice.
+// SPLIT: fp32 q | k | v in, K / V split into hi / lo fp16 pairs while staged, hi.hi' + lo.hi' + hi.lo' for every product and
+// P carrying 2^10, exactly the operand scheme of attention_split_kernel; O leaves as the fp16 pair [hi(W) | lo(W)].
+// Keys >= L (last block): rows clamped to L - 1 (finite copies), scores forced to -huge, so their P is 0; only the key
+// tiles / PV steps that hold a valid key run.
+// ---------------------------------------------------------------------------------------------
+constexpr int ATL_KB = 64;   // keys per block: four 16-key S^T tiles, two 32-key P V steps
+constexpr int ATL_NW = 8;    // waves per workgroup
+
+template <bool SPLIT>
+__global__ __launch_bounds__(64 * ATL_NW) void attention_long_kernel(const void *__restrict__ qkv_, int L, int W, int heads,
+                                                                     _Float16 *__restrict__ out, int nqt, int tpg) {
+    constexpr int NT = 64 * ATL_NW;
+    constexpr int ARR = ATL_KB * 128;               // bytes of one [KB][64] fp16 array
+    constexpr int BUF = (SPLIT ? 4 : 2) * ARR;      // Kh | Kl | Vh | Vl (split) or K | V (fp16)
+    constexpr int NST = SPLIT ? 2 : 1;              // 16-byte staging chunks per thread per array
+    static_assert(ATL_KB * (SPLIT ? 16 : 8) == NST * NT, "one block = NST staging chunks per thread");
+    static_assert(ATL_NW * 16 * 72 * 2 <= 2 * BUF, "the O patches reuse the two K / V buffers");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int pair = blockIdx.x, b = pair / heads, h = pair - b * heads;
+    const int64_t ld = 3 * (int64_t)W;
+    const int qt = blockIdx.y * tpg + wave;
+    const bool active = wave < tpg && qt < nqt;   // wave-uniform
+    const int nkb = (L + ATL_KB - 1) / ATL_KB;
+    const float scale_log2e = 0.125f * 1.44269504088896340736f;
+
+    typedef typename std::conditional<SPLIT, float, _Float16>::type T;
+    const T *base = reinterpret_cast<const T *>(qkv_) + (int64_t)b * L * ld + h * 64;
+
+    // staging registers: (fp16) one 16-byte chunk of K and of V; (split) two chunks of 4 floats of each
+    uint4 kr16 = make_uint4(0, 0, 0, 0), vr16 = kr16;
+    float4 krf[NST], vrf[NST];
+    auto stage_load = [&](int kb) {
+        if constexpr (SPLIT) {
+#pragma unroll
+            for (int i = 0; i < NST; ++i) {
+                const int idx = tid + i * NT, row = idx >> 4, c = idx & 15;
+                const int key = kb * ATL_KB + row, kc = key < L ? key : L - 1;
+                const float *p = reinterpret_cast<const float *>(base) + (int64_t)kc * ld + c * 4;
+                krf[i] = load_nt_f4(p + W);
+                vrf[i] = load_nt_f4(p + 2 * W);
+            }
+        } else {
+            const int row = tid >> 3, c = tid & 7;
+            const int key = kb * ATL_KB + row, kc = key < L ? key : L - 1;
+            const _Float16 *p = reinterpret_cast<const _Float16 *>(base) + (int64_t)kc * ld + c * 8;
+            kr16 = load_nt16(p + W);
+            vr16 = load_nt16(p + 2 * W);
+        }
+    };
+    auto stage_store = [&](int buf) {
+        unsigned char *Kb = smem + buf * BUF;
+        if constexpr (SPLIT) {
+            unsigned char *Kh = Kb, *Kl = Kb + ARR, *Vh = Kb + 2 * ARR, *Vl = Kb + 3 * ARR;
+#pragma unroll
+            for (int i = 0; i < NST; ++i) {
+                const int idx = tid + i * NT, row = idx >> 4, c = idx & 15;
+                h4_t hi, lo;
+                const int ko = row * 128 + (((c >> 1) ^ (row & 7)) << 4) + (c & 1) * 8;
+                split4(krf[i], hi, lo);
+                *reinterpret_cast<h4_t *>(Kh + ko) = hi;
+                *reinterpret_cast<h4_t *>(Kl + ko) = lo;
+                const int vo = row * 128 + (((c >> 1) ^ (((row >> 1) & 3) << 1)) << 4) + (c & 1) * 8;
+                split4(vrf[i], hi, lo);
+                *reinterpret_cast<h4_t *>(Vh + vo) = hi;
+                *reinterpret_cast<h4_t *>(Vl + vo) = lo;
+            }
+        } else {
+            unsigned char *Ks = Kb, *Vs = Kb + ARR;
+            const int row = tid >> 3, c = tid & 7;
+            *reinterpret_cast<uint4 *>(Ks + row * 128 + ((c ^ (row & 7)) << 4)) = kr16;
+            *reinterpret_cast<uint4 *>(Vs + row * 128 + ((c ^ (((row >> 1) & 3) << 1)) << 4)) = vr16;
+        }
+    };
+
+    // Q of the wave's tile (B operand: B[k = d][col = query], 8 consecutive d per lane per 32-wide k step); rows past L clamped
+    f16x8 qh[2], ql[2];
+    {
+        const int q = (active ? qt : 0) * 16 + fr;
+        const int qc = q < L ? q : L - 1;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            if constexpr (SPLIT) {
+                const float *qp = reinterpret_cast<const float *>(base) + (int64_t)qc * ld + ks * 32 + fq * 8;
+                const float4 a0 = *reinterpret_cast<const float4 *>(qp), a1 = *reinterpret_cast<const float4 *>(qp + 4);
+                const float qv[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+                split_pairs<8>(qv, qh[ks], ql[ks]);
+            } else {
+                qh[ks] = *reinterpret_cast<const f16x8 *>(reinterpret_cast<const _Float16 *>(base) + (int64_t)qc * ld + ks * 32 + fq * 8);
+                ql[ks] = qh[ks];
+            }
+        }
+    }
+
+    f32x4 o[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -3.0e38f, lsum = 0.f;   // running max (of the raw scores) of this lane's query column; this lane's partial row sum
+
+    stage_load(0);
+    stage_store(0);
+    __syncthreads();
+    for (int kb = 0; kb < nkb; ++kb) {
+        if (kb + 1 < nkb) stage_load(kb + 1);   // in flight while block kb is computed
+        if (active) {
+            const unsigned char *Kb = smem + (kb & 1) * BUF;
+            const unsigned char *Kh = Kb, *Kl = Kb + ARR;
+            const unsigned char *Vh = Kb + (SPLIT ? 2 : 1) * ARR, *Vl = Kb + 3 * ARR;
+            const int key0 = kb * ATL_KB;
+            const int nv = L - key0 < ATL_KB ? L - key0 : ATL_KB;   // valid keys of the block (>= 1)
+            const int ntile = (nv + 15) >> 4, nstep = (nv + 31) >> 5;
+            f32x4 s[4];
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt) {
+                s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (kt < ntile) {
+#pragma unroll
+                    for (int ks = 0; ks < 2; ++ks) {
+                        const int ko = (kt * 16 + fr) * 128 + (((ks * 4 + fq) ^ (lane & 7)) << 4);
+                        const f16x8 kh = *reinterpret_cast<const f16x8 *>(Kh + ko);
+                        s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, qh[ks], s[kt], 0, 0, 0);
+                        if constexpr (SPLIT) {
+                            const f16x8 kl = *reinterpret_cast<const f16x8 *>(Kl + ko);
+                            s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl, qh[ks], s[kt], 0, 0, 0);
+                            s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, ql[ks], s[kt], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+            if (nv < ATL_KB) {   // the last block: keys >= L
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (kt * 16 + fq * 4 + r >= nv) s[kt][r] = -3.0e38f;
+            }
+            float bmx = -3.0e38f;
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt) bmx = fmaxf(bmx, fmaxf(fmaxf(s[kt][0], s[kt][1]), fmaxf(s[kt][2], s[kt][3])));
+            bmx = xor16_32_max(bmx);
+            const float mn = fmaxf(m, bmx);
+            const float alpha = __builtin_amdgcn_exp2f((m - mn) * scale_log2e);   // 1 when the max did not move; 0 at block 0
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
+            lsum *= alpha;
+            m = mn;
+            // p = exp2(s c - m c) (split: times 2^10, see attention_split_kernel); masked keys give exp2(-huge) = 0
+            const float nmx = SPLIT ? fmaf(-mn, scale_log2e, 10.0f) : -mn * scale_log2e;
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float p = __builtin_amdgcn_exp2f(fmaf(s[kt][r], scale_log2e, nmx));
+                    s[kt][r] = p;
+                    lsum += p;
+                }
+            // O^T += V^T P^T over 32-key steps; P^T fragment element j <-> key 32*s2 + 16*(j>>2) + 4*fq + (j&3)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                if (s2 < nstep) {
+                    f16x8 ph, pl;
+                    if constexpr (SPLIT) {
+                        const float pv[8] = {s[2 * s2][0], s[2 * s2][1], s[2 * s2][2], s[2 * s2][3],
+                                             s[2 * s2 + 1][0], s[2 * s2 + 1][1], s[2 * s2 + 1][2], s[2 * s2 + 1][3]};
+                        split_pairs<8>(pv, ph, pl);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            ph[j] = (_Float16)s[2 * s2][j];
+                            ph[4 + j] = (_Float16)s[2 * s2 + 1][j];
+                        }
+                        pl = ph;
+                    }
+#pragma unroll
+                    for (int dt = 0; dt < 4; ++dt) {
+                        const int trq = fr >> 2, trp = fr & 3;
+                        const int row0 = s2 * 32 + fq * 4 + trq, row1 = row0 + 16;
+                        const int chunk = dt * 2 + (trp >> 1);
+                        const int o0 = row0 * 128 + ((chunk ^ (((row0 >> 1) & 3) << 1)) << 4) + (trp & 1) * 8;
+                        const int o1 = row1 * 128 + ((chunk ^ (((row1 >> 1) & 3) << 1)) << 4) + (trp & 1) * 8;
+                        typedef short s8_t __attribute__((ext_vector_type(8)));
+                        const att_s4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((att_lds_s4 *)(Vh + o0));
+                        const att_s4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((att_lds_s4 *)(Vh + o1));
+                        const s8_t vh8 = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+                        const f16x8 vh = __builtin_bit_cast(f16x8, vh8);
+                        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, ph, o[dt], 0, 0, 0);
+                        if constexpr (SPLIT) {
+                            const att_s4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((att_lds_s4 *)(Vl + o0));
+                            const att_s4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((att_lds_s4 *)(Vl + o1));
+                            const s8_t vl8 = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+                            const f16x8 vl = __builtin_bit_cast(f16x8, vl8);
+                            o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl, ph, o[dt], 0, 0, 0);
+                            o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, pl, o[dt], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+        }
+        if (kb + 1 < nkb) stage_store((kb + 1) & 1);   // that buffer was last read in block kb - 1, before the barrier below
+        __syncthreads();
+    }
+    // (after the last barrier both K / V buffers are free: they hold the waves' O patches)
+    if (!active) return;
+    const float sum = xor16_32_sum(lsum);
+    const float inv = 1.0f / sum;
+    constexpr int OS = 72;
+    _Float16 *ot = reinterpret_cast<_Float16 *>(smem) + wave * (16 * OS);
+    h4_t ohi[4], olo[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+        const float ovf[4] = {o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv};
+        if constexpr (SPLIT) {
+            split_pairs<4>(ovf, ohi[dt], olo[dt]);
+        } else {
+            ohi[dt] = h4_t{(_Float16)ovf[0], (_Float16)ovf[1], (_Float16)ovf[2], (_Float16)ovf[3]};
+            olo[dt] = ohi[dt];
+        }
+    }
+#pragma unroll
+    for (int part = 0; part < (SPLIT ? 2 : 1); ++part) {
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+            *reinterpret_cast<h4_t *>(ot + fr * OS + dt * 16 + fq * 4) = part == 0 ? ohi[dt] : olo[dt];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int row = it * 8 + (lane >> 3), ch = lane & 7;
+            const uint4 v = *reinterpret_cast<const uint4 *>(ot + row * OS + ch * 8);
+            const int qrow = qt * 16 + row;
+            if (qrow < L) {
+                if constexpr (SPLIT)
+                    store_nt16(out + ((int64_t)b * L + qrow) * 2 * W + part * W + h * 64 + ch * 8, v);
+                else
+                    store_nt16(out + ((int64_t)b * L + qrow) * W + h * 64 + ch * 8, v);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // head: ln_post on the CLS row, CLS @ proj, optional eval-BN necks, concat -> [B][W + out_dim]
 // model/clip/model.py:471-474, model/make_model.py:98-115
 // ---------------------------------------------------------------------------------------------
@@ -1024,9 +1282,9 @@ static int vit_check_cfg(const mpreid_vit_cfg *c) {
         return MPREID_ERR_UNSUPPORTED;
     }
     ARG_CHECK(c->h_res == (c->img_h - c->patch) / c->stride + 1 && c->w_res == (c->img_w - c->patch) / c->stride + 1);
-    if (c->h_res * c->w_res + 1 > 256) {
-        mpreid_set_error("token count %d > 256 not supported by the LDS-resident attention kernel",
-                         c->h_res * c->w_res + 1);
+    if (c->h_res * c->w_res + 1 > MPREID_VIT_MAX_TOKENS) {
+        mpreid_set_error("token count %d > %d (MPREID_VIT_MAX_TOKENS, 512 x 512 at stride 16) not supported by the attention kernels",
+                         c->h_res * c->w_res + 1, MPREID_VIT_MAX_TOKENS);
         return MPREID_ERR_UNSUPPORTED;
     }
     return MPREID_OK;
@@ -1109,8 +1367,32 @@ static int launch_attention_split(const float *qkv, int B, int L, int W, int hea
     return MPREID_OK;
 }
 
+// L > 256: the streaming kernel.  Query tiles are dealt to ceil(tiles / 8) workgroups per (image, head) as evenly as the
+// 8 waves allow (L = 257: 17 tiles as 6 + 6 + 5; L = 442: 28 as 7 x 4); a CLS-only call is one workgroup with one tile.
+template <bool SPLIT>
+static int launch_attention_long(const void *qkv, int B, int L, int W, int heads, _Float16 *out, int q_tiles,
+                                 hipStream_t stream) {
+    const size_t lds = (size_t)2 * (SPLIT ? 4 : 2) * ATL_KB * 128;
+    static PerDeviceOnce attr_once;
+    const int rc = attr_once.run([&]() -> int {
+        if (lds > 48 * 1024)
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(attention_long_kernel<SPLIT>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        return MPREID_OK;
+    });
+    if (rc) return rc;
+    const int nqt = (q_tiles > 0) ? q_tiles : (L + 15) / 16;
+    const int groups = (nqt + ATL_NW - 1) / ATL_NW;
+    const int tpg = (nqt + groups - 1) / groups;
+    hipLaunchKernelGGL((attention_long_kernel<SPLIT>), dim3((unsigned)(B * heads), (unsigned)groups), dim3(64 * ATL_NW), lds,
+                       stream, qkv, L, W, heads, out, nqt, tpg);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
 static int attention_split_dispatch(const float *qkv, int B, int L, int W, int heads, _Float16 *out, int q_tiles,
                                     hipStream_t stream) {
+    if (L > 256) return launch_attention_long<true>(qkv, B, L, W, heads, out, q_tiles, stream);
     const int kt = (L + 15) / 16;
     if (kt <= 2) return launch_attention_split<2, 2>(qkv, B, L, W, heads, out, q_tiles, stream);
     if (L == 129) return launch_attention_split<8, 4, true>(qkv, B, L, W, heads, out, q_tiles, stream);   // ViT-B/16 at 256 x 128
@@ -1123,6 +1405,7 @@ static int attention_split_dispatch(const float *qkv, int B, int L, int W, int h
 // K/V staging of a CLS-only call (one query tile) is still spread over 256 threads
 static int attention_dispatch(const _Float16 *qkv, int B, int L, int W, int heads, _Float16 *out, int q_tiles,
                               hipStream_t stream) {
+    if (L > 256) return launch_attention_long<false>(qkv, B, L, W, heads, out, q_tiles, stream);
     const int kt = (L + 15) / 16;
     if (kt <= 2) return launch_attention<2, 2, true>(qkv, B, L, W, heads, out, q_tiles, stream);
     if (kt <= 10) {
@@ -1383,6 +1666,57 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float *__restr
     }
 }
 
+// The same per query, for L whose K and V do not fit the LDS at once (L * 512 B > 160 KB, L > 320): K / V pass through LDS in
+// chunks of ATF_CHUNK keys.  grid (B * heads, ceil(L / 256)): one query per thread, so a thread's state is one row and every
+// thread of the workgroup takes part in the staging; per query the key order and every operation are those of the kernel above.
+constexpr int ATF_CHUNK = 128;   // keys per chunk: 64 KB of LDS
+__global__ __launch_bounds__(256) void attention_f32_chunked_kernel(const float *__restrict__ qkv, int L, int W, int heads,
+                                                                    float *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float *Ks = reinterpret_cast<float *>(smem), *Vs = Ks + ATF_CHUNK * 64;
+    const int b = blockIdx.x / heads, h = blockIdx.x % heads, tid = threadIdx.x;
+    const int t = blockIdx.y * 256 + tid;
+    const bool valid = t < L;
+    const float *base = qkv + (int64_t)b * L * 3 * W + h * 64;
+    float q[64], acc[64];
+#pragma unroll
+    for (int c = 0; c < 64; c += 4) {
+        const float4 v = valid ? *reinterpret_cast<const float4 *>(base + (int64_t)t * 3 * W + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        q[c] = v.x * 0.125f; q[c + 1] = v.y * 0.125f; q[c + 2] = v.z * 0.125f; q[c + 3] = v.w * 0.125f;   // 64^-0.5, exact
+        acc[c] = acc[c + 1] = acc[c + 2] = acc[c + 3] = 0.0f;
+    }
+    float m = -3.402823466e+38f, l = 0.0f;
+    for (int j0 = 0; j0 < L; j0 += ATF_CHUNK) {
+        const int n = L - j0 < ATF_CHUNK ? L - j0 : ATF_CHUNK;
+        __syncthreads();   // every thread is done with the previous chunk
+        for (int idx = tid; idx < n * 16; idx += 256) {
+            const int row = idx >> 4, c4 = (idx & 15) * 4;
+            const float *src = base + (int64_t)(j0 + row) * 3 * W;
+            *reinterpret_cast<float4 *>(Ks + row * 64 + c4) = *reinterpret_cast<const float4 *>(src + W + c4);
+            *reinterpret_cast<float4 *>(Vs + row * 64 + c4) = *reinterpret_cast<const float4 *>(src + 2 * W + c4);
+        }
+        __syncthreads();
+        if (valid) {
+            for (int j = 0; j < n; ++j) {
+                const float *kr = Ks + j * 64, *vr = Vs + j * 64;
+                float s = 0.0f;
+#pragma unroll
+                for (int c = 0; c < 64; ++c) s = fmaf(q[c], kr[c], s);
+                const float mn = fmaxf(m, s);
+                const float corr = expf(m - mn), pj = expf(s - mn);
+                l = l * corr + pj;
+#pragma unroll
+                for (int c = 0; c < 64; ++c) acc[c] = fmaf(pj, vr[c], acc[c] * corr);
+                m = mn;
+            }
+        }
+    }
+    if (!valid) return;
+    float *o = out + ((int64_t)b * L + t) * W + h * 64;
+#pragma unroll
+    for (int c = 0; c < 64; ++c) o[c] = __fdiv_rn(acc[c], l);
+}
+
 struct VitLayoutF32 {
     int L, P, M, Kp;
     size_t patches, x, a, qkv, hbuf, y_cls, total;
@@ -1450,9 +1784,12 @@ static int vit_forward_f32_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weig
                            w->ln_pre_g, w->ln_pre_b, (void *)x, (int64_t)W);
         LAUNCH_CHECK();
     }
-    const size_t att_lds = (size_t)L * 64 * 4 * 2;
+    // K / V of a head resident in LDS where they fit (L <= 320), streamed in chunks above that
+    const bool att_chunked = (size_t)L * 64 * 4 * 2 > 160 * 1024;
+    const size_t att_lds = att_chunked ? (size_t)ATF_CHUNK * 64 * 4 * 2 : (size_t)L * 64 * 4 * 2;
     if (att_lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(attention_f32_kernel),
+        HIP_TRY(hipFuncSetAttribute(att_chunked ? reinterpret_cast<const void *>(attention_f32_chunked_kernel)
+                                                : reinterpret_cast<const void *>(attention_f32_kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)att_lds));
     for (int l = 0; l < cfg->layers; ++l) {
         const mpreid_vit_layer &ly = w->layers[l];
@@ -1461,8 +1798,12 @@ static int vit_forward_f32_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weig
         LAUNCH_CHECK();
         if ((rc = mpreid_gemm_f32_linear(a, (const float *)ly.in_proj_w, v.M, 3 * W, W, ly.in_proj_b, qkv, 3 * W, F32_LIN, stream)))
             return rc;
-        hipLaunchKernelGGL(attention_f32_kernel, dim3((unsigned)(B * cfg->heads)), dim3(256), att_lds, stream, qkv, L, W,
-                           cfg->heads, a);
+        if (att_chunked)
+            hipLaunchKernelGGL(attention_f32_chunked_kernel, dim3((unsigned)(B * cfg->heads), (unsigned)((L + 255) / 256)), dim3(256),
+                               att_lds, stream, qkv, L, W, cfg->heads, a);
+        else
+            hipLaunchKernelGGL(attention_f32_kernel, dim3((unsigned)(B * cfg->heads)), dim3(256), att_lds, stream, qkv, L, W,
+                               cfg->heads, a);
         LAUNCH_CHECK();
         if ((rc = mpreid_gemm_f32_linear(a, (const float *)ly.out_proj_w, v.M, W, W, ly.out_proj_b, x, W, F32_LIN_RES, stream)))
             return rc;
