@@ -45,6 +45,8 @@ extern "C" {
  *   jaccard_wave (-1 auto), jaccard_wave_rows (10240), jaccard_table (0)   form of the Jaccard stage
  *   csc_atomic (0)                       inverted index: the round-1 atomic build
  *   rerank_overlap (-1 auto)             exact query rows in line (0) / on a side stream (1)
+ *   wide_sort_lds (4096), wide_jaccard_rows (24576)   WIDE re-ranking: largest neighbour sort held in LDS (larger ones
+ *                           use workspace scratch), gallery rows per Jaccard chunk -- same bits either way
  *   verbose (0)             occupancy messages on stderr
  * Unknown keys are reported on stderr and ignored.  Switches that change RESULTS exist only in -DMPREID_ABLATION builds. */
 
@@ -100,14 +102,14 @@ typedef struct {
     int64_t krecip_r_sum; /* sum over rows of |R(i, k1)| (k-reciprocal set sizes before expansion) */
     int64_t fallback_rows;/* sparse algorithm: rows whose candidate list could not be certified (done densely) */
     int64_t cand_total;   /* sparse algorithm: neighbour candidates emitted by the fused GEMM (sum over rows) */
-    int32_t algo;         /* MPREID_RERANK_DENSE / _SPARSE / _SPARSE_SPLIT3: what the call actually ran */
+    int32_t algo;         /* MPREID_RERANK_DENSE / _SPARSE / _SPARSE_SPLIT3 / _WIDE: what the call actually ran */
     /* filled when timing != 0 (hipEvents on the stream).  DENSE: gemm = N x N exact distances, topk = row maxima +
      * neighbour selection.  SPARSE: gemm = fp16 operands + sample pass + thresholds + fused candidate GEMM, topk =
      * exact refinement + fallback rows, dq = exact distance rows of the queries. */
     float ms_gemm, ms_topk, ms_krecip, ms_qe, ms_csc, ms_jaccard, ms_total, ms_dq;
 } mpreid_rerank_stats;
 
-/* Two algorithms, the same bits out (tests/test_gpu_rerank.py):
+/* Three algorithms, the same bits out (tests/test_gpu_rerank.py, tests/test_gpu_rerank_wide.py):
  *   DENSE   the N x N fp32 distance matrix is computed (exact fp32 MFMA), kept in HBM and scanned for the first
  *           max(k1+1, k2) neighbours of every row.  Any N, local_distmat / only_local supported.
  *   SPARSE  the N x N matrix is never materialised: a one-pass fp16 GEMM on the matrix cores emits, per row, the
@@ -117,7 +119,12 @@ typedef struct {
  *           fall back to the dense computation of that row.  Needs N >= 2048, max(k1+1, k2) <= 64, no local_distmat.
  *   AUTO    SPARSE when it applies, else DENSE.  A sparse call may return MPREID_ERR_RETRY_DENSE (degenerate data:
  *           too many fallback rows, a query-expansion row above 4096 entries, row norms >= 3e4): repeat it with
- *           MPREID_RERANK_DENSE and a workspace sized for DENSE. */
+ *           MPREID_RERANK_DENSE and a workspace sized for DENSE.  AUTO never chooses WIDE.
+ *   WIDE    DENSE's arithmetic for ANY k1 >= 0, k2 >= 1 (clamped against N as numpy slicing clamps them) and any N whose
+ *           workspace fits the device: every table whose size grows with k (selection keys, reciprocity positions,
+ *           expansion lists, weights, query-expansion accumulators, the Jaccard stage's per-query tables) lives in the
+ *           workspace instead of LDS.  local_distmat / only_local supported.  A completeness path: several times slower
+ *           than DENSE where both apply (DESIGN.md section 2 has the measured ratio). */
 #define MPREID_RERANK_AUTO 0
 #define MPREID_RERANK_DENSE 1
 #define MPREID_RERANK_SPARSE 2
@@ -126,10 +133,15 @@ typedef struct {
  * and the Jaccard term are bit-identical to the other modes, |final - exact final| <= lambda * 1e-6 / max.  Never chosen
  * by AUTO. */
 #define MPREID_RERANK_SPARSE_SPLIT3 3
+#define MPREID_RERANK_WIDE 4
 /* Bytes of device workspace re_ranking needs for this problem (DENSE: dominated by the N x N fp32 distance matrix,
  * 4*N*N; SPARSE: by the sample distances N*N/4 bytes and the query rows 4*nq*N). */
 size_t mpreid_rerank_workspace_bytes(int64_t nq, int64_t ng, int d, int k1, int k2, int has_local);      /* DENSE */
 size_t mpreid_rerank_workspace_bytes_ex(int64_t nq, int64_t ng, int d, int k1, int k2, int has_local, int algo);
+/* 1 when `algo` accepts this problem, 0 when the call would end with MPREID_ERR_UNSUPPORTED for one of the limits below
+ * (or the arguments are invalid).  No side effects, no device needed, the launchers' own expressions: ask it before
+ * choosing an algorithm instead of retrying a refused call.  AUTO: SPARSE applies, or DENSE fits. */
+int mpreid_rerank_fits(int64_t nq, int64_t ng, int d, int k1, int k2, int has_local, int algo);
 
 /* re_ranking(probFea, galFea, k1, k2, lambda_value, local_distmat=None, only_local=False)
  *   q [nq][d], g [ng][d] fp32 device; local_dev: NULL or [N][N] fp32 device (N = nq+ng);
@@ -138,12 +150,26 @@ size_t mpreid_rerank_workspace_bytes_ex(int64_t nq, int64_t ng, int d, int k1, i
  * float16 and lambda to float32.  The call synchronises `stream` internally (sizes of the sparse
  * structures are read back) and returns after the result is complete.
  * stats may be NULL; with timing != 0 per-stage times are measured with hipEvents on `stream`.
- * Limits (the reference has none, utils/reranking.py:53-54; it is called with k1 = 50, k2 = 15, utils/metrics.py:127):
+ * Limits (the reference has none, utils/reranking.py:53-54; it is called with k1 = 50, k2 = 15, utils/metrics.py:127).
+ * DENSE, SPARSE and AUTO have two (mpreid_rerank_fits answers them without a call):
  *   max(k1 + 1, k2) <= 256 -- the neighbour selection sorts its winners in one 256-entry LDS network and the reciprocity
  *   masks are 256 bits per row -> MPREID_ERR_UNSUPPORTED above that;
  *   the expansion lists of one row live in LDS: 8 * min(N, (k1 + 1) * (1 + ceil(k1 / 2))) + N / 8 + 8 * (k1 + 1) + 2 KB must
- *   fit a workgroup's 160 KB, i.e. k1 <= ~190 at N >= 20 000 (k1 <= 255 for N <= 18 000) -> hipErrorInvalidValue from the
- *   launch configuration above that (a loud failure, never a wrong result);
+ *   fit a workgroup's 160 KB, i.e. k1 <= ~190 at N >= 20 000 (k1 <= 255 for N <= 18 000) -> MPREID_ERR_UNSUPPORTED above
+ *   that (a loud failure, never a wrong result).  (Their query-expansion and Jaccard kernels also keep 8 and 14 bytes of
+ *   LDS per entry of the LARGEST V_qe row, a data-dependent size: a call inside the two limits whose rows grow past
+ *   ~11 000 entries ends with MPREID_ERR_UNSUPPORTED as well.)
+ * WIDE has neither: N = nq + ng < 2^31 - 64 and the workspace are its only limits.  Its workspace, with K = min(k1 + 1, N),
+ * KR = max(K, min(k2, N)), vcap = min(K * (1 + half_k1), N), qcap = min(N, k2 * vcap) (0 when k2 = 1), fcap = qcap or vcap
+ * when k2 = 1, P = KR rounded up to a power of two, W = min(N, 1024) workgroups, every term rounded up to 256 bytes:
+ *   4 N d + 4 N + 4 N ld (x 2 with local_distmat; ld = N rounded up to 64) + 4 N            features, norms, D, MT, row max
+ *   + 4 N KR + 8 N K + 4 N K + 8 W P (only when P > 4096)                                   neighbour table, index-sorted copy,
+ *                                                                                           reciprocity positions, sort scratch
+ *   + 8 N + 6 N vcap + 4 W vcap                                                             V rows, weight scratch
+ *   + 4 N + 6 N qcap + 4 W N                                                                V_qe rows, accumulator rows
+ *   + 12 (N + 1) + 6 ng fcap + 64                                                           inverted index, counters
+ * (mpreid_rerank_workspace_bytes_ex(..., MPREID_RERANK_WIDE) returns it: 6.7 GB at N = 20 000, d = 768, k = 50 / 15.)
+ * The row-sharded phases below (mpreid_rr_*, mpreid/distributed.py) run the DENSE / SPARSE kernels and keep the two limits.
  *   N = nq + ng < 2^31 - 64. */
 /* mpreid_rerank_f32 (+ mpreid_rerank_workspace_bytes, mpreid_rerank_debug_copy) is the DENSE algorithm: it never returns
  * the data-dependent MPREID_ERR_RETRY_DENSE.  mpreid_rerank_f32_ex takes the algorithm (AUTO / SPARSE: faster, may ask for

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("MPREID_LIB") or os.path.join(_HERE, "libmpreid_hip.so
 GEMM_F32_EXACT = 0
 GEMM_F16_FAST = 1
 GEMM_F16_SPLIT3 = 2
-RERANK_AUTO, RERANK_DENSE, RERANK_SPARSE, RERANK_SPARSE_SPLIT3 = 0, 1, 2, 3
+RERANK_AUTO, RERANK_DENSE, RERANK_SPARSE, RERANK_SPARSE_SPLIT3, RERANK_WIDE = 0, 1, 2, 3, 4
 ERR_RETRY_DENSE = -5
 
 #: every symbol include/mpreid.h declares (tests check the library exports all of them)
@@ -24,7 +24,7 @@ SYMBOLS = [
     "mpreid_sqnorm_f32", "mpreid_l2_normalize_f32", "mpreid_distance_workspace_bytes",
     "mpreid_euclidean_distance_f32", "mpreid_cosine_similarity_f32",
     "mpreid_rerank_workspace_bytes", "mpreid_rerank_f32", "mpreid_rerank_debug_copy",
-    "mpreid_rerank_workspace_bytes_ex", "mpreid_rerank_f32_ex", "mpreid_rerank_debug_copy_ex",
+    "mpreid_rerank_workspace_bytes_ex", "mpreid_rerank_f32_ex", "mpreid_rerank_debug_copy_ex", "mpreid_rerank_fits",
     "mpreid_eval_rank_positions", "mpreid_rr_dist_rows", "mpreid_rr_vcap", "mpreid_rr_krecip", "mpreid_rr_krecip_scratch_bytes",
     "mpreid_rr_sparse_workspace_bytes", "mpreid_rr_neighbours_sparse", "mpreid_rr_krecip_sparse", "mpreid_rr_pack_rows", "mpreid_rr_rowptr", "mpreid_rr_ell_to_csr", "mpreid_rr_csr_to_ell", "mpreid_rr_qe_count",
     "mpreid_rr_qe_fill", "mpreid_rr_jaccard", "mpreid_rr_jaccard_hist_bytes",
@@ -181,6 +181,8 @@ def load():
     L.mpreid_rerank_debug_copy.argtypes = [vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp]
     L.mpreid_rerank_workspace_bytes_ex.restype = sz
     L.mpreid_rerank_workspace_bytes_ex.argtypes = [i64, i64, i32, i32, i32, i32, i32]
+    L.mpreid_rerank_fits.restype = i32
+    L.mpreid_rerank_fits.argtypes = [i64, i64, i32, i32, i32, i32, i32]
     L.mpreid_rerank_f32_ex.restype = i32
     L.mpreid_rerank_f32_ex.argtypes = [vp, vp, i64, i64, i32, i32, i32, f64, vp, i32, vp, i64, vp, sz, vp,
                                        C.POINTER(RerankStats), i32, i32]

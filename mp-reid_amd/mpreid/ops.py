@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import GEMM_F16_FAST, GEMM_F16_SPLIT3, GEMM_F32_EXACT  # noqa: F401  (re-exported)
-from ._lib import RERANK_AUTO, RERANK_DENSE, RERANK_SPARSE, RERANK_SPARSE_SPLIT3  # noqa: F401
+from ._lib import RERANK_AUTO, RERANK_DENSE, RERANK_SPARSE, RERANK_SPARSE_SPLIT3, RERANK_WIDE  # noqa: F401
 
 _ws_cache: Dict[tuple, torch.Tensor] = {}
 
@@ -114,6 +114,9 @@ def re_ranking(q, g, k1: int, k2: int, lambda_value: float, local_distmat=None, 
     call that hits a data-dependent capacity is repeated densely), RERANK_DENSE, RERANK_SPARSE -- same bits;
     RERANK_SPARSE_SPLIT3: the sparse algorithm with the blend term's distance rows from the fp16 matrix cores (3-term
     split): neighbour table / V / V_qe / Jaccard term bit-identical, |final - exact| <= lambda * 1e-6 / max.
+    RERANK_WIDE: the dense arithmetic for any k1 / k2 (AUTO / DENSE / SPARSE refuse max(k1 + 1, k2) > 256 and expansion
+    lists beyond a workgroup's LDS, include/mpreid.h "Limits"; ``rerank_fits`` tells beforehand) -- same bits, slower; never
+    chosen by AUTO here (utils.reranking, the reference-signature layer, switches to it by itself).
     ws_tag: name of the cached workspace; calls that run CONCURRENTLY on different streams need different tags (the C
     entry point is re-entrant per stream with caller-owned workspaces)."""
     dev = _lib.require_gpu()
@@ -148,6 +151,12 @@ def re_ranking(q, g, k1: int, k2: int, lambda_value: float, local_distmat=None, 
                                              C.c_void_p(vq.ctypes.data), _lib.stream_ptr(), int(stats["algo"])),
                "mpreid_rerank_debug_copy_ex")
     return out, stats, rank, vc, vq
+
+
+def rerank_fits(nq: int, ng: int, d: int, k1: int, k2: int, has_local: bool = False, algo: int = _lib.RERANK_AUTO) -> bool:
+    """True when ``algo`` accepts the problem, False when re_ranking would refuse it for one of the documented limits
+    (mpreid_rerank_fits: no GPU needed, no side effects)."""
+    return bool(_lib.load().mpreid_rerank_fits(int(nq), int(ng), int(d), int(k1), int(k2), int(bool(has_local)), int(algo)))
 
 
 def gemm_f16_nt(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
