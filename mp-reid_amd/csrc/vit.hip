@@ -1323,8 +1323,8 @@ static int launch_attention(const _Float16 *qkv, int B, int L, int W, int heads,
                 &occ, reinterpret_cast<const void *>(attention_kernel<KTP, NW, EXACT>), 64 * NW, lds));
             blocks_per_cu_dev[slot] = occ > 0 ? occ : 1;
             if (mpreid_tune("verbose", 0))
-                fprintf(stderr, "[mpreid] attention<%d,%d> on device %d: %d workgroups/CU by the occupancy API (lds %zu B, %d threads)\n",
-                        KTP, NW, dev, occ, lds, 64 * NW);
+                fprintf(stderr, "[mpreid] attention<%d,%d,%s> on device %d: %d workgroups/CU by the occupancy API (lds %zu B, %d threads)\n",
+                        KTP, NW, EXACT ? "EXACT" : "MASKALL", dev, occ, lds, 64 * NW);
         }
         blocks_per_cu = blocks_per_cu_dev[slot];
     }
@@ -1348,6 +1348,12 @@ static int launch_attention_split(const float *qkv, int B, int L, int W, int hea
         if (lds > 48 * 1024)
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(attention_split_kernel<KTP, NW, XKEY>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (mpreid_tune("verbose", 0)) {   // once per instantiation and device, like launch_attention's line
+            int dev = 0;
+            HIP_TRY(hipGetDevice(&dev));
+            fprintf(stderr, "[mpreid] attention_split<%d,%d%s> on device %d: lds %zu B, %d threads\n", KTP, NW, XKEY ? ",XKEY" : "",
+                    dev, lds, 64 * NW);
+        }
         return MPREID_OK;
     });
     if (rc) return rc;
@@ -1378,6 +1384,12 @@ static int launch_attention_long(const void *qkv, int B, int L, int W, int heads
         if (lds > 48 * 1024)
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(attention_long_kernel<SPLIT>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (mpreid_tune("verbose", 0)) {
+            int dev = 0;
+            HIP_TRY(hipGetDevice(&dev));
+            fprintf(stderr, "[mpreid] attention_long<%s> on device %d: lds %zu B, %d threads\n", SPLIT ? "split" : "fp16", dev, lds,
+                    64 * ATL_NW);
+        }
         return MPREID_OK;
     });
     if (rc) return rc;
@@ -1422,8 +1434,7 @@ static int attention_dispatch(const _Float16 *qkv, int B, int L, int W, int head
     if (kt <= 14)
         return kt >= 13 ? launch_attention<14, 8, true>(qkv, B, L, W, heads, out, q_tiles, stream)
                         : launch_attention<14, 8, false>(qkv, B, L, W, heads, out, q_tiles, stream);
-    return kt >= 15 ? launch_attention<16, 8, true>(qkv, B, L, W, heads, out, q_tiles, stream)
-                    : launch_attention<16, 8, false>(qkv, B, L, W, heads, out, q_tiles, stream);
+    return launch_attention<16, 8, true>(qkv, B, L, W, heads, out, q_tiles, stream);   // kt is 15 or 16: always EXACT
 }
 
 static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const float *img,
