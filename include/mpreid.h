@@ -207,6 +207,20 @@ int mpreid_eval_rank_positions(const float *dist_dev, int64_t ld, int nq, int ng
                                const int64_t *g_pids_dev, int rcap, int32_t *pos_out_dev, int32_t *cnt_out_dev,
                                mpreid_stream_t stream);
 
+/* The same under the Market-1501 protocol: for every query the gallery items with the query's pid AND the query's camera
+ * are junk and leave the ranking -- the filter the reference's eval_func promises (utils/metrics.py:28-88, docstring
+ * :29-31), keeps commented out at line 54, and runs in its other evaluation tail
+ * (processor/processor_uniprompt_stage2.py:476-505).  A gallery item is RELEVANT when it has the query's pid and is not
+ * junk; its position is the number of KEPT (non-junk) items with a smaller (distance, gallery index) key.
+ * pos_out [nq][rcap] int32: the ascending positions of the relevant items among the kept ones, padded with -1;
+ * cnt_out [nq] = number of relevant items (0: the query is invalid under the protocol), or -1 when the row exceeds the
+ * LDS capacity.  LIMIT: relevant AND junk keys share the sorted list in LDS, so the count that hits min(rcap, 8192) is the
+ * number of PID MATCHES of the query (relevant + junk), not the number of relevant items: size rcap from the pid counts,
+ * as for mpreid_eval_rank_positions.  The camera ids are read for pid matches only; the pass over the row reads no labels. */
+int mpreid_eval_rank_positions_cam(const float *dist_dev, int64_t ld, int nq, int ng, const int64_t *q_pids_dev,
+                                   const int64_t *g_pids_dev, const int64_t *q_camids_dev, const int64_t *g_camids_dev,
+                                   int rcap, int32_t *pos_out_dev, int32_t *cnt_out_dev, mpreid_stream_t stream);
+
 /* ---- row-sharded re-ranking: the same kernels, phase by phase over a row range ------------
  * Rows [r_lo, r_lo+rows) of the N x N problem belong to the calling rank; between the phases the caller
  * all-gathers (RCCL) the rank table, the sparse V rows and the sparse V_qe rows.  mpreid/distributed.py

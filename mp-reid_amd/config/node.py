@@ -84,6 +84,10 @@ def make_defaults():
         "TEST": {"IMS_PER_BATCH": 64, "RE_RANKING": False, "WEIGHT": "", "NECK_FEAT": "before", "FEAT_NORM": "yes",
                  "DIST_MAT": "dist_mat.npy", "EVAL": False,
                  "DISTANCE_MODE": "exact", "RERANK_ALGO": "exact",   # not reference keys: see processor.do_inference
+                 # not a reference key: True evaluates under the Market-1501 protocol -- for each query the gallery images
+                 # of the same identity from the same camera are removed (utils/metrics.py; the reference's eval_func
+                 # keeps that line commented out, utils/metrics.py:54)
+                 "REMOVE_SAME_CAM": False,
                  # Uni-Prompt evaluation (reference config/defaults.py:331-344)
                  "TTA_ENABLED": False, "TTPT": {"ENABLED": False, "LR": 0.001, "STEPS": 5, "TEMPERATURE": 0.07}},
         "OUTPUT_DIR": "",

@@ -10,6 +10,7 @@
 //      (value, index) order — exactly the position a stable argsort gives it.
 // HBM-bound: 4*nq*ng bytes read once (+ pids); Market-1501 scale: 214 MB.
 // The host finishes CMC / AP from the positions (float64, numpy's pairwise order) — utils/metrics.py.
+// eval_rank_kernel<true> does the same under the Market-1501 protocol (same-identity same-camera gallery items removed).
 #include "common.h"
 
 constexpr int EV_CAP_MAX = 8192; // max relevant gallery items per query handled on the GPU (64 KB of keys + 32 KB of counters)
@@ -29,19 +30,35 @@ __device__ __forceinline__ unsigned long long ev_key(float f, unsigned idx) {
 // C * (R + 1) <= hw (at most 64) copies of them, copy = lane & (C - 1).  Round 5's single copy took one LDS atomic per
 // gallery item into ~22 addresses (Market-1501: ~21 relevant items per query): up to 64 lanes of an instruction on one
 // address, serialised by the LDS atomic unit; with R < 32 every lane owns its copy and no two lanes ever collide.
+//
+// CAM = true is the Market-1501 protocol (the filter the reference promises at utils/metrics.py:29-31, keeps commented out
+// at :54 and runs at processor/processor_uniprompt_stage2.py:476-505): gallery items with the query's pid AND the query's
+// camera are JUNK -- removed from the ranking.  Junk items are pid hits, so step 1 reads g_cams only for the hits and the
+// sorted list holds relevant and junk keys together (R = pid hits).  The junk flag is bit 0 of the key's index field,
+// BELOW the gallery index (idx = 2 j + junk, j < 2^31): j is unique, so two keys never compare on the flag and the list
+// keeps its (distance, gallery index) order on ties; no second LDS array follows the sort's swaps.  Step 2 buckets every
+// gallery item as before (junk and relevant items land in their own buckets); step 3 subtracts from a relevant item's
+// position the number of junk keys sorted in front of it and writes the relevant entries compacted.
+// CAM = false is the kernel without the filter: q_cams / g_cams are not read (the launcher passes null) and its
+// instructions are those the non-template kernel compiled to.
+template <bool CAM>
 __global__ __launch_bounds__(256) void eval_rank_kernel(const float *__restrict__ dist, int64_t ld, int nq, int ng,
                                                         const long long *__restrict__ q_pids,
-                                                        const long long *__restrict__ g_pids, int rcap, int cap, int hw,
+                                                        const long long *__restrict__ g_pids,
+                                                        const long long *__restrict__ q_cams,
+                                                        const long long *__restrict__ g_cams, int rcap, int cap, int hw,
                                                         int *__restrict__ pos_out, int *__restrict__ cnt_out) {
     extern __shared__ unsigned long long ev_lds[];
     unsigned long long *rel = ev_lds;
     unsigned *hist = reinterpret_cast<unsigned *>(ev_lds + cap);
     __shared__ unsigned s_cnt;
-    __shared__ int s_wave[4];
+    __shared__ int s_wave[CAM ? 8 : 4]; // [4..7]: wave totals of the junk flags
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.x;
     const float *row = dist + (int64_t)q * ld;
     const long long pid = q_pids[q];
+    long long cam = 0;
+    if constexpr (CAM) cam = q_cams[q];
     if (tid == 0) s_cnt = 0;
     __syncthreads();
     // 1. relevant items (wave-aggregated reservation: one LDS atomic per wave and 64 items)
@@ -55,7 +72,11 @@ __global__ __launch_bounds__(256) void eval_rank_kernel(const float *__restrict_
             base = __shfl(base, 0, 64);
             if (hit) {
                 const unsigned p = base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-                if (p < (unsigned)cap) rel[p] = ev_key(row[j], (unsigned)j);
+                if constexpr (CAM) {
+                    if (p < (unsigned)cap) rel[p] = ev_key(row[j], ((unsigned)j << 1) | (g_cams[j] == cam ? 1u : 0u));
+                } else {
+                    if (p < (unsigned)cap) rel[p] = ev_key(row[j], (unsigned)j);
+                }
             }
         }
     }
@@ -65,8 +86,11 @@ __global__ __launch_bounds__(256) void eval_rank_kernel(const float *__restrict_
         if (tid == 0) cnt_out[q] = -1;
         return;
     }
-    if (tid == 0) cnt_out[q] = R;
+    if constexpr (!CAM)
+        if (tid == 0) cnt_out[q] = R;
     if (R == 0) {
+        if constexpr (CAM)
+            if (tid == 0) cnt_out[q] = 0;
         for (int t = tid; t < rcap; t += 256) pos_out[(int64_t)q * rcap + t] = -1;
         return;
     }
@@ -96,7 +120,8 @@ __global__ __launch_bounds__(256) void eval_rank_kernel(const float *__restrict_
     // 2. bucket every gallery item: b = number of relevant keys < key_j (a relevant item t lands in bucket t)
     unsigned *mine = hist + (lane & (C - 1)) * nb;
     for (int j = tid; j < ng; j += 256) {
-        const unsigned long long k = ev_key(row[j], (unsigned)j);
+        // (CAM: flag bit clear -- the item's own list entry, flagged or not, is still the first one >= k)
+        const unsigned long long k = ev_key(row[j], CAM ? (unsigned)j << 1 : (unsigned)j);
         int lo = 0, hi = R; // first t with rel[t] >= k
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
@@ -114,31 +139,65 @@ __global__ __launch_bounds__(256) void eval_rank_kernel(const float *__restrict_
         __syncthreads();
     }
     // 3. position of relevant item t = number of items with a smaller key = sum_{b<=t} hist[b] - 1 (itself)
+    //    (CAM: minus the junk keys among rel[0..t), written at index t - that number; junk entries are not written)
     unsigned run = 0;
+    int jrun = 0;
     for (int t0 = 0; t0 < R; t0 += 256) {
         const int t = t0 + tid;
         const int v = (t < R) ? (int)hist[t] : 0;
+        int jf = 0;
+        if constexpr (CAM) jf = (t < R) ? (int)(rel[t] & 1ull) : 0;
         // block inclusive scan
-        int x = v;
+        int x = v, jx = jf;
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
             const int y = __shfl_up(x, off, 64);
             if (lane >= off) x += y;
+            if constexpr (CAM) {
+                const int jy = __shfl_up(jx, off, 64);
+                if (lane >= off) jx += jy;
+            }
         }
         __syncthreads();
-        if (lane == 63) s_wave[wave] = x;
+        if (lane == 63) {
+            s_wave[wave] = x;
+            if constexpr (CAM) s_wave[4 + wave] = jx;
+        }
         __syncthreads();
-        int base = 0, tot = 0;
+        int base = 0, tot = 0, jbase = 0, jtot = 0;
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
             if (w < wave) base += s_wave[w];
             tot += s_wave[w];
+            if constexpr (CAM) {
+                if (w < wave) jbase += s_wave[4 + w];
+                jtot += s_wave[4 + w];
+            }
         }
-        if (t < R) pos_out[(int64_t)q * rcap + t] = (int)(run + (unsigned)(base + x)) - 1;
+        if constexpr (CAM) {
+            const int jb = jrun + jbase + jx; // junk keys among rel[0..t]
+            if (t < R && !jf) pos_out[(int64_t)q * rcap + (t - jb)] = (int)(run + (unsigned)(base + x)) - 1 - jb;
+            jrun += jtot;
+        } else {
+            if (t < R) pos_out[(int64_t)q * rcap + t] = (int)(run + (unsigned)(base + x)) - 1;
+        }
         run += (unsigned)tot;
         __syncthreads();
     }
-    for (int t = R + tid; t < rcap; t += 256) pos_out[(int64_t)q * rcap + t] = -1;
+    const int nrel = R - jrun;
+    if constexpr (CAM)
+        if (tid == 0) cnt_out[q] = nrel;
+    for (int t = nrel + tid; t < rcap; t += 256) pos_out[(int64_t)q * rcap + t] = -1;
+}
+
+// the launch geometry of both instantiations: cap (LDS entries of the sorted list), hw (counter words), LDS bytes
+static inline size_t ev_geometry(int rcap, int *cap_out, int *hw_out) {
+    int cap = 64;
+    while (cap < rcap && cap < EV_CAP_MAX) cap <<= 1;
+    const int hw = cap + 1 > EV_HIST_MIN ? cap + 1 : EV_HIST_MIN;
+    *cap_out = cap;
+    *hw_out = hw;
+    return (size_t)cap * 8 + (size_t)hw * 4;
 }
 
 extern "C" int mpreid_eval_rank_positions(const float *dist_dev, int64_t ld, int nq, int ng, const int64_t *q_pids_dev,
@@ -146,14 +205,12 @@ extern "C" int mpreid_eval_rank_positions(const float *dist_dev, int64_t ld, int
                                           int32_t *cnt_out_dev, mpreid_stream_t stream) {
     ARG_CHECK(dist_dev && q_pids_dev && g_pids_dev && pos_out_dev && cnt_out_dev && nq > 0 && ng > 0 && ld >= ng &&
               rcap > 0);
-    int cap = 64;
-    while (cap < rcap && cap < EV_CAP_MAX) cap <<= 1;
-    const int hw = cap + 1 > EV_HIST_MIN ? cap + 1 : EV_HIST_MIN;
-    const size_t lds = (size_t)cap * 8 + (size_t)hw * 4;
+    int cap, hw;
+    const size_t lds = ev_geometry(rcap, &cap, &hw);
     static PerDeviceOnce attr_once;
     {
         const int rc = attr_once.run([]() -> int {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel),
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel<false>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize,
                                         EV_CAP_MAX * 8 + (EV_CAP_MAX + 1) * 4));
             return MPREID_OK;
@@ -161,8 +218,36 @@ extern "C" int mpreid_eval_rank_positions(const float *dist_dev, int64_t ld, int
         if (rc != MPREID_OK) return rc;
     }
     void *ptok = mpreid_prof_begin((hipStream_t)stream);
-    hipLaunchKernelGGL(eval_rank_kernel, dim3((unsigned)nq), dim3(256), lds, (hipStream_t)stream, dist_dev, ld, nq, ng,
-                       (const long long *)q_pids_dev, (const long long *)g_pids_dev, rcap, cap, hw, pos_out_dev,
+    hipLaunchKernelGGL(eval_rank_kernel<false>, dim3((unsigned)nq), dim3(256), lds, (hipStream_t)stream, dist_dev, ld,
+                       nq, ng, (const long long *)q_pids_dev, (const long long *)g_pids_dev,
+                       (const long long *)nullptr, (const long long *)nullptr, rcap, cap, hw, pos_out_dev, cnt_out_dev);
+    mpreid_prof_end(ptok, (hipStream_t)stream, MPREID_PROF_EVALRANK, nq, ng, 0, 4.0 * (double)nq * (double)ng);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
+extern "C" int mpreid_eval_rank_positions_cam(const float *dist_dev, int64_t ld, int nq, int ng,
+                                              const int64_t *q_pids_dev, const int64_t *g_pids_dev,
+                                              const int64_t *q_camids_dev, const int64_t *g_camids_dev, int rcap,
+                                              int32_t *pos_out_dev, int32_t *cnt_out_dev, mpreid_stream_t stream) {
+    ARG_CHECK(dist_dev && q_pids_dev && g_pids_dev && q_camids_dev && g_camids_dev && pos_out_dev && cnt_out_dev &&
+              nq > 0 && ng > 0 && ld >= ng && rcap > 0);
+    int cap, hw;
+    const size_t lds = ev_geometry(rcap, &cap, &hw);
+    static PerDeviceOnce attr_once; // its own: the attribute belongs to the function, not to the file
+    {
+        const int rc = attr_once.run([]() -> int {
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel<true>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        EV_CAP_MAX * 8 + (EV_CAP_MAX + 1) * 4));
+            return MPREID_OK;
+        });
+        if (rc != MPREID_OK) return rc;
+    }
+    void *ptok = mpreid_prof_begin((hipStream_t)stream);
+    hipLaunchKernelGGL(eval_rank_kernel<true>, dim3((unsigned)nq), dim3(256), lds, (hipStream_t)stream, dist_dev, ld, nq,
+                       ng, (const long long *)q_pids_dev, (const long long *)g_pids_dev,
+                       (const long long *)q_camids_dev, (const long long *)g_camids_dev, rcap, cap, hw, pos_out_dev,
                        cnt_out_dev);
     mpreid_prof_end(ptok, (hipStream_t)stream, MPREID_PROF_EVALRANK, nq, ng, 0, 4.0 * (double)nq * (double)ng);
     LAUNCH_CHECK();

@@ -114,6 +114,10 @@ def merge_batches(group, device):
     return img, camids, views
 
 
+SAME_CAM_NOTE = ("TEST.REMOVE_SAME_CAM: for each query, gallery images of the same identity from the same camera are "
+                 "removed before ranking (Market-1501 protocol)")
+
+
 def do_inference(cfg, model, val_loader, num_query):
     device = "cuda"
     logger = logging.getLogger("transreid.test")
@@ -129,12 +133,16 @@ def do_inference(cfg, model, val_loader, num_query):
         str(getattr(cfg.TEST, "DISTANCE_MODE", "exact"))]
     evaluator.rerank_algo = {"exact": _ops.RERANK_AUTO, "split3": _ops.RERANK_SPARSE_SPLIT3}[
         str(getattr(cfg.TEST, "RERANK_ALGO", "exact"))]
+    # TEST.REMOVE_SAME_CAM (not a reference key): the Market-1501 protocol of utils/metrics.py, default off like upstream
+    evaluator.remove_same_cam = bool(getattr(cfg.TEST, "REMOVE_SAME_CAM", False))
     evaluator.reset()
 
     # the reference's test.py never initialises a process group (test.py:39,65): under a launcher (WORLD_SIZE > 1) this
     # call does, and binds the rank to cuda:LOCAL_RANK, before anything touches a device (raises when the ranks of the
     # node cannot each see their own device -- MODEL.DEVICE_ID must list them: INTEGRATION.md section C)
     rank, world = _D.ensure_group_from_env(logger)
+    if evaluator.remove_same_cam and rank == 0:
+        logger.info(SAME_CAM_NOTE)
     model.to(device)
     model.eval()
     img_path_list = []

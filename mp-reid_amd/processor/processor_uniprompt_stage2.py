@@ -19,7 +19,7 @@ import time
 import torch
 
 from mpreid import ops as _ops
-from processor.processor import ENCODE_GROUP, grouped_batches, merge_batches
+from processor.processor import ENCODE_GROUP, SAME_CAM_NOTE, grouped_batches, merge_batches
 from utils.metrics import R1_mAP_eval
 
 
@@ -29,6 +29,9 @@ def do_inference(cfg, model, val_loader, num_query):
     logger.info("Enter inferencing")
 
     evaluator = R1_mAP_eval(num_query, max_rank=50, feat_norm=cfg.TEST.FEAT_NORM)
+    evaluator.remove_same_cam = bool(getattr(cfg.TEST, "REMOVE_SAME_CAM", False))   # not a reference key (config/node.py)
+    if evaluator.remove_same_cam:
+        logger.info(SAME_CAM_NOTE)
     evaluator.reset()
 
     model.to(device)
@@ -72,6 +75,9 @@ def do_inference_ttpt_option_a(cfg, model, val_loader, num_query):
 
     model.to(device)
     evaluator = R1_mAP_eval(num_query, max_rank=50, feat_norm=cfg.TEST.FEAT_NORM)
+    evaluator.remove_same_cam = bool(getattr(cfg.TEST, "REMOVE_SAME_CAM", False))   # not a reference key (config/node.py)
+    if evaluator.remove_same_cam:
+        logger.info(SAME_CAM_NOTE)
     evaluator.reset()
     model.eval()
 

@@ -2,7 +2,7 @@
 ``R1_mAP_eval`` accumulator, with the heavy steps on the MI355X (libmpreid_hip.so).
 
 Signatures kept (reference utils/metrics.py): euclidean_distance(qf, gf) :7, cosine_similarity(qf, gf) :15,
-eval_func(distmat, q_pids, g_pids, q_camids, g_camids, max_rank=50) :28,
+eval_func(distmat, q_pids, g_pids, q_camids, g_camids, max_rank=50) :28 (+ remove_same_cam=False, below),
 R1_mAP_eval(num_query, max_rank=50, feat_norm=True, reranking=False) with reset/update/compute :91-134.
 
 Differences that are deliberate and invisible to callers:
@@ -11,6 +11,17 @@ Differences that are deliberate and invisible to callers:
     ``eval_func`` itself (numpy in, numpy out) stays a host function with the reference's signature.
   * ties in eval_func's ranking are broken by ascending gallery index (the reference's
     np.argsort is unstable, so it has no defined order on ties).
+
+Market-1501 protocol (opt-in, not in the reference's eval_func as shipped): the reference's docstring (:29-31) promises
+that, for each query, the gallery images of the same identity from the same camera are discarded, and line :54 that does
+it is commented out; its other evaluation tail (processor/processor_uniprompt_stage2.py:476-505) runs it.  By default the
+camera ids are therefore accepted and unused, like upstream.  With ``remove_same_cam=True`` (eval_func, eval_func_device,
+eval_func_sharded; ``R1_mAP_eval.remove_same_cam``; config key TEST.REMOVE_SAME_CAM) a gallery item j is JUNK for query
+q when g_pids[j] == q_pids[q] and g_camids[j] == q_camids[q]: junk items leave the ranking, the other pid matches are
+the relevant ones, a relevant item's position counts the kept items with a smaller (distance, gallery index) key, and
+a query is valid iff a relevant item is left.  That is eval_func with its line :54 restored.  max_rank is clamped by the
+gallery size before the filter (:36-38); a row that keeps fewer than max_rank items continues its CMC at 1 after its
+first hit (the reference could not stack such ragged rows).
 """
 import numpy as np
 import torch
@@ -33,17 +44,50 @@ def cosine_similarity(qf, gf):
     return _ops.cosine_similarity(_as_tensor(qf), _as_tensor(gf)).cpu().numpy()
 
 
-def eval_func(distmat, q_pids, g_pids, q_camids, g_camids, max_rank=50):
+def _need_camids(q_camids, g_camids):
+    if q_camids is None or g_camids is None:
+        raise ValueError("remove_same_cam=True needs q_camids and g_camids")
+
+
+def _eval_func_samecam(distmat, q_pids, g_pids, q_camids, g_camids, max_rank):
+    """eval_func under the Market-1501 protocol (module docstring): host, numpy, stable order."""
+    q_camids = np.asarray(q_camids)
+    g_camids = np.asarray(g_camids)
+    num_q, num_g = distmat.shape
+    order = np.argsort(distmat, axis=1, kind="stable")
+    match = (g_pids[order] == q_pids[:, None])
+    junk = match & (g_camids[order] == q_camids[:, None])
+    hit = match & ~junk
+    valid = hit.any(axis=1)
+    num_valid_q = float(valid.sum())
+    assert num_valid_q > 0, "Error: all query identities do not appear in gallery"
+    hit, junk = hit[valid], junk[valid]
+    kept_rank = np.cumsum(~junk, axis=1)               # 1-based rank among the kept items (at kept entries)
+    running = np.cumsum(hit, axis=1)
+    first = kept_rank[np.arange(hit.shape[0]), hit.argmax(axis=1)] - 1
+    cmc_rows = (np.arange(max_rank)[None, :] >= first[:, None]).astype(np.float32)
+    all_cmc = cmc_rows.sum(0) / num_valid_q
+    prec_at_hit = (running / np.maximum(kept_rank, 1)) * hit     # (kept_rank is 0 only in front of the first kept item)
+    all_AP = prec_at_hit.sum(axis=1) / hit.sum(axis=1)
+    return all_cmc, np.mean(all_AP)
+
+
+def eval_func(distmat, q_pids, g_pids, q_camids, g_camids, max_rank=50, remove_same_cam=False):
     """Market-1501 style CMC and mAP exactly as the reference computes them: gallery samples that
-    share pid AND camera with the query are NOT removed (that filter is disabled upstream), so the
-    camera ids are accepted and unused.  Host-side, vectorised over queries."""
+    share pid AND camera with the query are NOT removed (that filter is disabled upstream), so by default the
+    camera ids are accepted and unused.  remove_same_cam=True removes them (module docstring).
+    Host-side, vectorised over queries."""
     distmat = np.asarray(distmat)
     q_pids = np.asarray(q_pids)
     g_pids = np.asarray(g_pids)
+    if remove_same_cam:
+        _need_camids(q_camids, g_camids)
     num_q, num_g = distmat.shape
     if num_g < max_rank:
         max_rank = num_g
         print("Note: number of gallery samples is quite small, got {}".format(num_g))
+    if remove_same_cam:
+        return _eval_func_samecam(distmat, q_pids, g_pids, q_camids, g_camids, max_rank)
     order = np.argsort(distmat, axis=1, kind="stable")
     hit = (g_pids[order] == q_pids[:, None])
     valid = hit.any(axis=1)
@@ -65,12 +109,14 @@ def eval_func(distmat, q_pids, g_pids, q_camids, g_camids, max_rank=50):
 _warned_host_ranking = False
 
 
-def _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch=None):
+def _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch=None, q_camids=None, g_camids=None):
     """Ranking statistics of the query ROWS in `dist` (device tensor [rows, ng] fp32): (cmc hit counts [max_rank] float32
     summed over the valid rows, AP of every valid row in row order (float64), number of valid rows).  Sums of 0/1 values
     are exact in float32, so hit counts of row shards add up to the unsharded counts bit for bit.
     `after_launch()` is called once the ranking kernel is queued and before the host waits for it (compute() starts the
-    matrix's D2H copy there, ordered BEHIND the kernel)."""
+    matrix's D2H copy there, ordered BEHIND the kernel).
+    With camera ids (both or neither) the rows are ranked under the Market-1501 protocol: same-identity same-camera gallery
+    items are removed, a row is valid iff a relevant item is left (mpreid_eval_rank_positions_cam)."""
     import ctypes as C
     from mpreid import _lib
     dev = _lib.require_gpu()
@@ -80,6 +126,11 @@ def _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch=None):
     num_q, num_g = dist.shape
     q_pids = np.ascontiguousarray(q_pids, dtype=np.int64)
     g_pids = np.ascontiguousarray(g_pids, dtype=np.int64)
+    cam = q_camids is not None
+    if cam:
+        q_camids = np.ascontiguousarray(q_camids, dtype=np.int64)
+        g_camids = np.ascontiguousarray(g_camids, dtype=np.int64)
+        assert q_camids.shape == q_pids.shape and g_camids.shape == g_pids.shape
     if num_q == 0:
         if after_launch is not None:
             after_launch()
@@ -88,10 +139,18 @@ def _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch=None):
     qp, gp = torch.from_numpy(q_pids).to(dev), torch.from_numpy(g_pids).to(dev)
     pos = torch.empty((num_q, rcap), dtype=torch.int32, device=dev)
     cnt = torch.empty(num_q, dtype=torch.int32, device=dev)
-    _lib.check(L.mpreid_eval_rank_positions(C.c_void_p(dist.data_ptr()), dist.stride(0), num_q, num_g,
-                                            C.c_void_p(qp.data_ptr()), C.c_void_p(gp.data_ptr()), rcap,
-                                            C.c_void_p(pos.data_ptr()), C.c_void_p(cnt.data_ptr()), _lib.stream_ptr()),
-               "mpreid_eval_rank_positions")
+    if cam:   # rcap from the pid counts bounds the relevant AND the junk items: both live in the kernel's sorted list
+        qc, gc = torch.from_numpy(q_camids).to(dev), torch.from_numpy(g_camids).to(dev)
+        _lib.check(L.mpreid_eval_rank_positions_cam(C.c_void_p(dist.data_ptr()), dist.stride(0), num_q, num_g,
+                                                    C.c_void_p(qp.data_ptr()), C.c_void_p(gp.data_ptr()),
+                                                    C.c_void_p(qc.data_ptr()), C.c_void_p(gc.data_ptr()), rcap,
+                                                    C.c_void_p(pos.data_ptr()), C.c_void_p(cnt.data_ptr()),
+                                                    _lib.stream_ptr()), "mpreid_eval_rank_positions_cam")
+    else:
+        _lib.check(L.mpreid_eval_rank_positions(C.c_void_p(dist.data_ptr()), dist.stride(0), num_q, num_g,
+                                                C.c_void_p(qp.data_ptr()), C.c_void_p(gp.data_ptr()), rcap,
+                                                C.c_void_p(pos.data_ptr()), C.c_void_p(cnt.data_ptr()), _lib.stream_ptr()),
+                   "mpreid_eval_rank_positions")
     if after_launch is not None:
         after_launch()
     pos, cnt = pos.cpu().numpy().astype(np.int64), cnt.cpu().numpy().astype(np.int64)
@@ -110,7 +169,12 @@ def _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch=None):
         pos = np.pad(pos, ((0, 0), (0, wide - pos.shape[1])), constant_values=-1)
         for r, qi in enumerate(over):
             order = np.argsort(rows[r], kind="stable")
-            p = np.nonzero(g_pids[order] == q_pids[qi])[0]
+            match = g_pids[order] == q_pids[qi]
+            if cam:   # the same filter as the kernel: positions among the kept items
+                junk = match & (g_camids[order] == q_camids[qi])
+                p = (np.cumsum(~junk) - 1)[match & ~junk]
+            else:
+                p = np.nonzero(match)[0]
             pos[qi, :] = -1
             pos[qi, :p.size] = p
             cnt[qi] = p.size
@@ -126,7 +190,8 @@ def _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch=None):
     return cmc_rows.sum(0), terms.sum(axis=1) / cnt, num_valid
 
 
-def eval_func_device(dist, q_pids, g_pids, q_camids=None, g_camids=None, max_rank=50, after_launch=None):
+def eval_func_device(dist, q_pids, g_pids, q_camids=None, g_camids=None, max_rank=50, after_launch=None,
+                     remove_same_cam=False):
     """eval_func with the ranking done on the GPU (dist: device tensor [nq, ng] fp32, left on the device).
 
     Per query the kernel returns the positions of the relevant gallery items in the ascending (distance, index)
@@ -134,31 +199,47 @@ def eval_func_device(dist, q_pids, g_pids, q_camids=None, g_camids=None, max_ran
     finished here in float64.  CMC is identical to eval_func's; AP sums the same terms (hits up to k) / k in a
     different order than numpy's pairwise reduction over the dense row, i.e. |delta mAP| ~ 1e-16.
 
+    remove_same_cam=True: the Market-1501 protocol (module docstring) through mpreid_eval_rank_positions_cam; without it
+    the camera ids are unused and the call is what it was before the option existed.
+
     Under a process group (one rank per GPU) `dist` may be this rank's ROW block and q_pids its rows' pids: see
     eval_func_sharded."""
+    if remove_same_cam:
+        _need_camids(q_camids, g_camids)
     num_g = dist.shape[1]
     if num_g < max_rank:
         max_rank = num_g
         print("Note: number of gallery samples is quite small, got {}".format(num_g))
-    hits, ap, num_valid = _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch)
+    if remove_same_cam:
+        hits, ap, num_valid = _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch, q_camids, g_camids)
+    else:
+        hits, ap, num_valid = _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch)
     assert num_valid > 0, "Error: all query identities do not appear in gallery"
     return hits / float(num_valid), np.mean(ap)
 
 
-def eval_func_sharded(dist_rows, q_pids_local, g_pids, max_rank=50):
+def eval_func_sharded(dist_rows, q_pids_local, g_pids, max_rank=50, q_camids_local=None, g_camids=None,
+                      remove_same_cam=False):
     """eval_func over query rows sharded across the ranks of the default process group (SURVEY.md section 8e, row
     `eval_func`): every rank ranks its own rows [q_lo, q_hi) on its GPU; the hit counts (exact small integers) are
     summed and the per-query AP lists are concatenated in rank = query order, so every rank ends up with the cmc / mAP
-    of the unsharded call BIT FOR BIT (integer sums; np.mean over the same float64 list in the same order)."""
+    of the unsharded call BIT FOR BIT (integer sums; np.mean over the same float64 list in the same order).
+    remove_same_cam=True (with this rank's rows' camera ids and all gallery camera ids): the Market-1501 protocol, row by
+    row as in eval_func_device."""
     import torch.distributed  # noqa: F401  (ReduceOp)
     from mpreid import distributed as D
+    if remove_same_cam:
+        _need_camids(q_camids_local, g_camids)
     rank, world = D.rank_world()
     num_g = dist_rows.shape[1]
     if num_g < max_rank:
         max_rank = num_g
         if rank == 0:
             print("Note: number of gallery samples is quite small, got {}".format(num_g))
-    hits, ap, num_valid = _eval_rows_device(dist_rows, q_pids_local, g_pids, max_rank)
+    if remove_same_cam:
+        hits, ap, num_valid = _eval_rows_device(dist_rows, q_pids_local, g_pids, max_rank, None, q_camids_local, g_camids)
+    else:
+        hits, ap, num_valid = _eval_rows_device(dist_rows, q_pids_local, g_pids, max_rank)
     if D.sharded_active():
         staged = D._pg().get_backend() == "gloo"
         dev = "cpu" if staged else dist_rows.device
@@ -239,6 +320,7 @@ class R1_mAP_eval():
         self.reranking = reranking
         self.distance_mode = _ops.GEMM_F32_EXACT   # _ops.GEMM_F16_SPLIT3 (<= 1e-6) / GEMM_F16_FAST (~1e-4): TEST.DISTANCE_MODE
         self.rerank_algo = _ops.RERANK_AUTO   # _ops.RERANK_SPARSE_SPLIT3: faster at large N, outputs within 1e-6
+        self.remove_same_cam = False    # True: Market-1501 protocol (module docstring), TEST.REMOVE_SAME_CAM
         self.last_rerank_stats = None
 
     def reset(self):
@@ -289,14 +371,16 @@ class R1_mAP_eval():
         # blit kernels it waited for.  MPREID_EVAL_D2H=behind orders the copy after the kernel: used for kernel traces only.)
         import os
         box = {}
+        same_cam = bool(getattr(self, "remove_same_cam", False))
 
         def start_copy():
             box["h"], box["ev"] = _to_host_async([dist])
         if os.environ.get("MPREID_EVAL_D2H") == "behind":
-            cmc, mAP = eval_func_device(dist, q_pids, g_pids, q_camids, g_camids, after_launch=start_copy)
+            cmc, mAP = eval_func_device(dist, q_pids, g_pids, q_camids, g_camids, after_launch=start_copy,
+                                        remove_same_cam=same_cam)
         else:
             start_copy()
-            cmc, mAP = eval_func_device(dist, q_pids, g_pids, q_camids, g_camids)
+            cmc, mAP = eval_func_device(dist, q_pids, g_pids, q_camids, g_camids, remove_same_cam=same_cam)
         (h_dist,), copied = box["h"], box["ev"]
         feats_copied.synchronize()
         copied.synchronize()
@@ -342,6 +426,9 @@ class R1_mAP_eval():
         pids = [p for m, k in zip(meta, q_sizes) for p in m[0][:k]] + [p for m, k in zip(meta, q_sizes) for p in m[0][k:]]
         camids = [c for m, k in zip(meta, q_sizes) for c in m[1][:k]] + [c for m, k in zip(meta, q_sizes) for c in m[1][k:]]
         q_pids, g_pids = np.asarray(pids[:nq]), np.asarray(pids[nq:])
+        same_cam = bool(getattr(self, "remove_same_cam", False))
+        cam_kw = dict(q_camids_local=np.asarray(camids[q_lo:q_hi]), g_camids=np.asarray(camids[nq:]),
+                      remove_same_cam=True) if same_cam else {}
         qf_local, gf_local = feats[:nql].contiguous(), feats[nql:].contiguous()
         qf = D.all_gather_rows(qf_local, nq)            # the RCCL all-gather of the query features
         if self.reranking:
@@ -350,7 +437,7 @@ class R1_mAP_eval():
             gf = D.all_gather_rows(gf_local, ng)        # every rank needs all rows of the N x N problem's operands
             rows = D.re_ranking_sharded(qf, gf, 50, 15, 0.3, algo=getattr(self, "rerank_algo", 0))   # [nql, ng]
             _ops.release_workspaces("rerank")
-            cmc, mAP = eval_func_sharded(rows, q_pids[q_lo:q_hi], g_pids)
+            cmc, mAP = eval_func_sharded(rows, q_pids[q_lo:q_hi], g_pids, **cam_kw)
             distmat = D.gather_row_blocks_to_host(rows, dst=0)
             gf_out = gf
         else:
@@ -358,7 +445,7 @@ class R1_mAP_eval():
                 print('=> Computing DistMat with euclidean_distance')
             block = _ops.euclidean_distance(qf, gf_local, mode=self.distance_mode)     # [nq, ng_local]
             rows = D.column_to_row_blocks(block, nq, ng_sizes)                         # [nql, ng]
-            cmc, mAP = eval_func_sharded(rows, q_pids[q_lo:q_hi], g_pids)
+            cmc, mAP = eval_func_sharded(rows, q_pids[q_lo:q_hi], g_pids, **cam_kw)
             distmat = D.gather_column_blocks_to_host(block, dst=0)                     # host concatenation on rank 0
             gf_host = D.gather_row_blocks_to_host(gf_local, dst=0)
             gf_out = torch.from_numpy(gf_host) if rank == 0 else gf_local

@@ -3,6 +3,11 @@
 order inside R1_mAP_eval.compute()), and the whole of compute() in both orders.
 
     python tools/evalrank_bench.py [nq ng]
+    python tools/evalrank_bench.py --remove-same-cam [nq ng]
+
+--remove-same-cam: the camera-aware kernel (eval_rank_kernel<true>, the Market-1501 protocol: TEST.REMOVE_SAME_CAM) and the
+unfiltered one timed in the same process on the same matrix and pids, 6 cameras with uniform labels, launches interleaved;
+nothing else is measured in that mode.
 
 Round 5's trace (profiles/r05_bench_kernel_stats.csv) showed the kernel at 0.22 ms min / 5.39 ms average: this script
 separates the kernel's own time from what the concurrent blit copy does to it."""
@@ -24,7 +29,9 @@ from utils.metrics import R1_mAP_eval  # noqa: E402
 
 
 def main():
-    nq, ng = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (3368, 15913)
+    argv = [a for a in sys.argv[1:] if a != "--remove-same-cam"]
+    same_cam = len(argv) != len(sys.argv) - 1
+    nq, ng = (int(argv[0]), int(argv[1])) if len(argv) > 1 else (3368, 15913)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
     L = _lib.load()
@@ -40,6 +47,15 @@ def main():
         _lib.check(L.mpreid_eval_rank_positions(C.c_void_p(dist.data_ptr()), dist.stride(0), nq, ng, C.c_void_p(qp.data_ptr()),
                                                 C.c_void_p(gp.data_ptr()), rcap, C.c_void_p(pos.data_ptr()),
                                                 C.c_void_p(cnt.data_ptr()), _lib.stream_ptr()), "eval_rank")
+
+    cams = rng.integers(0, 6, size=nq + ng).astype(np.int64)
+    qc, gc = torch.from_numpy(cams[:nq]).to(dev), torch.from_numpy(cams[nq:]).to(dev)
+
+    def launch_cam():
+        _lib.check(L.mpreid_eval_rank_positions_cam(C.c_void_p(dist.data_ptr()), dist.stride(0), nq, ng, C.c_void_p(qp.data_ptr()),
+                                                    C.c_void_p(gp.data_ptr()), C.c_void_p(qc.data_ptr()), C.c_void_p(gc.data_ptr()),
+                                                    rcap, C.c_void_p(pos.data_ptr()), C.c_void_p(cnt.data_ptr()),
+                                                    _lib.stream_ptr()), "eval_rank_cam")
 
     def timed(fn, reps=10):
         fn()
@@ -64,6 +80,26 @@ def main():
         want = np.nonzero(pids[nq:][order] == pids[r])[0]
         assert c_h[r] == want.size and np.array_equal(p_h[r, :want.size], want), r
     print(f"shape {nq} x {ng}, rcap {rcap}: positions of rows 0-7 equal a stable argsort")
+    if same_cam:
+        launch_cam()
+        torch.cuda.synchronize()
+        p_h, c_h = pos.cpu().numpy(), cnt.cpu().numpy()
+        for r in range(8):
+            order = np.argsort(d_h[r], kind="stable")
+            match = pids[nq:][order] == pids[r]
+            junk = match & (cams[nq:][order] == cams[r])
+            want = (np.cumsum(~junk) - 1)[match & ~junk]
+            assert c_h[r] == want.size and np.array_equal(p_h[r, :want.size], want) and (p_h[r, want.size:] == -1).all(), r
+        print("camera-aware kernel: positions of rows 0-7 equal a stable argsort with the junk items removed")
+        res = {"unfiltered": [], "same-cam removed": []}
+        for _ in range(5):                      # interleaved, so that clock / neighbour drift hits both alike
+            res["unfiltered"].append(timed(launch))
+            res["same-cam removed"].append(timed(launch_cam))
+        for name, ts in res.items():
+            mn, avg, mx = min(t[0] for t in ts), sum(t[1] for t in ts) / len(ts), max(t[2] for t in ts)
+            print("kernel %-17s min/avg/max ms over 5 x 10 launches: %.4f %.4f %.4f  (%.0f GB/s of 4*nq*ng)"
+                  % (name, mn, avg, mx, 4.0 * nq * ng / avg / 1e6))
+        return
     alone = timed(launch)
     print("kernel alone            min/avg/max ms: %.3f %.3f %.3f  (%.0f GB/s of 4*nq*ng)" % (*alone, 4.0 * nq * ng / alone[1] / 1e6))
     side = torch.cuda.Stream(device=dev)
