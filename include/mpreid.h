@@ -221,6 +221,26 @@ int mpreid_eval_rank_positions_cam(const float *dist_dev, int64_t ld, int nq, in
                                    const int64_t *g_pids_dev, const int64_t *q_camids_dev, const int64_t *g_camids_dev,
                                    int rcap, int32_t *pos_out_dev, int32_t *cnt_out_dev, mpreid_stream_t stream);
 
+/* The same for a BATCH of (split, query) pairs over one resident matrix, in one launch -- multi-trial protocols
+ * (VehicleID's ten trials, reference test.py:46-63; RegDB; MMMP's exp_setting pairs) evaluate several (query set, gallery
+ * set) pairs over one set of images: the pool is encoded once, one pool x pool matrix [n_rows][n_cols] (leading dimension
+ * ld >= n_cols) stays on the device and every split reads its sub-matrix through index lists.  Pair b ranks row q_row[b] of
+ * the matrix against the columns g_idx[g_off[s] .. g_off[s + 1]) of split s = q_split[b]; the semantics are those of
+ * mpreid_eval_rank_positions -- of mpreid_eval_rank_positions_cam when q_camids_dev / g_camids_dev are given (both or
+ * neither) -- applied to the gathered row dist[q_row[b]][g_idx[...]].  The tie-break index of an item is its POSITION IN
+ * THE SPLIT'S LIST, not its column: the positions equal a stable argsort of the gathered row whatever order the list is in.
+ * q_pids / q_camids [nqt] are the pairs' labels; g_pids / g_camids [g_off[n_splits]] are the labels of the list entries,
+ * aligned with g_idx (the caller gathers them once: the kernel reads labels coalesced and gathers distances only).
+ * pos_out [nqt][rcap], cnt_out [nqt], the -1 padding and the cnt = -1 hand-back (more than min(rcap, 8192) pid matches in
+ * the pair's list) are as above; same LDS geometry.  LIMIT: the CONTENTS of q_row (< n_rows), q_split (< n_splits), g_off
+ * (ascending from 0) and g_idx (< n_cols) are device data and are NOT checked here: the caller validates them before
+ * upload (utils/metrics.py:eval_func_splits_device does). */
+int mpreid_eval_rank_positions_splits(const float *dist_dev, int64_t ld, int64_t n_rows, int64_t n_cols, int nqt,
+                                      const int32_t *q_row_dev, const int32_t *q_split_dev, const int64_t *q_pids_dev,
+                                      const int64_t *q_camids_dev, int n_splits, const int64_t *g_off_dev,
+                                      const int32_t *g_idx_dev, const int64_t *g_pids_dev, const int64_t *g_camids_dev,
+                                      int rcap, int32_t *pos_out_dev, int32_t *cnt_out_dev, mpreid_stream_t stream);
+
 /* ---- row-sharded re-ranking: the same kernels, phase by phase over a row range ------------
  * Rows [r_lo, r_lo+rows) of the N x N problem belong to the calling rank; between the phases the caller
  * all-gathers (RCCL) the rank table, the sparse V rows and the sparse V_qe rows.  mpreid/distributed.py
@@ -585,7 +605,9 @@ int mpreid_cast_f32_to_f16(const float *x_dev, void *y_dev, int64_t n, mpreid_st
  * output written) */
 #define MPREID_PROF_LAYERNORM 100
 #define MPREID_PROF_ATTENTION 101
-#define MPREID_PROF_EVALRANK 102   /* eval_rank_kernel: m = nq, n = ng; work = 4*nq*ng bytes (the matrix read once) */
+#define MPREID_PROF_EVALRANK 102   /* eval_rank_kernel: m = nq, n = ng; work = 4*nq*ng bytes (the matrix read once).  The splits
+                                    * entry point files m = pairs, n = n_cols, k = n_splits; work = 4 * sum over the pairs of the
+                                    * pair's gallery list length (the gathered distances) */
 typedef struct {
     int32_t epilogue;        /* GemmEpi id of the fp16 GEMM class, or MPREID_PROF_* */
     int32_t n, k;            /* GEMM N and K (split epilogues: K = 2 * kseg halfs per operand row; 3 * kseg is executed) */

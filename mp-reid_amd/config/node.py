@@ -79,7 +79,12 @@ def make_defaults():
                      "SYNTH_GALLERY": 15913, "SYNTH_IDS": 751, "SYNTH_SEED": 1234,
                      # SYNTH_RAW: the loader hands over DECODED uint8 images of ragged sizes (what PIL gives before
                      # val_transforms) and Resize + ToTensor + Normalize run on the GPU
-                     "SYNTH_RAW": False},
+                     "SYNTH_RAW": False,
+                     # PROTOCOL 'vehicleid' (not a reference key; the reference branches on NAMES == 'VehicleID', test.py:46):
+                     # TEST.TRIALS trials over ONE encoded pool, in each of them one random image per identity is the
+                     # gallery and all the others are queries (datasets/make_dataloader.py:vehicleid_trial_splits, drawn
+                     # from TRIAL_SEED).  '' = the single query-then-gallery evaluation
+                     "PROTOCOL": "", "TRIAL_SEED": 0},
         "DATALOADER": {"NUM_WORKERS": 0},
         "TEST": {"IMS_PER_BATCH": 64, "RE_RANKING": False, "WEIGHT": "", "NECK_FEAT": "before", "FEAT_NORM": "yes",
                  "DIST_MAT": "dist_mat.npy", "EVAL": False,
@@ -88,6 +93,7 @@ def make_defaults():
                  # of the same identity from the same camera are removed (utils/metrics.py; the reference's eval_func
                  # keeps that line commented out, utils/metrics.py:54)
                  "REMOVE_SAME_CAM": False,
+                 "TRIALS": 10,   # DATASETS.PROTOCOL 'vehicleid': number of trials (the reference's loop runs 10, test.py:47)
                  # Uni-Prompt evaluation (reference config/defaults.py:331-344)
                  "TTA_ENABLED": False, "TTPT": {"ENABLED": False, "LR": 0.001, "STEPS": 5, "TEMPERATURE": 0.07}},
         "OUTPUT_DIR": "",

@@ -114,6 +114,7 @@ __device__ __forceinline__ float wave_bfly_add(float s) {
 // the launch under (cls, m, n, k) with `work` = executed FLOPs (matrix kernels) or algorithmic bytes (HBM-bound kernels).
 // cls: a GemmEpi id for the fp16 GEMM kernels, MPREID_PROF_* for the others.
 void *mpreid_prof_begin(hipStream_t stream);
+bool mpreid_prof_active(); // mpreid_profile_enable(1) is in force: a launcher whose work figure costs something computes it only then
 void mpreid_prof_end(void *token, hipStream_t stream, int cls, int64_t m, int n, int k, double work);
 
 // Run `f` (returns an mpreid/hip status) once per HIP device for the call site that owns this object: function

@@ -10,8 +10,11 @@
 //      (value, index) order — exactly the position a stable argsort gives it.
 // HBM-bound: 4*nq*ng bytes read once (+ pids); Market-1501 scale: 214 MB.
 // The host finishes CMC / AP from the positions (float64, numpy's pairwise order) — utils/metrics.py.
-// eval_rank_kernel<true> does the same under the Market-1501 protocol (same-identity same-camera gallery items removed).
+// eval_rank_kernel<true, *> does the same under the Market-1501 protocol (same-identity same-camera gallery items removed).
+// eval_rank_kernel<*, true> ranks a batch of (split, query) pairs over ONE resident matrix in one launch: a pair's row is
+// a row of the matrix read through the split's list of columns (multi-trial protocols: VehicleID, RegDB).
 #include "common.h"
+#include <vector>
 
 constexpr int EV_CAP_MAX = 8192; // max relevant gallery items per query handled on the GPU (64 KB of keys + 32 KB of counters)
 constexpr int EV_HIST_MIN = 2112; // counter words of the smallest instance: room for privatised copies of a short bucket list
@@ -41,13 +44,25 @@ __device__ __forceinline__ unsigned long long ev_key(float f, unsigned idx) {
 // position the number of junk keys sorted in front of it and writes the relevant entries compacted.
 // CAM = false is the kernel without the filter: q_cams / g_cams are not read (the launcher passes null) and its
 // instructions are those the non-template kernel compiled to.
-template <bool CAM>
+//
+// SPLITS = true: block b is the PAIR b of a batch -- query row q_row[b] of the resident matrix against the gallery list
+// g_idx[g_off[s] .. g_off[s + 1]) of split s = q_split[b].  q_pids / q_cams / pos_out / cnt_out are indexed by the pair;
+// g_pids / g_cams are the labels of the list entries (pre-gathered by the caller, aligned with g_idx), so step 1 reads them
+// coalesced and only the distances go through the index list: item j of the row is dist[q_row[b]][g_idx[g_off[s] + j]].
+// The key's index field is j, the POSITION IN THE LIST (not the matrix column): the positions are those of a stable
+// argsort of the gathered row, whatever order the list is in.  `ng` is unused (every split has its own length).
+// SPLITS = false reads none of the four trailing arguments (the launchers pass null): the existing instantiations keep
+// their instructions.
+template <bool CAM, bool SPLITS>
 __global__ __launch_bounds__(256) void eval_rank_kernel(const float *__restrict__ dist, int64_t ld, int nq, int ng,
                                                         const long long *__restrict__ q_pids,
                                                         const long long *__restrict__ g_pids,
                                                         const long long *__restrict__ q_cams,
                                                         const long long *__restrict__ g_cams, int rcap, int cap, int hw,
-                                                        int *__restrict__ pos_out, int *__restrict__ cnt_out) {
+                                                        int *__restrict__ pos_out, int *__restrict__ cnt_out,
+                                                        const int *__restrict__ q_row, const int *__restrict__ q_split,
+                                                        const long long *__restrict__ g_off,
+                                                        const int *__restrict__ g_idx) {
     extern __shared__ unsigned long long ev_lds[];
     unsigned long long *rel = ev_lds;
     unsigned *hist = reinterpret_cast<unsigned *>(ev_lds + cap);
@@ -55,7 +70,15 @@ __global__ __launch_bounds__(256) void eval_rank_kernel(const float *__restrict_
     __shared__ int s_wave[CAM ? 8 : 4]; // [4..7]: wave totals of the junk flags
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.x;
-    const float *row = dist + (int64_t)q * ld;
+    const float *row = dist + (int64_t)(SPLITS ? q_row[q] : q) * ld;
+    if constexpr (SPLITS) { // this pair's split: its slice of the gallery lists and its length
+        const int s = q_split[q];
+        const long long o0 = g_off[s];
+        ng = (int)(g_off[s + 1] - o0);
+        g_pids += o0;
+        g_idx += o0;
+        if constexpr (CAM) g_cams += o0;
+    }
     const long long pid = q_pids[q];
     long long cam = 0;
     if constexpr (CAM) cam = q_cams[q];
@@ -73,9 +96,10 @@ __global__ __launch_bounds__(256) void eval_rank_kernel(const float *__restrict_
             if (hit) {
                 const unsigned p = base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
                 if constexpr (CAM) {
-                    if (p < (unsigned)cap) rel[p] = ev_key(row[j], ((unsigned)j << 1) | (g_cams[j] == cam ? 1u : 0u));
+                    if (p < (unsigned)cap)
+                        rel[p] = ev_key(row[SPLITS ? g_idx[j] : j], ((unsigned)j << 1) | (g_cams[j] == cam ? 1u : 0u));
                 } else {
-                    if (p < (unsigned)cap) rel[p] = ev_key(row[j], (unsigned)j);
+                    if (p < (unsigned)cap) rel[p] = ev_key(row[SPLITS ? g_idx[j] : j], (unsigned)j);
                 }
             }
         }
@@ -121,7 +145,7 @@ __global__ __launch_bounds__(256) void eval_rank_kernel(const float *__restrict_
     unsigned *mine = hist + (lane & (C - 1)) * nb;
     for (int j = tid; j < ng; j += 256) {
         // (CAM: flag bit clear -- the item's own list entry, flagged or not, is still the first one >= k)
-        const unsigned long long k = ev_key(row[j], CAM ? (unsigned)j << 1 : (unsigned)j);
+        const unsigned long long k = ev_key(row[SPLITS ? g_idx[j] : j], CAM ? (unsigned)j << 1 : (unsigned)j);
         int lo = 0, hi = R; // first t with rel[t] >= k
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
@@ -190,7 +214,7 @@ __global__ __launch_bounds__(256) void eval_rank_kernel(const float *__restrict_
     for (int t = nrel + tid; t < rcap; t += 256) pos_out[(int64_t)q * rcap + t] = -1;
 }
 
-// the launch geometry of both instantiations: cap (LDS entries of the sorted list), hw (counter words), LDS bytes
+// the launch geometry of every instantiation: cap (LDS entries of the sorted list), hw (counter words), LDS bytes
 static inline size_t ev_geometry(int rcap, int *cap_out, int *hw_out) {
     int cap = 64;
     while (cap < rcap && cap < EV_CAP_MAX) cap <<= 1;
@@ -210,7 +234,7 @@ extern "C" int mpreid_eval_rank_positions(const float *dist_dev, int64_t ld, int
     static PerDeviceOnce attr_once;
     {
         const int rc = attr_once.run([]() -> int {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel<false>),
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel<false, false>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize,
                                         EV_CAP_MAX * 8 + (EV_CAP_MAX + 1) * 4));
             return MPREID_OK;
@@ -218,9 +242,10 @@ extern "C" int mpreid_eval_rank_positions(const float *dist_dev, int64_t ld, int
         if (rc != MPREID_OK) return rc;
     }
     void *ptok = mpreid_prof_begin((hipStream_t)stream);
-    hipLaunchKernelGGL(eval_rank_kernel<false>, dim3((unsigned)nq), dim3(256), lds, (hipStream_t)stream, dist_dev, ld,
-                       nq, ng, (const long long *)q_pids_dev, (const long long *)g_pids_dev,
-                       (const long long *)nullptr, (const long long *)nullptr, rcap, cap, hw, pos_out_dev, cnt_out_dev);
+    hipLaunchKernelGGL((eval_rank_kernel<false, false>), dim3((unsigned)nq), dim3(256), lds, (hipStream_t)stream, dist_dev,
+                       ld, nq, ng, (const long long *)q_pids_dev, (const long long *)g_pids_dev,
+                       (const long long *)nullptr, (const long long *)nullptr, rcap, cap, hw, pos_out_dev, cnt_out_dev,
+                       (const int *)nullptr, (const int *)nullptr, (const long long *)nullptr, (const int *)nullptr);
     mpreid_prof_end(ptok, (hipStream_t)stream, MPREID_PROF_EVALRANK, nq, ng, 0, 4.0 * (double)nq * (double)ng);
     LAUNCH_CHECK();
     return MPREID_OK;
@@ -237,7 +262,7 @@ extern "C" int mpreid_eval_rank_positions_cam(const float *dist_dev, int64_t ld,
     static PerDeviceOnce attr_once; // its own: the attribute belongs to the function, not to the file
     {
         const int rc = attr_once.run([]() -> int {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel<true>),
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel<true, false>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize,
                                         EV_CAP_MAX * 8 + (EV_CAP_MAX + 1) * 4));
             return MPREID_OK;
@@ -245,11 +270,70 @@ extern "C" int mpreid_eval_rank_positions_cam(const float *dist_dev, int64_t ld,
         if (rc != MPREID_OK) return rc;
     }
     void *ptok = mpreid_prof_begin((hipStream_t)stream);
-    hipLaunchKernelGGL(eval_rank_kernel<true>, dim3((unsigned)nq), dim3(256), lds, (hipStream_t)stream, dist_dev, ld, nq,
-                       ng, (const long long *)q_pids_dev, (const long long *)g_pids_dev,
+    hipLaunchKernelGGL((eval_rank_kernel<true, false>), dim3((unsigned)nq), dim3(256), lds, (hipStream_t)stream, dist_dev,
+                       ld, nq, ng, (const long long *)q_pids_dev, (const long long *)g_pids_dev,
                        (const long long *)q_camids_dev, (const long long *)g_camids_dev, rcap, cap, hw, pos_out_dev,
-                       cnt_out_dev);
+                       cnt_out_dev, (const int *)nullptr, (const int *)nullptr, (const long long *)nullptr,
+                       (const int *)nullptr);
     mpreid_prof_end(ptok, (hipStream_t)stream, MPREID_PROF_EVALRANK, nq, ng, 0, 4.0 * (double)nq * (double)ng);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
+// A batch of (split, query) pairs over one resident matrix: include/mpreid.h.  One launch, one block per pair.
+extern "C" int mpreid_eval_rank_positions_splits(const float *dist_dev, int64_t ld, int64_t n_rows, int64_t n_cols, int nqt,
+                                                 const int32_t *q_row_dev, const int32_t *q_split_dev,
+                                                 const int64_t *q_pids_dev, const int64_t *q_camids_dev, int n_splits,
+                                                 const int64_t *g_off_dev, const int32_t *g_idx_dev,
+                                                 const int64_t *g_pids_dev, const int64_t *g_camids_dev, int rcap,
+                                                 int32_t *pos_out_dev, int32_t *cnt_out_dev, mpreid_stream_t stream) {
+    ARG_CHECK(dist_dev && q_row_dev && q_split_dev && q_pids_dev && g_off_dev && g_idx_dev && g_pids_dev && pos_out_dev &&
+              cnt_out_dev);
+    ARG_CHECK((q_camids_dev == nullptr) == (g_camids_dev == nullptr));
+    ARG_CHECK(n_rows > 0 && n_rows <= INT32_MAX && n_cols > 0 && n_cols <= INT32_MAX && ld >= n_cols && nqt > 0 &&
+              n_splits > 0 && rcap > 0);
+    const bool cam = q_camids_dev != nullptr;
+    int cap, hw;
+    const size_t lds = ev_geometry(rcap, &cap, &hw);
+    static PerDeviceOnce attr_once; // one per launcher, as above; it sets both instantiations this launcher starts
+    {
+        const int rc = attr_once.run([]() -> int {
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel<false, true>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        EV_CAP_MAX * 8 + (EV_CAP_MAX + 1) * 4));
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel<true, true>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        EV_CAP_MAX * 8 + (EV_CAP_MAX + 1) * 4));
+            return MPREID_OK;
+        });
+        if (rc != MPREID_OK) return rc;
+    }
+    // profiling runs only: the work figure (4 bytes per gathered distance, summed over the pairs) needs the split of
+    // every pair and the list lengths, which live on the device -- two small blocking copies BEFORE the timed interval
+    double work = 0.0;
+    if (mpreid_prof_active()) {
+        std::vector<int32_t> qs((size_t)nqt);
+        std::vector<int64_t> off((size_t)n_splits + 1);
+        HIP_TRY(hipMemcpyAsync(qs.data(), q_split_dev, qs.size() * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIP_TRY(hipMemcpyAsync(off.data(), g_off_dev, off.size() * 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        for (int b = 0; b < nqt; ++b)
+            if (qs[b] >= 0 && qs[b] < n_splits) work += 4.0 * (double)(off[qs[b] + 1] - off[qs[b]]);
+    }
+    void *ptok = mpreid_prof_begin((hipStream_t)stream);
+    if (cam)
+        hipLaunchKernelGGL((eval_rank_kernel<true, true>), dim3((unsigned)nqt), dim3(256), lds, (hipStream_t)stream,
+                           dist_dev, ld, nqt, 0, (const long long *)q_pids_dev, (const long long *)g_pids_dev,
+                           (const long long *)q_camids_dev, (const long long *)g_camids_dev, rcap, cap, hw, pos_out_dev,
+                           cnt_out_dev, (const int *)q_row_dev, (const int *)q_split_dev, (const long long *)g_off_dev,
+                           (const int *)g_idx_dev);
+    else
+        hipLaunchKernelGGL((eval_rank_kernel<false, true>), dim3((unsigned)nqt), dim3(256), lds, (hipStream_t)stream,
+                           dist_dev, ld, nqt, 0, (const long long *)q_pids_dev, (const long long *)g_pids_dev,
+                           (const long long *)nullptr, (const long long *)nullptr, rcap, cap, hw, pos_out_dev,
+                           cnt_out_dev, (const int *)q_row_dev, (const int *)q_split_dev, (const long long *)g_off_dev,
+                           (const int *)g_idx_dev);
+    mpreid_prof_end(ptok, (hipStream_t)stream, MPREID_PROF_EVALRANK, nqt, (int)n_cols, n_splits, work);
     LAUNCH_CHECK();
     return MPREID_OK;
 }

@@ -2162,6 +2162,7 @@ extern "C" int mpreid_profile_query(mpreid_profile_entry *out, int cap) {
 struct ProfToken {
     hipEvent_t e0;
 };
+bool mpreid_prof_active() { return g_prof_on; }
 void *mpreid_prof_begin(hipStream_t stream) {
     if (!g_prof_on) return nullptr;
     ProfToken *t = new ProfToken{};

@@ -101,3 +101,44 @@ def make_dataloader(cfg):
                                     tuple(cfg.INPUT.SIZE_TEST), int(cfg.TEST.IMS_PER_BATCH), int(d.SYNTH_SEED),
                                     raw=bool(d.get("SYNTH_RAW", False)))
     return None, None, val_loader, int(d.SYNTH_QUERY), int(d.SYNTH_IDS), 6, 1
+
+
+def vehicleid_trial_splits(pids, trials=10, seed=0):
+    """The VehicleID test protocol (reference datasets/vehicleid.py:137-144, looped ten times by test.py:46-63) as DATA:
+    a list of `trials` splits (q_idx, g_idx), int64 indices into the pool whose identities are `pids`.  In trial t one
+    image of every identity -- drawn with ``np.random.default_rng([seed, t])``, the identities visited in order of first
+    appearance in the pool -- is the gallery, all the other images are the queries; both lists ascend in pool order.
+    The reference draws with the unseeded global ``random.choice`` while it parses the dataset, so there are no upstream
+    bits to match: only the protocol is reproduced, and the same (pids, trials, seed) always gives the same splits."""
+    pids = np.asarray(pids)
+    if pids.ndim != 1 or pids.size == 0:
+        raise ValueError("vehicleid_trial_splits: pids must be a non-empty 1-D sequence")
+    if int(trials) < 1:
+        raise ValueError("vehicleid_trial_splits: trials must be >= 1")
+    _, first, inverse = np.unique(pids, return_index=True, return_inverse=True)
+    members = [[] for _ in first]
+    for i, u in enumerate(inverse.ravel()):
+        members[u].append(i)                                  # ascending pool positions of every identity
+    visit = np.argsort(first, kind="stable")                  # identities in order of first appearance
+    splits = []
+    for t in range(int(trials)):
+        rng = np.random.default_rng([int(seed), t])
+        in_gallery = np.zeros(pids.size, dtype=bool)
+        for u in visit:
+            in_gallery[members[u][int(rng.integers(len(members[u])))]] = True
+        splits.append((np.nonzero(~in_gallery)[0].astype(np.int64), np.nonzero(in_gallery)[0].astype(np.int64)))
+    return splits
+
+
+def make_trial_dataloader(cfg):
+    """(pool_loader, splits, num_classes, cam_num, view_num) for a multi-trial protocol (DATASETS.PROTOCOL): the pool is
+    the loader ``make_dataloader`` builds -- the same SYNTH_QUERY + SYNTH_GALLERY images from the same seeds, iterated
+    ONCE -- and the trials are index lists into it (TEST.TRIALS of them, from DATASETS.TRIAL_SEED)."""
+    protocol = str(cfg.DATASETS.get("PROTOCOL", ""))
+    if protocol != "vehicleid":
+        raise NotImplementedError(f"DATASETS.PROTOCOL {protocol!r}: only 'vehicleid' has a split generator here; any other "
+                                  "protocol hands its own (q_idx, g_idx) lists to do_inference_trials")
+    _, _, pool_loader, _, num_classes, cam_num, view_num = make_dataloader(cfg)
+    splits = vehicleid_trial_splits(pool_loader.pids, trials=int(cfg.TEST.get("TRIALS", 10)),
+                                    seed=int(cfg.DATASETS.get("TRIAL_SEED", 0)))
+    return pool_loader, splits, num_classes, cam_num, view_num

@@ -16,7 +16,7 @@ import torch
 
 from mpreid import distributed as _D
 from mpreid.pipeline import EncodePipeline
-from utils.metrics import R1_mAP_eval
+from utils.metrics import R1_mAP_eval, R1_mAP_eval_splits
 
 
 class _ShardedLoader:
@@ -118,13 +118,8 @@ SAME_CAM_NOTE = ("TEST.REMOVE_SAME_CAM: for each query, gallery images of the sa
                  "removed before ranking (Market-1501 protocol)")
 
 
-def do_inference(cfg, model, val_loader, num_query):
-    device = "cuda"
-    logger = logging.getLogger("transreid.test")
-    logger.info("Enter inferencing")
-
-    reranking = bool(getattr(cfg.TEST, "RE_RANKING", False))  # upstream defines the key but never reads it
-    evaluator = R1_mAP_eval(num_query, max_rank=50, feat_norm=cfg.TEST.FEAT_NORM, reranking=reranking)
+def _configure_evaluator(cfg, evaluator):
+    """the evaluator attributes that come from config keys (shared by do_inference and do_inference_trials)"""
     # TEST.DISTANCE_MODE / TEST.RERANK_ALGO (not reference keys): arithmetic of the distance matrix -- 'exact' (default: the
     # bit-parity fp32 chain), 'split3' (fp16 matrix cores, |err| <= 1e-6), 'f16' (one pass, ~1e-4) -- and of the re-ranking
     # ('exact' | 'split3': blend-term distance rows from the fp16 matrix cores, ranks identical, outputs within 1e-6)
@@ -137,6 +132,34 @@ def do_inference(cfg, model, val_loader, num_query):
     evaluator.remove_same_cam = bool(getattr(cfg.TEST, "REMOVE_SAME_CAM", False))
     evaluator.reset()
 
+
+def _encode_into(cfg, model, loader, evaluator):
+    """the reference's loop body (`img = img.to(device); feat = model(img, ...); evaluator.update(...)`, :187-198) as a
+    pipeline: a stager thread drains the loader into pinned group buffers and uploads them on a copy stream while
+    earlier groups are encoded on two alternating streams (mpreid/pipeline.py); the evaluator sees the loader's own
+    batches, in order.  MPREID_PIPELINE="stage=pinned,streams=1,slots=4" overrides the defaults (measurements).
+    Returns (image paths, pipeline statistics)."""
+    img_path_list = []
+    opts = dict(kv.split("=", 1) for kv in os.environ.get("MPREID_PIPELINE", "").split(",") if "=" in kv)
+    pipe = EncodePipeline(model, group=int(opts.get("group", getattr(model, "encode_group", ENCODE_GROUP))),
+                          sie_camera=bool(cfg.MODEL.SIE_CAMERA), sie_view=bool(cfg.MODEL.SIE_VIEW),
+                          streams=int(opts.get("streams", 2)), slots=int(opts.get("slots", 3)),
+                          stage=opts.get("stage", "direct"))
+    for feat, (_, pid, camid, _, _, imgpath) in pipe.run(loader):
+        evaluator.update((feat, pid, camid))
+        img_path_list.extend(imgpath)
+    return img_path_list, pipe.stats
+
+
+def do_inference(cfg, model, val_loader, num_query):
+    device = "cuda"
+    logger = logging.getLogger("transreid.test")
+    logger.info("Enter inferencing")
+
+    reranking = bool(getattr(cfg.TEST, "RE_RANKING", False))  # upstream defines the key but never reads it
+    evaluator = R1_mAP_eval(num_query, max_rank=50, feat_norm=cfg.TEST.FEAT_NORM, reranking=reranking)
+    _configure_evaluator(cfg, evaluator)
+
     # the reference's test.py never initialises a process group (test.py:39,65): under a launcher (WORLD_SIZE > 1) this
     # call does, and binds the rank to cuda:LOCAL_RANK, before anything touches a device (raises when the ranks of the
     # node cannot each see their own device -- MODEL.DEVICE_ID must list them: INTEGRATION.md section C)
@@ -145,23 +168,10 @@ def do_inference(cfg, model, val_loader, num_query):
         logger.info(SAME_CAM_NOTE)
     model.to(device)
     model.eval()
-    img_path_list = []
     if world > 1:
         logger.info("rank {} of {}: encoding 1/{} of the queries and its gallery shard".format(rank, world, world))
         val_loader = shard_val_loader(val_loader, num_query)
-    # the reference's loop body (`img = img.to(device); feat = model(img, ...); evaluator.update(...)`, :187-198) as a
-    # pipeline: a stager thread drains the loader into pinned group buffers and uploads them on a copy stream while
-    # earlier groups are encoded on two alternating streams (mpreid/pipeline.py); the evaluator sees the loader's own
-    # batches, in order.  MPREID_PIPELINE="stage=pinned,streams=1,slots=4" overrides the defaults (measurements).
-    opts = dict(kv.split("=", 1) for kv in os.environ.get("MPREID_PIPELINE", "").split(",") if "=" in kv)
-    pipe = EncodePipeline(model, group=int(opts.get("group", getattr(model, "encode_group", ENCODE_GROUP))),
-                          sie_camera=bool(cfg.MODEL.SIE_CAMERA), sie_view=bool(cfg.MODEL.SIE_VIEW),
-                          streams=int(opts.get("streams", 2)), slots=int(opts.get("slots", 3)),
-                          stage=opts.get("stage", "direct"))
-    for feat, (_, pid, camid, _, _, imgpath) in pipe.run(val_loader):
-        evaluator.update((feat, pid, camid))
-        img_path_list.extend(imgpath)
-    do_inference.last_pipeline_stats = pipe.stats
+    _, do_inference.last_pipeline_stats = _encode_into(cfg, model, val_loader, evaluator)
 
     cmc, mAP, _, _, _, _, _ = evaluator.compute()
     do_inference.last_evaluator = evaluator   # (measurements: bench.py times compute() again on the same features)
@@ -171,3 +181,35 @@ def do_inference(cfg, model, val_loader, num_query):
         for r in [1, 5, 10]:
             logger.info("CMC curve, Rank-{:<3}:{:.1%}".format(r, cmc[r - 1]))
     return cmc[0], cmc[4]
+
+
+def do_inference_trials(cfg, model, pool_loader, splits):
+    """The reference's VehicleID branch (test.py:46-63) with the pool encoded ONCE: `pool_loader` yields every test image
+    one time, `splits` is a list of (q_idx, g_idx) index lists into it, one per trial
+    (datasets.make_dataloader.vehicleid_trial_splits, or any other protocol's lists).  Same encode pipeline and config keys
+    as do_inference (TEST.DISTANCE_MODE, RERANK_ALGO, REMOVE_SAME_CAM, RE_RANKING); the evaluator is R1_mAP_eval_splits.
+    Logs the reference's per-trial line (its missing placeholder supplied) and its averaged line; returns
+    (rank1 [S], rank5 [S], mAP [S]).  Single-process: under WORLD_SIZE > 1 the evaluator raises NotImplementedError."""
+    import numpy as np
+    device = "cuda"
+    logger = logging.getLogger("transreid.test")
+    logger.info("Enter inferencing: {} trials over one encoded pool".format(len(splits)))
+    reranking = bool(getattr(cfg.TEST, "RE_RANKING", False))
+    evaluator = R1_mAP_eval_splits(splits, max_rank=50, feat_norm=cfg.TEST.FEAT_NORM, reranking=reranking)
+    _configure_evaluator(cfg, evaluator)
+    if evaluator.remove_same_cam:
+        logger.info(SAME_CAM_NOTE)
+    model.to(device)
+    model.eval()
+    _, do_inference_trials.last_pipeline_stats = _encode_into(cfg, model, pool_loader, evaluator)
+    cmcs, mAPs, _, _, _ = evaluator.compute()
+    do_inference_trials.last_evaluator = evaluator
+    rank1 = np.array([c[0] for c in cmcs])
+    rank5 = np.array([c[min(4, len(c) - 1)] for c in cmcs])   # (a gallery of fewer than 5 items: its last rank)
+    for trial in range(len(cmcs)):
+        logger.info("rank_1:{:.1%}, rank_5 {:.1%}, mAP {:.1%} : trial : {}".format(rank1[trial], rank5[trial], mAPs[trial],
+                                                                                  trial))
+    n = float(len(cmcs))
+    logger.info("sum_rank_1:{:.1%}, sum_rank_5 {:.1%}, sum_mAP {:.1%}".format(rank1.sum() / n, rank5.sum() / n,
+                                                                              mAPs.sum() / n))
+    return rank1, rank5, mAPs

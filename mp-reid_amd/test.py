@@ -7,8 +7,10 @@ config (YAML + command-line overrides, frozen) -> logger ("transreid", <OUTPUT_D
 model -> ``load_param(TEST.WEIGHT)`` -> ``do_inference`` (ViT-B/16 on the GPU, R1_mAP_eval with the HIP distance /
 re-ranking kernels).  Differences from the reference, on purpose: TEST.WEIGHT may be empty (seeded random weights, for
 smoke runs); MODEL.DEVICE_ID selects the HIP device through HIP_VISIBLE_DEVICES *before* anything touches the GPU;
-the VehicleID 10-trial loop is not reproduced (VehicleID's parser is out of scope); ``main`` returns
-(rank1, rank5) so that tests can call it in-process.  Multi-GPU: ``python -m torch.distributed.run --nnodes=1
+the VehicleID 10-trial loop (test.py:46-63) is taken with DATASETS.PROTOCOL vehicleid (not NAMES: VehicleID's parser is out
+of scope) and encodes the pool ONCE -- TEST.TRIALS trials drawn from DATASETS.TRIAL_SEED are ranked against one resident
+pool x pool matrix (processor.do_inference_trials); ``main`` returns (rank1, rank5) -- (rank1 [S], rank5 [S], mAP [S])
+under that protocol -- so that tests can call it in-process.  Multi-GPU: ``python -m torch.distributed.run --nnodes=1
 --nproc-per-node P --master-addr 127.0.0.1 test.py --config_file ...`` runs one rank per GPU; every rank encodes its
 shard and all of them return the same (rank1, rank5) as the single-GPU run.
 """
@@ -69,6 +71,8 @@ def main(argv=None):
     from model.make_model import make_model
     from processor.processor import do_inference
 
+    if str(cfg.DATASETS.get("PROTOCOL", "")) == "vehicleid":
+        return _main_trials(cfg, logger, world)
     _, _, val_loader, num_query, num_classes, camera_num, view_num = make_dataloader(cfg)
     model = make_model(cfg, num_class=num_classes, camera_num=camera_num, view_num=view_num)
     if cfg.TEST.WEIGHT:
@@ -81,6 +85,22 @@ def main(argv=None):
         dist.barrier()
         dist.destroy_process_group()
     return res
+
+
+def _main_trials(cfg, logger, world):
+    """DATASETS.PROTOCOL vehicleid (reference test.py:46-63): TEST.TRIALS trials over one encoded pool"""
+    if world > 1:
+        raise NotImplementedError("multi-trial evaluation is single-process")
+    from datasets.make_dataloader import make_trial_dataloader
+    from model.make_model import make_model
+    from processor.processor import do_inference_trials
+    pool_loader, splits, num_classes, camera_num, view_num = make_trial_dataloader(cfg)
+    model = make_model(cfg, num_class=num_classes, camera_num=camera_num, view_num=view_num)
+    if cfg.TEST.WEIGHT:
+        model.load_param(cfg.TEST.WEIGHT)
+    else:
+        logger.info("TEST.WEIGHT is empty: evaluating the seeded random initialisation (MODEL.INIT_SEED)")
+    return do_inference_trials(cfg, model, pool_loader, splits)
 
 
 if __name__ == "__main__":

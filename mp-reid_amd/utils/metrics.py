@@ -22,6 +22,13 @@ the relevant ones, a relevant item's position counts the kept items with a small
 a query is valid iff a relevant item is left.  That is eval_func with its line :54 restored.  max_rank is clamped by the
 gallery size before the filter (:36-38); a row that keeps fewer than max_rank items continues its CMC at 1 after its
 first hit (the reference could not stack such ragged rows).
+
+Multi-trial protocols (VehicleID's ten trials, reference test.py:46-63 + datasets/vehicleid.py:137-144; RegDB's trials and
+MMMP's exp_setting pairs are of the same kind) evaluate several (query set, gallery set) pairs over ONE set of images.  The
+reference re-encodes everything per trial; here the pool is encoded once and the trials are DATA: a split is a pair
+(q_idx, g_idx) of integer arrays indexing the pool in update() order -- non-empty, in [0, N), g_idx without duplicates
+(ValueError naming the split otherwise; a query that is also in its own gallery list is allowed).  eval_func_splits (host
+definition), eval_func_splits_device (one ranking launch over the resident pool x pool matrix) and R1_mAP_eval_splits.
 """
 import numpy as np
 import torch
@@ -109,6 +116,49 @@ def eval_func(distmat, q_pids, g_pids, q_camids, g_camids, max_rank=50, remove_s
 _warned_host_ranking = False
 
 
+def _finish_positions(pos, cnt, fetch_rows, q_pids, g_pids, max_rank, rcap, q_camids=None, g_camids=None):
+    """The host tail of the device ranking, shared by the single-split and the multi-split paths: from the kernel's
+    positions (pos [rows, rcap] int64 padded with -1, cnt [rows] int64) to (cmc hit counts, AP of every valid row, number of
+    valid rows) in float64.  Rows handed back with cnt < 0 (more relevant items than the kernel holds in LDS) are ranked
+    here: ``fetch_rows(over)`` returns their distance rows [len(over), ng] as numpy, aligned with g_pids / g_camids."""
+    num_q = pos.shape[0]
+    cam = q_camids is not None
+    over = np.nonzero(cnt < 0)[0]          # queries with more relevant items than the kernel handles: host ranking
+    if over.size:
+        global _warned_host_ranking
+        if not _warned_host_ranking:
+            _warned_host_ranking = True
+            import logging
+            logging.getLogger("transreid.test").warning(
+                "eval_func: %d of %d queries have more than %d relevant gallery items; their rows are ranked on the host "
+                "(np.argsort per row, same result)", over.size, num_q, rcap)
+        pos = np.concatenate([pos, np.full((num_q, 0), -1, np.int64)], axis=1)
+        rows = fetch_rows(over)
+        wide = max(int((g_pids[None, :] == q_pids[over, None]).sum(1).max()), pos.shape[1])
+        pos = np.pad(pos, ((0, 0), (0, wide - pos.shape[1])), constant_values=-1)
+        for r, qi in enumerate(over):
+            order = np.argsort(rows[r], kind="stable")
+            match = g_pids[order] == q_pids[qi]
+            if cam:   # the same filter as the kernel: positions among the kept items
+                junk = match & (g_camids[order] == q_camids[qi])
+                p = (np.cumsum(~junk) - 1)[match & ~junk]
+            else:
+                p = np.nonzero(match)[0]
+            pos[qi, :] = -1
+            pos[qi, :p.size] = p
+            cnt[qi] = p.size
+    valid = cnt > 0
+    num_valid = int(valid.sum())
+    if num_valid == 0:
+        return np.zeros(max_rank, np.float32), np.zeros(0, np.float64), 0
+    pos, cnt = pos[valid], cnt[valid]
+    first = pos[:, 0]
+    cmc_rows = (np.arange(max_rank)[None, :] >= first[:, None]).astype(np.float32)
+    t = np.arange(1, pos.shape[1] + 1, dtype=np.float64)[None, :]
+    terms = np.where(pos >= 0, t / np.maximum(pos + 1.0, 1.0), 0.0)
+    return cmc_rows.sum(0), terms.sum(axis=1) / cnt, num_valid
+
+
 def _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch=None, q_camids=None, g_camids=None):
     """Ranking statistics of the query ROWS in `dist` (device tensor [rows, ng] fp32): (cmc hit counts [max_rank] float32
     summed over the valid rows, AP of every valid row in row order (float64), number of valid rows).  Sums of 0/1 values
@@ -135,7 +185,7 @@ def _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch=None, q_camid
         if after_launch is not None:
             after_launch()
         return np.zeros(max_rank, np.float32), np.zeros(0, np.float64), 0
-    rcap = int(min(max(np.unique(g_pids, return_counts=True)[1].max(), 1), 8192))   # (the kernel's LDS limit, include/mpreid.h)
+    rcap = _pid_rcap(g_pids)
     qp, gp = torch.from_numpy(q_pids).to(dev), torch.from_numpy(g_pids).to(dev)
     pos = torch.empty((num_q, rcap), dtype=torch.int32, device=dev)
     cnt = torch.empty(num_q, dtype=torch.int32, device=dev)
@@ -154,40 +204,8 @@ def _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch=None, q_camid
     if after_launch is not None:
         after_launch()
     pos, cnt = pos.cpu().numpy().astype(np.int64), cnt.cpu().numpy().astype(np.int64)
-    over = np.nonzero(cnt < 0)[0]          # queries with more relevant items than the kernel handles: host ranking
-    if over.size:
-        global _warned_host_ranking
-        if not _warned_host_ranking:
-            _warned_host_ranking = True
-            import logging
-            logging.getLogger("transreid.test").warning(
-                "eval_func: %d of %d queries have more than %d relevant gallery items; their rows are ranked on the host "
-                "(np.argsort per row, same result)", over.size, num_q, rcap)
-        pos = np.concatenate([pos, np.full((num_q, 0), -1, np.int64)], axis=1)
-        rows = dist[torch.from_numpy(over).to(dev)].cpu().numpy()
-        wide = max(int((g_pids[None, :] == q_pids[over, None]).sum(1).max()), pos.shape[1])
-        pos = np.pad(pos, ((0, 0), (0, wide - pos.shape[1])), constant_values=-1)
-        for r, qi in enumerate(over):
-            order = np.argsort(rows[r], kind="stable")
-            match = g_pids[order] == q_pids[qi]
-            if cam:   # the same filter as the kernel: positions among the kept items
-                junk = match & (g_camids[order] == q_camids[qi])
-                p = (np.cumsum(~junk) - 1)[match & ~junk]
-            else:
-                p = np.nonzero(match)[0]
-            pos[qi, :] = -1
-            pos[qi, :p.size] = p
-            cnt[qi] = p.size
-    valid = cnt > 0
-    num_valid = int(valid.sum())
-    if num_valid == 0:
-        return np.zeros(max_rank, np.float32), np.zeros(0, np.float64), 0
-    pos, cnt = pos[valid], cnt[valid]
-    first = pos[:, 0]
-    cmc_rows = (np.arange(max_rank)[None, :] >= first[:, None]).astype(np.float32)
-    t = np.arange(1, pos.shape[1] + 1, dtype=np.float64)[None, :]
-    terms = np.where(pos >= 0, t / np.maximum(pos + 1.0, 1.0), 0.0)
-    return cmc_rows.sum(0), terms.sum(axis=1) / cnt, num_valid
+    return _finish_positions(pos, cnt, lambda over: dist[torch.from_numpy(over).to(dev)].cpu().numpy(), q_pids, g_pids,
+                             max_rank, rcap, q_camids, g_camids)
 
 
 def eval_func_device(dist, q_pids, g_pids, q_camids=None, g_camids=None, max_rank=50, after_launch=None,
@@ -259,6 +277,122 @@ def eval_func_sharded(dist_rows, q_pids_local, g_pids, max_rank=50, q_camids_loc
         ap = np.concatenate([p[max_rank + 1: max_rank + 1 + int(p[max_rank])] for p in parts])
     assert num_valid > 0, "Error: all query identities do not appear in gallery"
     return hits / float(num_valid), np.mean(ap)
+
+
+def _check_splits(splits, n):
+    """the splits [(q_idx, g_idx), ...] as int64 arrays, validated against a pool of n items (module docstring)"""
+    out = []
+    if len(splits) == 0:
+        raise ValueError("splits: no split given")
+    for i, split in enumerate(splits):
+        try:
+            q, g = split
+            q, g = np.asarray(q), np.asarray(g)
+        except (TypeError, ValueError):
+            raise ValueError(f"split {i}: not a (q_idx, g_idx) pair") from None
+        for name, a in (("q_idx", q), ("g_idx", g)):
+            if a.ndim != 1 or a.size == 0:
+                raise ValueError(f"split {i}: {name} is empty (or not a 1-D list)")
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"split {i}: {name} is not an integer array")
+            if int(a.min()) < 0 or int(a.max()) >= n:
+                raise ValueError(f"split {i}: {name} has an index outside [0, {n})")
+        if np.unique(g).size != g.size:
+            raise ValueError(f"split {i}: g_idx has duplicates")
+        out.append((q.astype(np.int64), g.astype(np.int64)))
+    return out
+
+
+def eval_func_splits(distmat_pool, pids, camids, splits, max_rank=50, remove_same_cam=False):
+    """CMC and mAP of several (query set, gallery set) pairs over ONE pool x pool distance matrix (multi-trial protocols:
+    module docstring).  By definition eval_func on every split's sub-matrix:
+    ``eval_func(distmat_pool[np.ix_(q, g)], pids[q], pids[g], camids[q], camids[g], max_rank, remove_same_cam)``.
+    Returns (list of S float32 cmc arrays -- each min(max_rank, len(g)) long, eval_func's own rule -- , float64 mAP [S]).
+    Host, numpy."""
+    distmat_pool = np.asarray(distmat_pool)
+    pids = np.asarray(pids)
+    camids = None if camids is None else np.asarray(camids)
+    if remove_same_cam and camids is None:
+        raise ValueError("remove_same_cam=True needs camids")
+    splits = _check_splits(splits, pids.shape[0])
+    cmcs, maps = [], np.zeros(len(splits), np.float64)
+    for i, (q, g) in enumerate(splits):
+        cmc, maps[i] = eval_func(distmat_pool[np.ix_(q, g)], pids[q], pids[g], None if camids is None else camids[q],
+                                 None if camids is None else camids[g], max_rank, remove_same_cam)
+        cmcs.append(cmc)
+    return cmcs, maps
+
+
+def _pid_rcap(pids):
+    return int(min(max(np.unique(pids, return_counts=True)[1].max(), 1), 8192))   # (the kernel's LDS limit, include/mpreid.h)
+
+
+def eval_func_splits_device(dist_pool, pids, camids, splits, max_rank=50, remove_same_cam=False):
+    """eval_func_splits with the ranking on the GPU: `dist_pool` is the pool x pool matrix as a device fp32 tensor (unit
+    column stride, rows through dist_pool.stride(0); left on the device).  ONE launch of mpreid_eval_rank_positions_splits
+    ranks every (split, query) pair -- a pair reads its row of the matrix through its split's gallery index list, no
+    sub-matrix is gathered -- and ONE D2H copy brings the positions back; per split, CMC / AP are then finished by the
+    float64 tail eval_func_device uses (_finish_positions), so a split's numbers are those of eval_func_device on its
+    sub-matrix.  Rows over the kernel's capacity are ranked on the host from the gathered row."""
+    import ctypes as C
+    from mpreid import _lib
+    dev = _lib.require_gpu()
+    L = _lib.load()
+    dist = dist_pool.detach()
+    assert dist.is_cuda and dist.dtype == torch.float32 and dist.dim() == 2 and dist.stride(1) == 1
+    pids = np.ascontiguousarray(pids, dtype=np.int64)
+    n = pids.shape[0]
+    assert dist.shape[0] == n and dist.shape[1] == n, f"dist_pool is {tuple(dist.shape)} for a pool of {n}"
+    cam = bool(remove_same_cam)
+    if cam:
+        if camids is None:
+            raise ValueError("remove_same_cam=True needs camids")
+        camids = np.ascontiguousarray(camids, dtype=np.int64)
+        assert camids.shape == pids.shape
+    splits = _check_splits(splits, n)
+    S = len(splits)
+    q_sizes = np.array([q.size for q, _ in splits], np.int64)
+    g_off = np.zeros(S + 1, np.int64)
+    g_off[1:] = np.cumsum([g.size for _, g in splits])
+    q_off = np.zeros(S + 1, np.int64)
+    q_off[1:] = np.cumsum(q_sizes)
+    nqt = int(q_off[-1])
+    assert nqt < 2 ** 31 and int(g_off[-1]) < 2 ** 40
+    q_row = np.concatenate([q for q, _ in splits])
+    g_idx = np.concatenate([g for _, g in splits])
+    q_split = np.repeat(np.arange(S, dtype=np.int32), q_sizes)
+    rcap = _pid_rcap(pids)                                    # bounds the pid matches of any row in any split
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
+    t_qrow, t_qsplit, t_gidx = up(q_row.astype(np.int32)), up(q_split), up(g_idx.astype(np.int32))
+    t_qp, t_goff, t_gp = up(pids[q_row]), up(g_off), up(pids[g_idx])
+    t_qc, t_gc = (up(camids[q_row]), up(camids[g_idx])) if cam else (None, None)
+    out = torch.empty(nqt * (rcap + 1), dtype=torch.int32, device=dev)      # pos [nqt][rcap] | cnt [nqt]: one D2H copy
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None     # noqa: E731
+    _lib.check(L.mpreid_eval_rank_positions_splits(
+        ptr(dist), dist.stride(0), n, n, nqt, ptr(t_qrow), ptr(t_qsplit), ptr(t_qp), ptr(t_qc), S, ptr(t_goff),
+        ptr(t_gidx), ptr(t_gp), ptr(t_gc), rcap, ptr(out), C.c_void_p(out.data_ptr() + 4 * nqt * rcap),
+        _lib.stream_ptr()), "mpreid_eval_rank_positions_splits")
+    host = out.cpu().numpy().astype(np.int64)
+    pos_all, cnt_all = host[:nqt * rcap].reshape(nqt, rcap), host[nqt * rcap:]
+    cmcs, maps = [], np.zeros(S, np.float64)
+    for i, (q, g) in enumerate(splits):
+        mr = max_rank
+        if g.size < mr:
+            mr = g.size
+            print("Note: number of gallery samples is quite small, got {}".format(g.size))
+        g_pids = pids[g]
+        w = _pid_rcap(g_pids)           # the width the single-split call gives its rows: the same float64 sums, bit for bit
+        lo, hi = int(q_off[i]), int(q_off[i + 1])
+        g_t = t_gidx[int(g_off[i]):int(g_off[i + 1])].long()
+
+        def fetch_rows(over, q=q, g_t=g_t):
+            return dist[torch.from_numpy(q[over]).to(dev)].index_select(1, g_t).cpu().numpy()
+        hits, ap, num_valid = _finish_positions(pos_all[lo:hi, :w].copy(), cnt_all[lo:hi].copy(), fetch_rows, pids[q],
+                                                g_pids, mr, w, camids[q] if cam else None, camids[g] if cam else None)
+        assert num_valid > 0, f"split {i}: Error: all query identities do not appear in gallery"
+        cmcs.append(hits / float(num_valid))
+        maps[i] = np.mean(ap)
+    return cmcs, maps
 
 
 def _check_finite(feats, collective=False):
@@ -450,3 +584,91 @@ class R1_mAP_eval():
             gf_host = D.gather_row_blocks_to_host(gf_local, dst=0)
             gf_out = torch.from_numpy(gf_host) if rank == 0 else gf_local
         return cmc, mAP, distmat, pids, camids, qf.cpu(), gf_out.cpu()
+
+
+def _pool_matrix_fits(n):
+    """whether the pool x pool fp32 matrix (4 n^2 bytes) stays under a quarter of the device's memory (mpreid_device_info)"""
+    import ctypes as C
+    from mpreid import _lib
+    hbm = C.c_size_t(0)
+    _lib.check(_lib.load().mpreid_device_info(None, 0, None, C.byref(hbm)), "mpreid_device_info")
+    return 4 * int(n) * int(n) <= int(hbm.value) // 4
+
+
+class R1_mAP_eval_splits():
+    """R1_mAP_eval for protocols that evaluate several (query set, gallery set) pairs over ONE set of images (VehicleID's
+    trials, reference test.py:46-63): update() takes the pool once, `splits` is a list of (q_idx, g_idx) index lists into
+    the pool in update() order.  compute() -> (cmc_list, mAP [S], pids, camids, feats_host).
+
+    Without re-ranking the pool x pool distance matrix is computed ONCE, stays on the device (``last_dist``) and every
+    split is ranked against it in one launch (eval_func_splits_device); an entry D[q, g] has the bits the single-split
+    evaluator computes for the same two feature rows.  With re-ranking the matrix depends on the split (the k-reciprocal
+    neighbourhoods are those of the split's own query + gallery set), and a pool whose matrix would exceed a quarter of
+    the device's memory has no room for it: both go split by split through the single-split code (gather the features,
+    re_ranking_device / euclidean_distance, eval_func_device).  Single-process only."""
+
+    def __init__(self, splits, max_rank=50, feat_norm=True, reranking=False):
+        self.splits = splits
+        self.max_rank = max_rank
+        self.feat_norm = feat_norm
+        self.reranking = reranking
+        self.distance_mode = _ops.GEMM_F32_EXACT
+        self.rerank_algo = _ops.RERANK_AUTO
+        self.remove_same_cam = False
+        self.last_rerank_stats = None
+        self.last_dist = None          # the pooled device matrix of the last compute() (None on the split-by-split path)
+
+    def reset(self):
+        self.feats = []
+        self.pids = []
+        self.camids = []
+        self.last_dist = None
+
+    def update(self, output):  # called once for each batch of the pool
+        feat, pid, camid = output
+        dev = _ops._lib.require_gpu()
+        self.feats.append(feat.detach().to(device=dev, dtype=torch.float32, copy=True))
+        self.pids.extend(np.asarray(pid))
+        self.camids.extend(np.asarray(camid))
+
+    def compute(self):
+        from mpreid import distributed as D
+        if D.sharded_active():
+            raise NotImplementedError("multi-trial evaluation is single-process")
+        feats = torch.cat(self.feats, dim=0)
+        _check_finite(feats)
+        if self.feat_norm:
+            print("The test feature is normalized")
+            feats = _ops.l2_normalize(feats)
+        (h_feats,), feats_copied = _to_host_async([feats])
+        pids, camids = np.asarray(self.pids), np.asarray(self.camids)
+        n = feats.shape[0]
+        splits = _check_splits(self.splits, n)
+        same_cam = bool(self.remove_same_cam)
+        self.last_dist = None
+        if not self.reranking and _pool_matrix_fits(n):
+            print('=> Computing the pool DistMat with euclidean_distance')
+            dist = _ops.euclidean_distance(feats, feats, mode=self.distance_mode)
+            cmcs, maps = eval_func_splits_device(dist, pids, camids, splits, self.max_rank, same_cam)
+            self.last_dist = dist
+        else:
+            dev = feats.device
+            cmcs, maps = [], np.zeros(len(splits), np.float64)
+            for i, (q, g) in enumerate(splits):
+                qf = feats[torch.from_numpy(q).to(dev)]
+                gf = feats[torch.from_numpy(g).to(dev)]
+                if self.reranking:
+                    print('=> Enter reranking')
+                    dist, self.last_rerank_stats = re_ranking_device(qf, gf, k1=50, k2=15, lambda_value=0.3,
+                                                                     algo=self.rerank_algo)
+                    _ops.release_workspaces("rerank")
+                else:
+                    dist = _ops.euclidean_distance(qf, gf, mode=self.distance_mode)
+                try:
+                    cmc, maps[i] = eval_func_device(dist, pids[q], pids[g], camids[q], camids[g], self.max_rank,
+                                                    remove_same_cam=same_cam)
+                except AssertionError as e:
+                    raise AssertionError(f"split {i}: {e}") from None
+                cmcs.append(cmc)
+        feats_copied.synchronize()
+        return cmcs, maps, self.pids, self.camids, h_feats
