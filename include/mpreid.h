@@ -579,6 +579,37 @@ int mpreid_conv_f16_nhwc(const void *act_dev, int batch, int h, int w, int cin, 
                          int cout, int cout_pad, int taps, const void *identity_dev, int relu, void *out_dev,
                          const void *zero_page_dev, mpreid_stream_t stream);
 
+/* One convolution of the SPLIT-precision RN50 tower as mpreid_rn50_forward_split runs it (unit tests, micro-benchmarks):
+ * the tower's own layer routine behind a C entry point, every operand and output form it has.  M = batch * h * w
+ * pixels; every row count is padded to Mp = M rounded up to 256.  conv: weights in the layouts documented at
+ * mpreid_rn50_conv_split above, taps 1 or 9 (stride 1, pad 1).
+ * Operand -- exactly one of
+ *   in_dev         fp32 NHWC [M][ld_in], the first conv->cin channels real (ld_in >= cin, ld_in % 4 == 0, 16-byte aligned;
+ *                  channels >= cin are not read); relu_in != 0: max(x, 0) is applied on the way.  Packed into
+ *                  pair_scratch_dev, fp16 [Mp][2 * kseg] = [hi(kseg) | lo(kseg)], rows >= M and channels >= cin zero
+ *   in_pairs_dev   that pair matrix, delivered by the caller (taps 1: all Mp rows are read; taps 9: rows < M);
+ *                  ld_in / relu_in / pair_scratch_dev are ignored
+ * Output, y = acc * oscale + bias with acc = sum over k of hi.hi' + lo.hi' + hi.lo' in fp32:
+ *   res 0, out_pairs_dev NULL      out_dev fp32 [Mp][npad] = y
+ *   res 1 (taps 1)                 out_dev += y;    res 2 (taps 1): out_dev = max(out_dev, 0) + y (the destination is a
+ *                                  block input whose ReLU was never written back)
+ *   res 0, out_pairs_dev           fp16 pairs [Mp][2 * pair_c] = [hi | lo] of relu(y), hi = fp16(v), lo = fp16(v - hi);
+ *                                  columns [cout, pair_c) zero in both halves; out_dev is not touched (may be NULL).
+ *                                  pair_c % 64 == 0, cout <= pair_c <= npad (taps 9: pair_c == 64 when cout <= 64, else
+ *                                  pair_c <= cout rounded up to 128)
+ *   res 1 / 2, out_pairs_dev       (taps 1, pair_c == npad) out_dev as above AND the pairs of relu(out_dev)
+ * Rows: taps 1 computes all Mp rows -- fp32 rows and pair rows in [M, Mp) ARE written (y of the zero rows of the packed
+ * operand, i.e. the bias, or whatever rows [M, Mp) of in_pairs_dev hold); taps 9 writes rows < M only.  All npad
+ * (2 * pair_c) columns of a written row are written, with one exception: a taps 9 convolution with cout <= 64 runs in ONE
+ * 64-wide tile and writes fp32 columns [0, 64) only (the tower never reads a padded column).  Written fp32 columns
+ * >= cout hold y of the zero weight rows (0 + bias 0).
+ * zero_page_dev: 256 bytes of zeros (taps 9; may be NULL for taps 1).  Argument errors: MPREID_ERR_ARG; those on the
+ * operand, res and the pair output's shape are found before anything is launched, the remaining ones of the GEMM
+ * launchers (alignment, sizes) after the pack of in_dev into pair_scratch_dev has been queued. */
+int mpreid_rn50_conv_split_layer(const mpreid_rn50_conv_split *conv, const float *in_dev, int ld_in, int relu_in,
+                                 const void *in_pairs_dev, int batch, int h, int w, int res, float *out_dev, void *out_pairs_dev,
+                                 int pair_c, void *pair_scratch_dev, const void *zero_page_dev, mpreid_stream_t stream);
+
 /* fp16 GEMM used by the encoder, exposed for the roofline bench and unit tests:
  * C[M][N] (fp32) = A[M][K] (fp16) x B[N][K]^T (fp16).  M, N multiples of 128... see DESIGN.md. */
 int mpreid_gemm_f16_nt(const void *a_dev, const void *b_dev, float *c_dev, int64_t m, int64_t n, int64_t k,

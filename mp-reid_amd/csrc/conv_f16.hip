@@ -288,6 +288,8 @@ int launch_conv_f16(const ConvArgs &a, hipStream_t stream) {
     if (a.split) {   // the pair form: 3x3 only, fp32 out
         ARG_CHECK(a.act && a.wgt && a.bias && (a.out32 || a.out_pairs) && a.zero_page && a.taps == 9 && a.C > 0 && a.C % CBK == 0 && a.M > 0);
         ARG_CHECK(!a.out_pairs || (a.pair_c % 64 == 0 && a.pair_c >= a.N));
+        // every pair column must lie in a tile (64 wide up to 64 channels, else 128): a column past the last tile would never be written
+        ARG_CHECK(!a.out_pairs || a.pair_c <= (a.N <= 64 ? 64 : (a.N + 127) / 128 * 128));
         ARG_CHECK(a.Npad % 128 == 0 && a.N > 0 && a.Npad >= a.N && a.ldo % 4 == 0 && a.ldo >= a.Npad && a.H > 0 && a.W > 0 &&
                   a.M % (a.H * a.W) == 0);
         return a.N <= 64 ? launch_conv_variant<9, false, 64, true>(a, stream) : launch_conv_variant<9, false, 128, true>(a, stream);

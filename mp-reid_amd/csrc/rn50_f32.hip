@@ -545,6 +545,9 @@ LayoutSplit layout_split(const mpreid_rn50_cfg *cfg, int B) {
     // activation buffers: the widest tensors are the stem's (H/2 x W/2 x width), layer1's (H/4 x W/4 x 4 width, strides padded to
     // 128) and -- per pixel count -- nothing later is larger
     const int64_t px2 = (int64_t)(cfg->img_h / 2) * (cfg->img_w / 2), px4 = px2 / 4;
+    // (A 3x3 convolution with cout <= 64 -- the stem's, layer1's conv2 -- runs in one 64-wide tile and writes columns [0, 64) of its
+    // 128-float rows only: columns [64, 128) of those buffers stay UNINITIALISED.  Every reader -- the packs, the average pools --
+    // reads the C real channels and nothing past them.)
     // GEMM outputs have their rows padded to 256 and their channel stride to 128.  Widest tensor per resolution: the stem's
     // (H/2 x W/2 x width); H/4: layer1's output 4 width; H/8: layer2's 8 width; H/16: layer4's 32 width
     int64_t a = pad_rows((int64_t)B * px2) * np(wd);
@@ -597,12 +600,17 @@ int conv_split(const mpreid_rn50_conv_split &c, ActView &in, int B, int H, int W
     // for the implicit GEMM, include/mpreid.h)
     ARG_CHECK(c.w && c.bias && c.cin == in.C && c.cin % 4 == 0 && c.kseg % 64 == 0 && c.kseg >= c.cin &&
               (c.taps == 9 || c.kseg >= c.taps * c.cin) && c.npad % 128 == 0 && c.npad >= c.cout && (c.taps == 1 || c.taps == 9));
+    // (the 1x1 pair epilogues' shapes, ahead of the pack: a bad call launches nothing; checked again where they are used)
+    ARG_CHECK(c.taps == 9 || !pair_out || (res ? pair_c == c.npad : (pair_c % 64 == 0 && pair_c >= c.cout && pair_c <= c.npad)));
     const int64_t threads = Mp * (c.kseg / 4);
     const dim3 grid((unsigned)((threads + 255) / 256));
     if (c.taps == 9) {
         // 3x3: the input as pairs [pixel][hi(C) | lo(C)] (ReLU applied on the way), then the implicit GEMM over the nine shifted
         // views of it (conv_f16.hip, pair form) -- no im2col matrix (it cost 9x the activation bytes, written and read)
         ARG_CHECK(res == 0 && zero_page != nullptr);
+        // the pair output's shape, checked HERE (launch_conv_f16 checks it again) so that a bad call launches nothing: every pair
+        // column must lie in a tile of the implicit GEMM (one 64-wide tile up to 64 channels, else 128-wide ones)
+        ARG_CHECK(!pair_out || (pair_c % 64 == 0 && pair_c >= c.cout && pair_c <= (c.cout <= 64 ? 64 : c.npad)));
         if (act_pairs)   // the producer wrote this convolution's pair operand itself (GE_S_BIAS_RELU_PAIR)
             pairs = const_cast<_Float16 *>(act_pairs);
         else if (in.dirty)
@@ -653,7 +661,7 @@ int conv_split(const mpreid_rn50_conv_split &c, ActView &in, int B, int H, int W
         return launch_gemm_f16(g, GE_S_BIAS_RES_PAIR, stream);
     }
     if (pair_out) {        // 1x1 whose only consumer is a pair convolution: relu(.) as that convolution's operand, no fp32 tensor
-        ARG_CHECK(res == 0 && pair_c % 64 == 0 && pair_c >= c.cout);
+        ARG_CHECK(res == 0 && pair_c % 64 == 0 && pair_c >= c.cout && pair_c <= c.npad);   // (columns past npad have no tile: nobody would write them)
         g.out = pair_out;
         g.ldo = 2 * (int64_t)pair_c;
         g.pair_c = pair_c;
@@ -849,4 +857,20 @@ extern "C" int mpreid_rn50_forward_split_view(const mpreid_rn50_cfg *cfg, const 
                                               float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
     ARG_CHECK((img_f32 != nullptr) != (img_hwc != nullptr) && (!img_hwc || (mean && stdv)) && view >= 0 && view <= 3);
     return rn50_forward_split_impl(cfg, w, stem_in(img_f32, img_hwc, mean, stdv, view), B, out, ws, ws_bytes, stream_);
+}
+
+// unit-test / micro-benchmark entry: ONE convolution of the split tower, every operand and output form conv_split has
+// (include/mpreid.h).  Nothing is launched here: the pack, the GEMM / implicit GEMM and their checks are conv_split's.
+extern "C" int mpreid_rn50_conv_split_layer(const mpreid_rn50_conv_split *conv, const float *in, int ld_in, int relu_in,
+                                            const void *in_pairs, int batch, int h, int w, int res, float *out, void *out_pairs,
+                                            int pair_c, void *pair_scratch, const void *zero_page, mpreid_stream_t stream) {
+    ARG_CHECK(conv != nullptr && batch > 0 && h > 0 && w > 0 && (int64_t)batch * h * w <= (int64_t)INT32_MAX - 256);
+    ARG_CHECK((in != nullptr) != (in_pairs != nullptr));              // the operand: fp32 (packed here) or pairs, not both
+    ARG_CHECK(!in || (pair_scratch != nullptr && ld_in >= conv->cin && ld_in % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0));
+    ARG_CHECK(res >= 0 && res <= 2 && (out != nullptr || (out_pairs != nullptr && res == 0)));
+    ARG_CHECK(out_pairs != nullptr || pair_c == 0);
+    ActView x{const_cast<float *>(in), conv->cin, ld_in, relu_in != 0};
+    const _Float16 *ip = (const _Float16 *)in_pairs;
+    return conv_split(*conv, x, batch, h, w, res, out, (_Float16 *)pair_scratch, (hipStream_t)stream, (const _Float16 *)zero_page,
+                      (_Float16 *)out_pairs, pair_c, conv->taps == 9 ? nullptr : ip, conv->taps == 9 ? ip : nullptr);
 }

@@ -32,6 +32,7 @@ SYMBOLS = [
     "mpreid_vit_workspace_bytes", "mpreid_vit_forward", "mpreid_vit_forward_u8", "mpreid_vit_forward_view",
     "mpreid_vit_workspace_bytes_f32", "mpreid_vit_forward_f32", "mpreid_vit_forward_f32_view",
     "mpreid_tta_mean_f32", "mpreid_resize_workspace_bytes", "mpreid_resize_bilinear_u8", "mpreid_conv_f16_nhwc",
+    "mpreid_rn50_conv_split_layer",
     "mpreid_rn50_workspace_bytes", "mpreid_rn50_forward", "mpreid_rn50_workspace_bytes_f32", "mpreid_rn50_forward_f32",
     "mpreid_rn50_workspace_bytes_split", "mpreid_rn50_forward_split", "mpreid_rn50_forward_f32_u8", "mpreid_rn50_forward_split_u8",
     "mpreid_rn50_forward_f32_view", "mpreid_rn50_forward_split_view",
@@ -281,6 +282,8 @@ def load():
                                                  C.POINTER(C.c_float), i32, i32, vp, vp, sz, vp]
     L.mpreid_conv_f16_nhwc.restype = i32
     L.mpreid_conv_f16_nhwc.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp]
+    L.mpreid_rn50_conv_split_layer.restype = i32
+    L.mpreid_rn50_conv_split_layer.argtypes = [C.POINTER(Rn50ConvSplit), vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp]
     L.mpreid_gemm_f16_nt.restype = i32
     L.mpreid_gemm_f16_nt.argtypes = [vp, vp, vp, i64, i64, i64, vp]
     L.mpreid_gemm_f16_nt_ex.restype = i32

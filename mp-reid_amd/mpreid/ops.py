@@ -561,6 +561,80 @@ def conv_f16_nhwc(act: torch.Tensor, wgt: torch.Tensor, bias: torch.Tensor, cout
     return out
 
 
+def pairs_of(w2d, bias, cin: int, taps: int, dev):
+    """folded fp32 matrix [cout][taps * cin] + bias -> (Rn50ConvSplit, [pair matrix, bias]): the zero-padded fp16 pair
+    matrix [npad][hi(kseg) | lo(kseg)] of W * 2^e (include/mpreid.h, mpreid_rn50_conv_split); the two device tensors
+    must outlive the struct, which holds their addresses"""
+    cout, k = w2d.shape
+    kseg, npad = _pad_to(k, 64), _pad_to(cout, 128)
+    wp = np.zeros((npad, kseg), np.float32)
+    wp[:cout, :k] = w2d.astype(np.float32)
+    bp = np.zeros(npad, np.float32)
+    bp[:cout] = bias
+    amax = float(np.abs(wp).max())
+    e = 9 - int(np.floor(np.log2(amax))) if amax > 0 and np.isfinite(amax) else 0
+    wt = torch.from_numpy(wp).to(dev)
+    pair = torch.empty((npad, 2 * kseg), dtype=torch.float16, device=dev)
+    _lib.check(_lib.load().mpreid_split_pack_f32(_ptr(wt), npad, kseg, float(2.0 ** e), _ptr(pair), _lib.stream_ptr()),
+               "mpreid_split_pack_f32")
+    torch.cuda.current_stream().synchronize()   # wt is a temporary of this call
+    bt = torch.from_numpy(bp).to(dev)
+    return _lib.Rn50ConvSplit(_ptr(pair), _ptr(bt), cin, cout, taps, kseg, npad, float(2.0 ** -e)), [pair, bt]
+
+
+def pairs_of_3x3(w, bias, dev):
+    """folded [cout][cin][3][3] + bias -> (Rn50ConvSplit, [slabs, bias]) for the implicit GEMM (csrc/conv_f16.hip, pair
+    form): fp16 slabs [cout_pad128][tap][cin_pad64 / 64][hi(64) | lo(64)] of W * 2^e; kseg = cin_pad64"""
+    cout, cin = w.shape[:2]
+    cp, npad = _pad_to(cin, 64), _pad_to(cout, 128)
+    wp = np.zeros((npad, 9, cp), np.float32)
+    wp[:cout, :, :cin] = w.transpose(0, 2, 3, 1).reshape(cout, 9, cin).astype(np.float32)
+    bp = np.zeros(npad, np.float32)
+    bp[:cout] = bias
+    amax = float(np.abs(wp).max())
+    e = 9 - int(np.floor(np.log2(amax))) if amax > 0 and np.isfinite(amax) else 0
+    wt = torch.from_numpy(wp).to(dev) * float(2.0 ** e)          # exact: a power of two
+    hi = wt.half()
+    lo = (wt - hi.float()).half()
+    hi, lo = hi.view(npad, 9, cp // 64, 1, 64), lo.view(npad, 9, cp // 64, 1, 64)
+    slab = torch.cat([hi, lo], dim=3).reshape(npad, 9 * (cp // 64) * 2 * 64).contiguous()
+    bt = torch.from_numpy(bp).to(dev)
+    return _lib.Rn50ConvSplit(_ptr(slab), _ptr(bt), cin, cout, 9, cp, npad, float(2.0 ** -e)), [slab, bt]
+
+
+def conv_split_layer(conv, B: int, H: int, W: int, x: Optional[torch.Tensor] = None, relu_in: bool = False,
+                     in_pairs: Optional[torch.Tensor] = None, res: int = 0, out: Optional[torch.Tensor] = None,
+                     pair_c: int = 0, pair_out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None):
+    """one convolution of the split RN50 tower (mpreid_rn50_conv_split_layer, include/mpreid.h) -> (out, pair_out).
+    conv: an Rn50ConvSplit (pairs_of / pairs_of_3x3).  x: fp32 [B*H*W, ld_in] NHWC rows (ReLU on read with relu_in), or
+    in_pairs: fp16 [Mp, 2 * kseg], Mp = B*H*W rounded up to 256.  out: fp32 [Mp, npad] (res 1: += ; res 2: max(out, 0) +);
+    pair_c > 0: the ReLU-ed result as fp16 pairs [Mp, 2 * pair_c] -- instead of `out` when res == 0, beside it otherwise.
+    Buffers that are not passed are allocated (uninitialised: see the header for the rows that are written)."""
+    dev = _lib.require_gpu()
+    M = B * H * W
+    Mp = _pad_to(M, 256)
+    if x is not None:
+        assert x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and x.dim() == 2 and x.shape[0] == M
+        if scratch is None:
+            scratch = torch.empty((Mp, 2 * conv.kseg), dtype=torch.float16, device=dev)
+        assert scratch.dtype == torch.float16 and scratch.is_contiguous() and scratch.numel() >= Mp * 2 * conv.kseg
+    if in_pairs is not None:
+        assert in_pairs.dtype == torch.float16 and in_pairs.is_contiguous() and tuple(in_pairs.shape) == (Mp, 2 * conv.kseg)
+    if pair_c and pair_out is None:
+        pair_out = torch.empty((Mp, 2 * pair_c), dtype=torch.float16, device=dev)
+    if pair_out is not None:
+        assert pair_out.dtype == torch.float16 and pair_out.is_contiguous() and tuple(pair_out.shape) == (Mp, 2 * pair_c)
+    if out is None and (res or pair_out is None):
+        assert not res, "a residual form adds onto `out`"
+        out = torch.empty((Mp, conv.npad), dtype=torch.float32, device=dev)
+    if out is not None:
+        assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (Mp, conv.npad)
+    _lib.check(_lib.load().mpreid_rn50_conv_split_layer(
+        C.byref(conv), _ptr(x), 0 if x is None else x.shape[1], int(relu_in), _ptr(in_pairs), B, H, W, int(res), _ptr(out),
+        _ptr(pair_out), int(pair_c), _ptr(scratch), _ptr(_zero_page(dev)), _lib.stream_ptr()), "mpreid_rn50_conv_split_layer")
+    return out, pair_out
+
+
 class Rn50Encoder:
     """Device-resident CLIP RN50 image encoder + the RN50 eval head of build_transformer.
 
@@ -709,49 +783,22 @@ class Rn50Encoder:
             wk = dev32(w.transpose(0, 2, 3, 1).reshape(cout, kh * kw * cin))   # k order (kh, kw, c)
             return _lib.Rn50ConvF32(_ptr(wk), _ptr(dev32(b)), cin, cout, kh * kw)
 
-        def pairs_of(w2d, bias, cin, taps):
-            """folded fp32 matrix [cout][taps * cin] + bias -> Rn50ConvSplit (zero-padded pair matrix of W * 2^e)"""
-            cout, k = w2d.shape
-            kseg, npad = _pad_to(k, 64), _pad_to(cout, 128)
-            wp = np.zeros((npad, kseg), np.float32)
-            wp[:cout, :k] = w2d.astype(np.float32)
-            bp = np.zeros(npad, np.float32)
-            bp[:cout] = bias
-            amax = float(np.abs(wp).max())
-            e = 9 - int(np.floor(np.log2(amax))) if amax > 0 and np.isfinite(amax) else 0
-            wt = torch.from_numpy(wp).to(dev)
-            pair = torch.empty((npad, 2 * kseg), dtype=torch.float16, device=dev)
-            _lib.check(_lib.load().mpreid_split_pack_f32(_ptr(wt), npad, kseg, float(2.0 ** e), _ptr(pair), _lib.stream_ptr()),
-                       "mpreid_split_pack_f32")
-            torch.cuda.current_stream().synchronize()   # wt is a temporary of this call
-            self._keep.append(pair)
-            return _lib.Rn50ConvSplit(_ptr(pair), _ptr(dev32(bp)), cin, cout, taps, kseg, npad, float(2.0 ** -e))
+        def pairs_of_(w2d, bias, cin, taps):
+            conv, keep = pairs_of(w2d, bias, cin, taps, dev)
+            self._keep += keep
+            return conv
 
-        def pairs_of_3x3(w, bias):
-            """folded [cout][cin][3][3] -> Rn50ConvSplit for the implicit GEMM (csrc/conv_f16.hip, pair form): fp16 slabs
-            [cout_pad128][tap][cin_pad64 / 64][hi(64) | lo(64)] of W * 2^e; kseg = cin_pad64"""
-            cout, cin = w.shape[:2]
-            cp, npad = _pad_to(cin, 64), _pad_to(cout, 128)
-            wp = np.zeros((npad, 9, cp), np.float32)
-            wp[:cout, :, :cin] = w.transpose(0, 2, 3, 1).reshape(cout, 9, cin).astype(np.float32)
-            bp = np.zeros(npad, np.float32)
-            bp[:cout] = bias
-            amax = float(np.abs(wp).max())
-            e = 9 - int(np.floor(np.log2(amax))) if amax > 0 and np.isfinite(amax) else 0
-            wt = torch.from_numpy(wp).to(dev) * float(2.0 ** e)          # exact: a power of two
-            hi = wt.half()
-            lo = (wt - hi.float()).half()
-            hi, lo = hi.view(npad, 9, cp // 64, 1, 64), lo.view(npad, 9, cp // 64, 1, 64)
-            slab = torch.cat([hi, lo], dim=3).reshape(npad, 9 * (cp // 64) * 2 * 64).contiguous()
-            self._keep.append(slab)
-            return _lib.Rn50ConvSplit(_ptr(slab), _ptr(dev32(bp)), cin, cout, 9, cp, npad, float(2.0 ** -e))
+        def pairs_of_3x3_(w, bias):
+            conv, keep = pairs_of_3x3(w, bias, dev)
+            self._keep += keep
+            return conv
 
         def conv_s(cname, bname):
             w, b = fold(cname, bname)
             cout, cin, kh, kw = w.shape
             if kh * kw == 9:
-                return pairs_of_3x3(w, b)
-            return pairs_of(w.transpose(0, 2, 3, 1).reshape(cout, kh * kw * cin), b, cin, kh * kw)
+                return pairs_of_3x3_(w, b)
+            return pairs_of_(w.transpose(0, 2, 3, 1).reshape(cout, kh * kw * cin), b, cin, kh * kw)
 
         s1w, s1b = fold("conv1", "bn1")
         blocks = []
@@ -792,7 +839,7 @@ class Rn50Encoder:
             self.c_ws.blocks = C.cast(self.c_sblocks, C.POINTER(_lib.Rn50BlockSplit))
             self.c_ws.stem2, self.c_ws.stem3 = conv_s("conv2", "bn2"), conv_s("conv3", "bn3")
             for n in ("k", "v"):
-                setattr(self.c_ws, n, pairs_of(get(f"attnpool.{n}_proj.weight").astype(np.float64),
+                setattr(self.c_ws, n, pairs_of_(get(f"attnpool.{n}_proj.weight").astype(np.float64),
                                                get(f"attnpool.{n}_proj.bias").astype(np.float64), E, 1))
         cw.stem1_w, cw.stem1_b = _ptr(dev32(s1w)), _ptr(dev32(s1b))
         cw.stem2, cw.stem3 = conv("conv2", "bn2"), conv("conv3", "bn3")

@@ -214,6 +214,61 @@ def test_rn50_split_mode_options_vs_oracle():
     _check(got, orc.rn50_features(sd, cfg, imgs), 2e-5)
 
 
+WIDE = dict(layers=(1, 1, 2, 1), width=16, heads=8, out_dim=64, h_res=6, w_res=4)
+
+
+def _rows_in_batches_of_three(enc, x):
+    """every image of x encoded inside a batch of 3 (384 / 640 / 1152 ... pixels per layer: never a multiple of 256, the
+    tower's unfused path): rows in the order of x"""
+    rows = []
+    for s0 in range(0, len(x), 3):
+        idx = [(s0 + j) % len(x) for j in range(3)]
+        f = enc(x[idx].contiguous()).cpu().numpy()
+        rows += [f[j] for j in range(3) if s0 + j < len(x)]
+    return np.stack(rows)
+
+
+@pytest.mark.parametrize("name,B", [("small", 2), ("small", 8), ("small", 32), ("wide", 2), ("wide", 16)])
+def test_rn50_split_fused_pair_paths_on_padded_channel_counts(name, B):
+    """the producer-written pair operands (conv1 -> conv2, conv2 -> conv3, conv3 -> the next block's conv1) engage only when a
+    layer's pixel count is a multiple of 256, and only the reduced configs have cout < pair_c, cout < npad and cin < kseg:
+    batches at which they engage layer by layer -- 64x32: B = 2 layer1 only, B = 8 through layer3's input, B = 32 every layer;
+    96x64, layers (1, 1, 2, 1): B = 2, B = 16 -- against the fp32 oracle at the tower's 2e-5, and every row bit-identical to the
+    same image encoded inside a batch of 3 (the unfused path: the tower is batch-independent by design)"""
+    from mpreid import ops, synth
+    cfg, hw, seed = (SMALL, (64, 32), 12) if name == "small" else (WIDE, (96, 64), 21)
+    sd = synth.rn50_state_dict(cfg, seed=seed)
+    imgs = synth.synthetic_images(B, hw[0], hw[1], seed=50 + B)
+    enc = ops.Rn50Encoder(cfg, sd, hw, precision="split")
+    x = torch.from_numpy(imgs)
+    got = enc(x).cpu().numpy()
+    print(f"rn50 split, fused paths, {name} B={B}: rel-L2", _check(got, orc.rn50_features(sd, cfg, imgs), 2e-5))
+    assert np.array_equal(got, _rows_in_batches_of_three(enc, x))
+    assert np.array_equal(enc(x).cpu().numpy(), got)   # run to run
+
+
+def test_rn50_split_fused_pair_paths_u8_and_bn_neck():
+    """the uint8 entry and NECK_FEAT 'after' at a batch where the pair operands are producer-written (64x32, B = 8)"""
+    from mpreid import ops, synth
+    sd = synth.rn50_state_dict(SMALL, seed=12)
+    rng = np.random.default_rng(6)
+    bn = {n: (1 + 0.1 * rng.standard_normal(d).astype(np.float32), 0.1 * rng.standard_normal(d).astype(np.float32),
+              0.1 * rng.standard_normal(d).astype(np.float32), (0.5 + rng.random(d)).astype(np.float32))
+          for n, d in (("bottleneck", 512), ("bottleneck_proj", 64))}
+    enc = ops.Rn50Encoder(SMALL, sd, (64, 32), neck_after=True, bn=bn, precision="split")
+    u8 = torch.from_numpy(rng.integers(0, 256, (8, 64, 32, 3), dtype=np.uint8))
+    mean, std = (0.5, 0.4, 0.45), (0.5, 0.25, 0.3)
+    t = u8.permute(0, 3, 1, 2).float().div(255)
+    t = ((t - torch.tensor(mean)[None, :, None, None]) / torch.tensor(std)[None, :, None, None]).contiguous()
+    got = enc.forward_u8(u8, mean, std).cpu().numpy()
+    _check(got, orc.rn50_features(sd, SMALL, t.numpy(), bn=bn, neck_feat="after"), 2e-5)
+    assert np.array_equal(got, enc(t).cpu().numpy())
+    rows = []
+    for s0 in (0, 3, 5):   # batches of 3: the unfused path
+        rows.append(enc.forward_u8(u8[s0:s0 + 3].contiguous(), mean, std).cpu().numpy())
+    assert np.array_equal(got, np.concatenate([rows[0], rows[1][:2], rows[2]]))
+
+
 def test_rn50_image_to_map_parity():
     """image -> mAP for MODEL.NAME RN50 (north_star: within 1e-4 of the reference CPU path): identity-structured synthetic
     images through the fp32-mode tower -> normalise -> distance / re-ranking -> eval against the fp32 oracle pipeline.
