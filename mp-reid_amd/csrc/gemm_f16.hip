@@ -2095,9 +2095,37 @@ __global__ __launch_bounds__(256, 2) void dist_sym_p2_kernel(GemmArgs g, int til
 // ---------------------------------------------------------------------------------------------
 #include <map>
 #include <mutex>
+#include <set>
+#include <string>
 #include <tuple>
 #include <vector>
 namespace {
+// The tile walk gemm_f16_big_kernel takes, for the line below: a COPY of the kernel's three expressions GR / owned / blocked (nb = grid
+// size, walk = GemmArgs::walk, sym = a symmetric problem on an epilogue that knows them; neither mode = the plain strided walk).
+// A copy, not a function the kernel shares: routed through one, every instantiation of the kernel compiled to a different scalar
+// prologue and register assignment.  Whoever changes the kernel's rule changes this one with it; the walk names the tests expect
+// (tests/test_gpu_rn50_split_layers.py) are written down by hand and would disagree with a stale copy's.
+struct BigWalk {
+    int GR;
+    bool owned, blocked;
+};
+BigWalk big_walk_of(int tiles_m, int tiles_n, int nb, int walk, bool sym) {
+    BigWalk w;
+    w.GR = ((walk & 7) == 3 || (walk & 8)) ? 4 : ((walk & 7) == 4 ? 16 : 8);
+    const int ngroups = (tiles_m + w.GR - 1) / w.GR;
+    w.owned = (nb % 8 == 0) && (tiles_m % (8 * w.GR) == 0 || (ngroups >= 24 && !(walk & 16) && !sym));
+    w.blocked = !w.owned && (nb % 64 == 0) && tiles_m * tiles_n >= nb;
+    return w;
+}
+// MPREID_TUNE=verbose=1: launch_one names the kernel (and the persistent kernel's tile walk) it launches on stderr, one line per
+// distinct (epilogue, kernel, walk, tiles_m, tiles_n, grid) of the process -- tests assert on these lines that a shape reached the
+// kernel and the walk it was chosen for.  Never called unless verbose is set.
+void gemm_verbose_line(const char *line) {
+    static std::mutex mu;
+    static std::set<std::string> said;
+    std::lock_guard<std::mutex> lk(mu);
+    if (said.insert(line).second) fprintf(stderr, "[mpreid] %s\n", line);
+}
 struct ProfClass {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
     double flops_total = 0.0;
@@ -2251,6 +2279,8 @@ static int launch_one(const GemmArgs &a_in, hipStream_t stream) {
         if (rc) return rc;
     }
     const int tiles_m = use_big ? a.M / BBM : a.M / GBM, tiles_n = use_big ? a.N / BBN : a.N / GBN;
+    static const int verbose = mpreid_tune("verbose", 0);
+    char vline[160];
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (g_prof_on) {
         HIP_TRY(hipEventCreate(&e0));
@@ -2291,6 +2321,11 @@ static int launch_one(const GemmArgs &a_in, hipStream_t stream) {
             static const int gridt = mpreid_tune("dist_sym_p2_grid", 0);
             static const int strip = std::max(1, mpreid_tune("dist_sym_p2_strip", 8));   // tile rows per strip of the walk
             const dim3 gdim((unsigned)(gridt ? gridt : grid));
+            if (verbose) {
+                snprintf(vline, sizeof vline, "gemm epi %d: two workgroups per CU 256x128%s, %dx%d tiles, grid %u", EPI,
+                         p2_full ? " (two tensors)" : " (symmetric)", a.M / PBM, a.N / PBN, gdim.x);
+                gemm_verbose_line(vline);
+            }
 #ifdef MPREID_ABLATION
             if (const char *sp = getenv("MPREID_GEMM_STAMPS")) a.stamps = reinterpret_cast<unsigned long long *>(strtoull(sp, nullptr, 16));
 #define MPREID_P2_CASE(V)                                                                                      \
@@ -2358,6 +2393,19 @@ static int launch_one(const GemmArgs &a_in, hipStream_t stream) {
             static const int grid_tune = mpreid_tune("gemm_grid", 0);   // experiment: persistent workgroups on fewer CUs (same bits)
             if (grid_tune > 0 && grid_tune < big_cus) big_cus = grid_tune;
             const dim3 grid(total_tiles < (unsigned)big_cus ? total_tiles : (unsigned)big_cus);
+            if (verbose) {   // (the walk: big_walk_of, the copy of the kernel's rule)
+                const bool sym = (EPI == GE_CAND || EPI == GE_EUCLID) && a.sym;
+                const BigWalk bw = big_walk_of(tiles_m, tiles_n, (int)grid.x, a.walk, sym);
+                char wname[64];
+                if (bw.owned)
+                    snprintf(wname, sizeof wname, "%sowned GR=%d %s", tiles_m % (8 * bw.GR) ? "ragged-" : "", bw.GR,
+                             (a.walk & 7) == 1 ? "column-fastest" : "row-fastest");
+                else
+                    snprintf(wname, sizeof wname, "%s", bw.blocked ? (sym ? "blocked compacted" : "blocked") : "strided");
+                snprintf(vline, sizeof vline, "gemm epi %d: persistent 256x256, walk %s, %dx%d tiles, grid %u", EPI, wname, tiles_m,
+                         tiles_n, grid.x);
+                gemm_verbose_line(vline);
+            }
 #ifdef MPREID_ABLATION
             if (dbg == 64 && gemm_epi_is_split(EPI)) {   // operand panels aliased onto two (L2-resident): see set_tile
                 HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16_big_kernel<EPI, 64>),
@@ -2435,6 +2483,11 @@ static int launch_one(const GemmArgs &a_in, hipStream_t stream) {
             }
         }
     } else {
+        if (verbose) {
+            snprintf(vline, sizeof vline, "gemm epi %d: 128x128, %dx%d tiles, grid %u", EPI, tiles_m, tiles_n,
+                     (unsigned)tiles_m * (unsigned)tiles_n);
+            gemm_verbose_line(vline);
+        }
         hipLaunchKernelGGL(gemm_f16_kernel<EPI>, dim3((unsigned)tiles_m * (unsigned)tiles_n), dim3(256), G_LDS_BYTES,
                                stream, a, tiles_m, tiles_n);
     }

@@ -133,6 +133,18 @@ def test_gemm_kernels_agree_bitwise(name, n, k, epi):
                                            C.c_void_p(bias.data_ptr()), x.shape[0], n, k, epi, _lib.stream_ptr()), name)
     torch.cuda.synchronize()
     assert torch.equal(ob[:ms], osm)
+    if epi in (0, 7, 8):
+        # ... in ALL 64 tile rows, not only the first: the 128x128 kernel over slices of 256 rows (no tile walk at all).  (Epilogues
+        # 1 / 2 / 3 have their full comparison in test_gpu_distance.py, test_gemm_kernels_agree_across_variants.)
+        full = init.clone()
+        for s in range(0, mb, ms):
+            blk = init[s:s + ms].clone()
+            _lib.check(L.mpreid_gemm_f16_nt_ex(C.c_void_p(a[s:s + ms].data_ptr()), C.c_void_p(w.data_ptr()), C.c_void_p(blk.data_ptr()),
+                                               C.c_void_p(bias.data_ptr()), ms, n, k, epi, _lib.stream_ptr()), name)
+            full[s:s + ms] = blk
+        torch.cuda.synchronize()
+        bad = (ob != full).any(dim=1).nonzero()
+        assert torch.equal(ob, full), (name, f"{bad.numel()} rows differ, first row {int(bad[0]) if bad.numel() else -1}")
     ref = a[:ms].float() @ w.float().T
     if epi in (1, 3):
         ref = ref + bias
