@@ -243,6 +243,30 @@ int mpreid_eval_rank_positions_splits(const float *dist_dev, int64_t ld, int64_t
                                       const int32_t *g_idx_dev, const int64_t *g_pids_dev, const int64_t *g_camids_dev,
                                       int rcap, int32_t *pos_out_dev, int32_t *cnt_out_dev, mpreid_stream_t stream);
 
+/* ---- ranked gallery lists: the first k entries of np.argsort(distmat, axis=1), utils/metrics.py:39 ----------
+ * For every row i of the resident block dist [nq][ng] (leading dimension ld >= ng; column j is GLOBAL gallery index
+ * col0 + j): the first k items in ascending (distance, global index) order -- -0 equal to +0, ties by the smaller index,
+ * i.e. np.argsort(row, kind="stable")[:k] of a NaN-free row -- as idx [nq][k] int32 (global indices) and val [nq][k] fp32
+ * (the matrix entries' own bits); cnt [nq] = min(k, kept items), entries past it are idx = -1, val = +inf.
+ * Labels (all four pointers, or all NULL; g_pids / g_camids [ng] are aligned with the block's columns, the caller offsets
+ * them): gallery items with the query's pid AND the query's camera are junk and do not enter the list -- the rule of
+ * mpreid_eval_rank_positions_cam.
+ * carry != 0: idx / val / cnt hold on entry a valid ascending list built from OTHER columns (cnt entries are taken, whatever
+ * the values behind them); the result is the first k of the union of that list and this block, so a gallery of any size
+ * is ranked block by block without its nq x ng matrix (mpreid/ops.py:search_topk).  carry == 0: the three are outputs only.
+ * Exact for any number of entries equal to the k-th distance (radix select over the 64-bit (distance, index) keys, then
+ * an LDS sort of at most 2048 keys: csrc/ranklist.hip); the result does not depend on the order in which atomics arrive.
+ * No alignment is assumed of dist_dev, ld or ng (callers pass column slices of wider matrices).
+ * MPREID_ERR_ARG: k < 1, nq < 0, ng < 0, only some of the four label pointers, col0 + ng >= 2^31.  LIMIT: k <=
+ * MPREID_RANK_TOPK_MAX -> MPREID_ERR_UNSUPPORTED above that; one workgroup per query, so a search with a handful of queries
+ * does not fill the chip.  nq == 0, or ng == 0 with carry, is a no-op; ng == 0 without carry writes empty lists. */
+#define MPREID_RANK_TOPK_MAX 1024
+int mpreid_rank_topk(const float *dist_dev, int64_t ld, int nq, int ng, int64_t col0, int k,
+                     const int64_t *q_pids_dev, const int64_t *g_pids_dev,
+                     const int64_t *q_camids_dev, const int64_t *g_camids_dev,   /* all four, or all NULL */
+                     int carry, int32_t *idx_io_dev, float *val_io_dev, int32_t *cnt_io_dev,
+                     mpreid_stream_t stream);
+
 /* ---- row-sharded re-ranking: the same kernels, phase by phase over a row range ------------
  * Rows [r_lo, r_lo+rows) of the N x N problem belong to the calling rank; between the phases the caller
  * all-gathers (RCCL) the rank table, the sparse V rows and the sparse V_qe rows.  mpreid/distributed.py

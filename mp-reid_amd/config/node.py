@@ -93,6 +93,10 @@ def make_defaults():
                  # of the same identity from the same camera are removed (utils/metrics.py; the reference's eval_func
                  # keeps that line commented out, utils/metrics.py:54)
                  "REMOVE_SAME_CAM": False,
+                 # not reference keys: RANK_LIST_K > 0 keeps, for every query, its first K gallery images in ranked order
+                 # (utils/metrics.py:rank_lists; K <= 1024) and test.py writes them to RANK_LIST_FILE
+                 # ('' = <OUTPUT_DIR>/rank_lists.npz; no OUTPUT_DIR either: nothing is written)
+                 "RANK_LIST_K": 0, "RANK_LIST_FILE": "",
                  "TRIALS": 10,   # DATASETS.PROTOCOL 'vehicleid': number of trials (the reference's loop runs 10, test.py:47)
                  # Uni-Prompt evaluation (reference config/defaults.py:331-344)
                  "TTA_ENABLED": False, "TTPT": {"ENABLED": False, "LR": 0.001, "STEPS": 5, "TEMPERATURE": 0.07}},

@@ -101,6 +101,15 @@ __device__ __forceinline__ void split_pairs(const float (&x)[N], HV &hi, HV &lo)
     }
 }
 
+// The ranking key of a matrix entry (evalrank.hip, ranklist.hip): ascending as an unsigned 64-bit integer = ascending
+// (distance, idx) with -0 equal to +0 -- the order a stable argsort of a NaN-free row gives.
+__device__ __forceinline__ unsigned long long ev_key(float f, unsigned idx) {
+    f = f + 0.0f; // -0 -> +0
+    unsigned u = __float_as_uint(f);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)u << 32) | idx;
+}
+
 __device__ __forceinline__ float wave_bfly_add(float s) {
     // fixed butterfly 32,16,8,4,2,1 — the order the oracle mirrors (oracle/mpreid_oracle.c sqnorm_row)
 #pragma unroll

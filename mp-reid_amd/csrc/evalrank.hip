@@ -19,13 +19,6 @@
 constexpr int EV_CAP_MAX = 8192; // max relevant gallery items per query handled on the GPU (64 KB of keys + 32 KB of counters)
 constexpr int EV_HIST_MIN = 2112; // counter words of the smallest instance: room for privatised copies of a short bucket list
 
-__device__ __forceinline__ unsigned long long ev_key(float f, unsigned idx) {
-    f = f + 0.0f; // -0 -> +0
-    unsigned u = __float_as_uint(f);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | idx;
-}
-
 // pos_out [nq][rcap] int32 ascending positions (padded with -1), cnt_out [nq] (= -1 when the query has more
 // than min(rcap, cap) relevant items: the caller falls back to the host for that row)
 // Dynamic LDS: rel [cap] u64 | hist [hw] u32, cap a power of two >= 64, hw = max(cap + 1, EV_HIST_MIN).

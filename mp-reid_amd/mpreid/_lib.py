@@ -17,6 +17,8 @@ GEMM_F16_FAST = 1
 GEMM_F16_SPLIT3 = 2
 RERANK_AUTO, RERANK_DENSE, RERANK_SPARSE, RERANK_SPARSE_SPLIT3, RERANK_WIDE = 0, 1, 2, 3, 4
 ERR_RETRY_DENSE = -5
+ERR_ARG, ERR_UNSUPPORTED = -1, -3
+RANK_TOPK_MAX = 1024   # MPREID_RANK_TOPK_MAX
 
 #: every symbol include/mpreid.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -25,7 +27,7 @@ SYMBOLS = [
     "mpreid_euclidean_distance_f32", "mpreid_cosine_similarity_f32",
     "mpreid_rerank_workspace_bytes", "mpreid_rerank_f32", "mpreid_rerank_debug_copy",
     "mpreid_rerank_workspace_bytes_ex", "mpreid_rerank_f32_ex", "mpreid_rerank_debug_copy_ex", "mpreid_rerank_fits",
-    "mpreid_eval_rank_positions", "mpreid_eval_rank_positions_cam", "mpreid_eval_rank_positions_splits", "mpreid_rr_dist_rows", "mpreid_rr_vcap", "mpreid_rr_krecip", "mpreid_rr_krecip_scratch_bytes",
+    "mpreid_eval_rank_positions", "mpreid_eval_rank_positions_cam", "mpreid_eval_rank_positions_splits", "mpreid_rank_topk", "mpreid_rr_dist_rows", "mpreid_rr_vcap", "mpreid_rr_krecip", "mpreid_rr_krecip_scratch_bytes",
     "mpreid_rr_sparse_workspace_bytes", "mpreid_rr_neighbours_sparse", "mpreid_rr_krecip_sparse", "mpreid_rr_pack_rows", "mpreid_rr_rowptr", "mpreid_rr_ell_to_csr", "mpreid_rr_csr_to_ell", "mpreid_rr_qe_count",
     "mpreid_rr_qe_fill", "mpreid_rr_jaccard", "mpreid_rr_jaccard_hist_bytes",
     "mpreid_rr_csc_chunks", "mpreid_rr_csc_count", "mpreid_rr_csc_fill", "mpreid_rr_jaccard_indexed",
@@ -195,6 +197,8 @@ def load():
     L.mpreid_eval_rank_positions_cam.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]
     L.mpreid_eval_rank_positions_splits.restype = i32
     L.mpreid_eval_rank_positions_splits.argtypes = [vp, i64, i64, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.mpreid_rank_topk.restype = i32
+    L.mpreid_rank_topk.argtypes = [vp, i64, i32, i32, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     L.mpreid_rr_dist_rows.restype = i32
     L.mpreid_rr_dist_rows.argtypes = [vp, vp, i64, i32, i64, i64, vp, i64, vp, vp, i32, vp]
     L.mpreid_rr_vcap.restype = i32

@@ -106,6 +106,120 @@ def cosine_similarity(q, g, mode: int = GEMM_F32_EXACT, out: Optional[torch.Tens
     return _distance("mpreid_cosine_similarity_f32", q, g, mode, out, col_offset)
 
 
+RANK_TOPK_MAX = _lib.RANK_TOPK_MAX
+_SEARCH_BUFFER_BYTES = 256 << 20   # search_topk's default [nq][chunk] distance buffer stays at or below this
+
+
+def _check_topk_k(k) -> int:
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k = {k}: a ranked list has at least one entry")
+    if k > RANK_TOPK_MAX:
+        raise ValueError(f"k = {k} exceeds the limit of {RANK_TOPK_MAX} entries per list (MPREID_RANK_TOPK_MAX)")
+    return k
+
+
+def _check_labels(labels, nq: int, ng: int):
+    """labels = (q_pids, g_pids, q_camids, g_camids), all four or None -> four int64 numpy / torch arrays of [nq] / [ng]"""
+    if labels is None or all(a is None for a in labels):
+        return None
+    if len(labels) != 4 or any(a is None for a in labels):
+        raise ValueError("labels: q_pids, g_pids, q_camids and g_camids go together (all four, or none)")
+    out = []
+    for name, a, n in zip(("q_pids", "g_pids", "q_camids", "g_camids"), labels, (nq, ng, nq, ng)):
+        if not torch.is_tensor(a):
+            a = np.asarray(a)
+        if tuple(a.shape) != (n,):
+            raise ValueError(f"labels: {name} has shape {tuple(a.shape)}, expected ({n},)")
+        out.append(a)
+    return out
+
+
+def _dev_i64(a, device) -> torch.Tensor:
+    if not torch.is_tensor(a):
+        a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64))
+    return a.detach().to(device=device, dtype=torch.int64).contiguous()
+
+
+def rank_topk(dist: torch.Tensor, k: int, col0: int = 0, labels=None, carry=None):
+    """The ranked lists of a resident matrix block (mpreid_rank_topk, include/mpreid.h): dist fp32 [nq, ng] on the device,
+    unit column stride, any row stride (a column slice of a wider matrix is fine); column j is global gallery index
+    col0 + j.  Returns device tensors (idx int32 [nq, k], val fp32 [nq, k], cnt int32 [nq]): per row the first k items of
+    np.argsort(row, kind="stable") with the matrix entries' own bits, padded with -1 / +inf past cnt.
+    labels = (q_pids, g_pids, q_camids, g_camids), g_* aligned with the block's columns: same-identity same-camera gallery
+    items are junk and leave the lists (Market-1501 protocol).  carry = (idx, val, cnt) of an earlier call over OTHER
+    columns: merged with this block IN PLACE and returned."""
+    k = _check_topk_k(k)
+    if not torch.is_tensor(dist) or dist.dim() != 2:
+        raise ValueError("dist: a 2-D fp32 device tensor is expected")
+    nq, ng = int(dist.shape[0]), int(dist.shape[1])
+    col0 = int(col0)
+    if col0 < 0 or col0 + ng >= 2 ** 31:
+        raise ValueError(f"col0 = {col0} with {ng} columns: global gallery indices must stay below 2^31")
+    labels = _check_labels(labels, nq, ng)
+    if carry is not None:
+        if len(carry) != 3:
+            raise ValueError("carry: the (idx, val, cnt) of an earlier call is expected")
+        for name, t, shape, dt in zip(("idx", "val", "cnt"), carry, ((nq, k), (nq, k), (nq,)),
+                                      (torch.int32, torch.float32, torch.int32)):
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt:
+                raise ValueError(f"carry: {name} must be a {dt} tensor of shape {shape}")
+    dev = _lib.require_gpu()
+    L = _lib.load()
+    dist = dist.detach()
+    assert dist.is_cuda and dist.dtype == torch.float32 and (dist.stride(1) == 1 or ng <= 1 or nq == 0), \
+        "dist: fp32 on the device with unit column stride"
+    if carry is not None:
+        idx, val, cnt = carry
+        assert all(t.is_cuda and t.is_contiguous() for t in carry)
+    else:
+        idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        val = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        cnt = torch.empty(nq, dtype=torch.int32, device=dev)
+    lab = [None] * 4 if labels is None else [_dev_i64(a, dev) for a in labels]
+    _lib.check(L.mpreid_rank_topk(_ptr(dist), max(int(dist.stride(0)), ng), nq, ng, col0, k, _ptr(lab[0]), _ptr(lab[1]),
+                                  _ptr(lab[2]), _ptr(lab[3]), int(carry is not None), _ptr(idx), _ptr(val), _ptr(cnt),
+                                  _lib.stream_ptr()), "mpreid_rank_topk")
+    return idx, val, cnt
+
+
+def search_topk(qf, gf, k: int, mode: int = GEMM_F32_EXACT, chunk: Optional[int] = None, q_pids=None, g_pids=None,
+                q_camids=None, g_camids=None):
+    """Ranked lists of euclidean_distance(qf, gf) WITHOUT the nq x ng matrix: the gallery goes through euclidean_distance
+    in blocks of `chunk` rows of gf into one reused [nq, chunk] buffer, and every block is merged into the lists with
+    rank_topk's carry.  chunk: any value >= 1 (smaller than k, not a divisor of ng: fine); default the largest that keeps
+    the buffer at or below 256 MB.  The lists are those of a stable argsort of the concatenated blocks; with
+    GEMM_F32_EXACT an entry does not depend on the blocking, so they are those of the unblocked matrix.  With all four
+    label arrays the Market-1501 filter applies.  Returns device tensors (idx int32 [nq, k], val fp32 [nq, k], cnt int32 [nq])."""
+    k = _check_topk_k(k)
+    shp_q, shp_g = tuple(qf.shape), tuple(gf.shape)
+    if len(shp_q) != 2 or len(shp_g) != 2 or shp_q[1] != shp_g[1]:
+        raise ValueError(f"qf {shp_q} and gf {shp_g}: two matrices with the same number of columns are expected")
+    nq, ng = int(shp_q[0]), int(shp_g[0])
+    if ng >= 2 ** 31:
+        raise ValueError("gallery indices must stay below 2^31")
+    if chunk is None:
+        chunk = max(_SEARCH_BUFFER_BYTES // (4 * max(nq, 1)), 1)
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"chunk = {chunk}: at least one gallery row per block")
+    labels = _check_labels((q_pids, g_pids, q_camids, g_camids), nq, ng)
+    dev = _lib.require_gpu()
+    qf, gf = _dev_f32(qf, dev), _dev_f32(gf, dev)
+    if labels is not None:
+        labels = [_dev_i64(a, dev) for a in labels]
+    chunk = max(min(chunk, ng), 1)
+    buf = torch.empty((nq, chunk), dtype=torch.float32, device=dev)
+    out = None
+    for c0 in range(0, max(ng, 1), chunk):
+        c1 = min(c0 + chunk, ng)
+        if c1 > c0:
+            euclidean_distance(qf, gf[c0:c1], mode=mode, out=buf, col_offset=0)
+        lab = None if labels is None else (labels[0], labels[1][c0:c1], labels[2], labels[3][c0:c1])
+        out = rank_topk(buf[:, :c1 - c0], k, col0=c0, labels=lab, carry=out)
+    return out
+
+
 def re_ranking(q, g, k1: int, k2: int, lambda_value: float, local_distmat=None, only_local: bool = False,
                timing: bool = False, debug: bool = False, algo: int = _lib.RERANK_AUTO, ws_tag: str = "rerank"):
     """utils/reranking.py:29-100 on the GPU.  Returns (device tensor [nq, ng] fp32, stats dict)

@@ -130,7 +130,39 @@ def _configure_evaluator(cfg, evaluator):
         str(getattr(cfg.TEST, "RERANK_ALGO", "exact"))]
     # TEST.REMOVE_SAME_CAM (not a reference key): the Market-1501 protocol of utils/metrics.py, default off like upstream
     evaluator.remove_same_cam = bool(getattr(cfg.TEST, "REMOVE_SAME_CAM", False))
+    # TEST.RANK_LIST_K (not a reference key): R1_mAP_eval also keeps every query's first K gallery items (last_rank_lists)
+    evaluator.rank_list_k = int(getattr(cfg.TEST, "RANK_LIST_K", 0) or 0)
     evaluator.reset()
+
+
+def rank_list_file(cfg):
+    """where do_inference writes the ranked lists: TEST.RANK_LIST_FILE, else <OUTPUT_DIR>/rank_lists.npz, else '' (nowhere)"""
+    name = str(getattr(cfg.TEST, "RANK_LIST_FILE", "") or "")
+    if name:
+        return name
+    return os.path.join(cfg.OUTPUT_DIR, "rank_lists.npz") if cfg.OUTPUT_DIR else ""
+
+
+def write_rank_lists(path, lists, pids, camids, paths, num_query, remove_same_cam=False, reranking=False):
+    """the ranked lists of one evaluation as an .npz: `lists` = R1_mAP_eval.last_rank_lists, `pids` / `camids` / `paths`
+    the evaluated images in update() order (queries first).  Arrays: indices int32 [nq, k] (gallery-relative: row numbers
+    of g_pids / g_paths; -1 padded), distances float32 [nq, k] (+inf padded), counts int32 [nq], q_pids, q_camids, g_pids,
+    g_camids (int64), q_paths, g_paths (str), k, remove_same_cam, reranking.  Returns the file name numpy wrote."""
+    import numpy as np
+    idx, val, cnt = lists
+    nq = int(num_query)
+    pids, camids = np.asarray(pids, dtype=np.int64), np.asarray(camids, dtype=np.int64)
+    paths = np.asarray([str(x) for x in paths], dtype=str)
+    assert idx.shape[0] == nq and pids.shape[0] == camids.shape[0] == paths.shape[0] >= nq
+    if not path.endswith(".npz"):
+        path += ".npz"   # (np.savez would append it silently)
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    np.savez(path, indices=np.asarray(idx, dtype=np.int32), distances=np.asarray(val, dtype=np.float32),
+             counts=np.asarray(cnt, dtype=np.int32), q_pids=pids[:nq], q_camids=camids[:nq], g_pids=pids[nq:],
+             g_camids=camids[nq:], q_paths=paths[:nq], g_paths=paths[nq:], k=np.int64(idx.shape[1]),
+             remove_same_cam=np.bool_(remove_same_cam), reranking=np.bool_(reranking))
+    return path
 
 
 def _encode_into(cfg, model, loader, evaluator):
@@ -171,10 +203,17 @@ def do_inference(cfg, model, val_loader, num_query):
     if world > 1:
         logger.info("rank {} of {}: encoding 1/{} of the queries and its gallery shard".format(rank, world, world))
         val_loader = shard_val_loader(val_loader, num_query)
-    _, do_inference.last_pipeline_stats = _encode_into(cfg, model, val_loader, evaluator)
+    img_paths, do_inference.last_pipeline_stats = _encode_into(cfg, model, val_loader, evaluator)
 
     cmc, mAP, _, _, _, _, _ = evaluator.compute()
     do_inference.last_evaluator = evaluator   # (measurements: bench.py times compute() again on the same features)
+    if evaluator.rank_list_k > 0:
+        out = rank_list_file(cfg)
+        logger.info("TEST.RANK_LIST_K: the first {} gallery images of each of the {} queries -> {}".format(
+            evaluator.rank_list_k, num_query, out or "evaluator.last_rank_lists only (no RANK_LIST_FILE / OUTPUT_DIR)"))
+        if out:
+            write_rank_lists(out, evaluator.last_rank_lists, evaluator.pids, evaluator.camids, img_paths, num_query,
+                             evaluator.remove_same_cam, reranking)
     if rank == 0:
         logger.info("Validation Results ")
         logger.info("mAP: {:.1%}".format(mAP))

@@ -32,6 +32,7 @@ def do_inference(cfg, model, val_loader, num_query):
     evaluator.remove_same_cam = bool(getattr(cfg.TEST, "REMOVE_SAME_CAM", False))   # not a reference key (config/node.py)
     if evaluator.remove_same_cam:
         logger.info(SAME_CAM_NOTE)
+    evaluator.rank_list_k = int(getattr(cfg.TEST, "RANK_LIST_K", 0) or 0)   # not a reference key: evaluator.last_rank_lists
     evaluator.reset()
 
     model.to(device)
@@ -78,6 +79,7 @@ def do_inference_ttpt_option_a(cfg, model, val_loader, num_query):
     evaluator.remove_same_cam = bool(getattr(cfg.TEST, "REMOVE_SAME_CAM", False))   # not a reference key (config/node.py)
     if evaluator.remove_same_cam:
         logger.info(SAME_CAM_NOTE)
+    evaluator.rank_list_k = int(getattr(cfg.TEST, "RANK_LIST_K", 0) or 0)   # not a reference key: evaluator.last_rank_lists
     evaluator.reset()
     model.eval()
 

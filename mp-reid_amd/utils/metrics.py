@@ -29,6 +29,10 @@ reference re-encodes everything per trial; here the pool is encoded once and the
 (q_idx, g_idx) of integer arrays indexing the pool in update() order -- non-empty, in [0, N), g_idx without duplicates
 (ValueError naming the split otherwise; a query that is also in its own gallery list is allowed).  eval_func_splits (host
 definition), eval_func_splits_device (one ranking launch over the resident pool x pool matrix) and R1_mAP_eval_splits.
+
+Ranked lists (not in the reference, which keeps np.argsort's result inside eval_func, :39): rank_lists (host definition:
+the first k entries of a stable argsort of every row, junk removed with remove_same_cam=True), rank_lists_device (the same
+on a resident matrix, mpreid_rank_topk) and ``R1_mAP_eval.rank_list_k`` / ``last_rank_lists`` (TEST.RANK_LIST_K).
 """
 import numpy as np
 import torch
@@ -395,6 +399,50 @@ def eval_func_splits_device(dist_pool, pids, camids, splits, max_rank=50, remove
     return cmcs, maps
 
 
+def _rank_list_args(shape, k, q_pids, g_pids, q_camids, g_camids, remove_same_cam):
+    """validated (k, labels or None) of rank_lists / rank_lists_device: ValueError before any device work"""
+    k = _ops._check_topk_k(k)
+    if len(shape) != 2:
+        raise ValueError(f"distmat has shape {tuple(shape)}: a [nq, ng] matrix is expected")
+    if not remove_same_cam:
+        return k, None
+    if any(a is None for a in (q_pids, g_pids, q_camids, g_camids)):
+        raise ValueError("remove_same_cam=True needs q_pids, g_pids, q_camids and g_camids")
+    return k, [np.asarray(a) for a in _ops._check_labels((q_pids, g_pids, q_camids, g_camids), shape[0], shape[1])]
+
+
+def rank_lists(distmat, k, q_pids=None, g_pids=None, q_camids=None, g_camids=None, remove_same_cam=False):
+    """Which gallery items come first for each query: the first k entries of ``np.argsort(distmat, axis=1)`` (reference
+    utils/metrics.py:39) with ties broken by ascending gallery index (kind="stable"; -0 equals +0).  With
+    remove_same_cam=True the gallery items with the query's pid AND the query's camera are junk and do not enter the list
+    (module docstring).  Returns (indices int64 [nq, k], distances float32 [nq, k], counts int64 [nq]): counts =
+    min(k, kept items), entries past it are -1 / +inf.  1 <= k <= 1024, as on the device.  Host, numpy: the definition."""
+    distmat = np.asarray(distmat)
+    k, labels = _rank_list_args(distmat.shape, k, q_pids, g_pids, q_camids, g_camids, remove_same_cam)
+    nq, ng = distmat.shape
+    idx = np.full((nq, k), -1, np.int64)
+    val = np.full((nq, k), np.inf, np.float32)
+    cnt = np.zeros(nq, np.int64)
+    order = np.argsort(distmat, axis=1, kind="stable")
+    for i in range(nq):
+        o = order[i]
+        if labels is not None:
+            o = o[~((labels[1][o] == labels[0][i]) & (labels[3][o] == labels[2][i]))]
+        o = o[:k]
+        cnt[i] = o.size
+        idx[i, :o.size] = o
+        val[i, :o.size] = distmat[i, o]
+    return idx, val, cnt
+
+
+def rank_lists_device(dist, k, q_pids=None, g_pids=None, q_camids=None, g_camids=None, remove_same_cam=False):
+    """rank_lists on a RESIDENT matrix (device tensor [nq, ng] fp32, left on the device) through ops.rank_topk: one
+    launch, the lists alone come back to the host.  Same return value as rank_lists, byte for byte."""
+    k, labels = _rank_list_args(tuple(dist.shape), k, q_pids, g_pids, q_camids, g_camids, remove_same_cam)
+    idx, val, cnt = _ops.rank_topk(dist, k, 0, labels)
+    return idx.cpu().numpy().astype(np.int64), val.cpu().numpy(), cnt.cpu().numpy().astype(np.int64)
+
+
 def _check_finite(feats, collective=False):
     """An encoder whose fp16 operand halves overflowed (|activation| > 65 504 in the 'split' / 'fp16' precision modes:
     include/mpreid.h, mpreid_vit_forward) hands over NaN / inf feature rows; ranking them would print a plausible-looking
@@ -456,6 +504,8 @@ class R1_mAP_eval():
         self.rerank_algo = _ops.RERANK_AUTO   # _ops.RERANK_SPARSE_SPLIT3: faster at large N, outputs within 1e-6
         self.remove_same_cam = False    # True: Market-1501 protocol (module docstring), TEST.REMOVE_SAME_CAM
         self.last_rerank_stats = None
+        self.rank_list_k = 0            # > 0: compute() also keeps every query's first k gallery items (TEST.RANK_LIST_K)
+        self.last_rank_lists = None     # (indices int64 [nq, k], distances float32 [nq, k], counts int64 [nq]) of rank_lists
 
     def reset(self):
         self.feats = []
@@ -472,6 +522,12 @@ class R1_mAP_eval():
 
     def compute(self):  # called after each epoch
         from mpreid import distributed as D
+        list_k = int(getattr(self, "rank_list_k", 0) or 0)
+        self.last_rank_lists = None
+        if list_k:
+            _ops._check_topk_k(list_k)
+            if D.sharded_active():
+                raise NotImplementedError("ranked lists are single-process")
         if D.sharded_active():
             return self._compute_sharded()
         feats = torch.cat(self.feats, dim=0)
@@ -515,6 +571,8 @@ class R1_mAP_eval():
         else:
             start_copy()
             cmc, mAP = eval_func_device(dist, q_pids, g_pids, q_camids, g_camids, remove_same_cam=same_cam)
+        if list_k:   # the lists of the matrix behind `distmat` (Euclidean or re-ranked), while it is resident
+            self.last_rank_lists = rank_lists_device(dist, list_k, q_pids, g_pids, q_camids, g_camids, same_cam)
         (h_dist,), copied = box["h"], box["ev"]
         feats_copied.synchronize()
         copied.synchronize()
