@@ -48,8 +48,9 @@ extern "C" {
  *   wide_sort_lds (4096), wide_jaccard_rows (24576)   WIDE re-ranking: largest neighbour sort held in LDS (larger ones
  *                           use workspace scratch), gallery rows per Jaccard chunk -- same bits either way
  *   verbose (0)             which attention instantiation runs (template arguments, once per device) and occupancy, on stderr;
- *                           which GEMM kernel a launch takes (128x128 / persistent 256x256 and its tile walk / two workgroups
- *                           per CU), tiles and grid: one line per distinct launch of the process
+ *                           which GEMM kernel a launch takes (128x128 / persistent 256x256 -- "(symmetric)" for the stored
+ *                           distances of one tensor -- and its tile walk / two workgroups per CU), tiles and grid: one line per
+ *                           distinct launch of the process
  * Unknown keys are reported on stderr and ignored.  Switches that change RESULTS exist only in -DMPREID_ABLATION builds. */
 
 typedef void *mpreid_stream_t; /* hipStream_t */

@@ -2402,8 +2402,9 @@ static int launch_one(const GemmArgs &a_in, hipStream_t stream) {
                              (a.walk & 7) == 1 ? "column-fastest" : "row-fastest");
                 else
                     snprintf(wname, sizeof wname, "%s", bw.blocked ? (sym ? "blocked compacted" : "blocked") : "strided");
-                snprintf(vline, sizeof vline, "gemm epi %d: persistent 256x256, walk %s, %dx%d tiles, grid %u", EPI, wname, tiles_m,
-                         tiles_n, grid.x);
+                // (the stored-distance epilogue's symmetric instance -- mirrored stores -- says so: the walk name alone does not)
+                snprintf(vline, sizeof vline, "gemm epi %d: persistent 256x256%s, walk %s, %dx%d tiles, grid %u", EPI,
+                         EPI == GE_EUCLID && a.sym ? " (symmetric)" : "", wname, tiles_m, tiles_n, grid.x);
                 gemm_verbose_line(vline);
             }
 #ifdef MPREID_ABLATION

@@ -54,9 +54,11 @@ def test_euclid_unnormalised_bit_exact(ops):
 
 
 def test_euclid_symmetric_bits(ops):
-    f = torch.from_numpy(_feat(700, 768, seed=9))
+    x = _feat(700, 768, seed=9)
+    f = torch.from_numpy(x)
     d = ops.euclidean_distance(f, f)
     assert torch.equal(d, d.t().contiguous())
+    assert np.array_equal(d.cpu().numpy(), orc.euclidean_distance(x, x))      # symmetric, and the right values
 
 
 def test_distance_vs_reference_golden(ops, golden):
