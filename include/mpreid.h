@@ -268,6 +268,29 @@ int mpreid_rank_topk(const float *dist_dev, int64_t ld, int nq, int ng, int64_t 
                      int carry, int32_t *idx_io_dev, float *val_io_dev, int32_t *cnt_io_dev,
                      mpreid_stream_t stream);
 
+/* ---- query expansion in feature space (AQE on the queries, DBA on the gallery rows; not in the reference) ----------
+ * Every output row is the similarity-weighted mean of the rows of src its list names:
+ *   kk = cnt[i] clamped to [0, k]; entries past it are ignored
+ *   s_j = max(1 - 0.5 * dist[i][j], 0)   fp32, one rounding: the cosine of two unit rows from their squared distance
+ *   w_j = 1 when alpha == 0 (also for s_j == 0); s_j multiplied alpha - 1 times, left to right in fp32, when alpha is an
+ *         integer 1 ... 8; powf(s_j, alpha) otherwise (that case alone is not bit-defined)
+ *   acc = 0; for j = 0 ... kk - 1 in LIST order: acc = fl(acc + fl(w_j * src[idx[i][j]][e])) -- a separate multiply and add
+ *   out[i][e] = fl(acc / float(kk)), a true divide; a row with an empty list becomes zeros
+ * idx / dist / cnt are exactly what mpreid_rank_topk writes ([rows][k], [rows][k], [rows]) for the all-pairs distances of
+ * the L2-NORMALISED rows, while src holds the RAW rows: the normalised copy only chooses the neighbours and the weights
+ * (utils/metrics.py:expand_features is the host definition, mpreid/ops.py:expand_features the driver).
+ * src [n_src][d] fp32 with leading dimension ld_src, out [rows][d] with ld_out; no alignment beyond 4 bytes is assumed
+ * (16-byte loads are used when both pointers and both leading dimensions allow it: the same bits).  One launch, no atomics;
+ * an element's bits do not depend on the launch geometry.  rows == 0 is a no-op.
+ * MPREID_ERR_ARG: k < 1, d < 1, rows < 0, n_src < 0, ld_src < d, ld_out < d, alpha < 0 or NaN, a null pointer, out overlapping
+ * src (other rows still read src).  MPREID_ERR_UNSUPPORTED: k > MPREID_RANK_TOPK_MAX (the list of a row lives in LDS).
+ * LIMIT: the CONTENTS of idx (0 <= idx < n_src in the first cnt entries of a row) are device data and are NOT checked here:
+ * the lists of mpreid_rank_topk over n_src columns satisfy it. */
+int mpreid_qe_aggregate_f32(const float *src_dev, int64_t n_src, int d, int64_t ld_src,
+                            const int32_t *idx_dev, const float *dist_dev, const int32_t *cnt_dev,
+                            int64_t rows, int k, float alpha,
+                            float *out_dev, int64_t ld_out, mpreid_stream_t stream);
+
 /* ---- row-sharded re-ranking: the same kernels, phase by phase over a row range ------------
  * Rows [r_lo, r_lo+rows) of the N x N problem belong to the calling rank; between the phases the caller
  * all-gathers (RCCL) the rank table, the sparse V rows and the sparse V_qe rows.  mpreid/distributed.py

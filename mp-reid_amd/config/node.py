@@ -97,6 +97,10 @@ def make_defaults():
                  # (utils/metrics.py:rank_lists; K <= 1024) and test.py writes them to RANK_LIST_FILE
                  # ('' = <OUTPUT_DIR>/rank_lists.npz; no OUTPUT_DIR either: nothing is written)
                  "RANK_LIST_K": 0, "RANK_LIST_FILE": "",
+                 # not reference keys: QE_K > 0 turns on query expansion in feature space before ranking (AQE on the
+                 # queries, DBA on the gallery rows; utils/metrics.py:expand_features) -- every feature row becomes the mean
+                 # of its first QE_K neighbours (itself included; K <= 1024) weighted by cosine ** QE_ALPHA, QE_TIMES rounds
+                 "QE_K": 0, "QE_ALPHA": 3.0, "QE_TIMES": 1,
                  "TRIALS": 10,   # DATASETS.PROTOCOL 'vehicleid': number of trials (the reference's loop runs 10, test.py:47)
                  # Uni-Prompt evaluation (reference config/defaults.py:331-344)
                  "TTA_ENABLED": False, "TTPT": {"ENABLED": False, "LR": 0.001, "STEPS": 5, "TEMPERATURE": 0.07}},

@@ -27,7 +27,7 @@ SYMBOLS = [
     "mpreid_euclidean_distance_f32", "mpreid_cosine_similarity_f32",
     "mpreid_rerank_workspace_bytes", "mpreid_rerank_f32", "mpreid_rerank_debug_copy",
     "mpreid_rerank_workspace_bytes_ex", "mpreid_rerank_f32_ex", "mpreid_rerank_debug_copy_ex", "mpreid_rerank_fits",
-    "mpreid_eval_rank_positions", "mpreid_eval_rank_positions_cam", "mpreid_eval_rank_positions_splits", "mpreid_rank_topk", "mpreid_rr_dist_rows", "mpreid_rr_vcap", "mpreid_rr_krecip", "mpreid_rr_krecip_scratch_bytes",
+    "mpreid_eval_rank_positions", "mpreid_eval_rank_positions_cam", "mpreid_eval_rank_positions_splits", "mpreid_rank_topk", "mpreid_qe_aggregate_f32", "mpreid_rr_dist_rows", "mpreid_rr_vcap", "mpreid_rr_krecip", "mpreid_rr_krecip_scratch_bytes",
     "mpreid_rr_sparse_workspace_bytes", "mpreid_rr_neighbours_sparse", "mpreid_rr_krecip_sparse", "mpreid_rr_pack_rows", "mpreid_rr_rowptr", "mpreid_rr_ell_to_csr", "mpreid_rr_csr_to_ell", "mpreid_rr_qe_count",
     "mpreid_rr_qe_fill", "mpreid_rr_jaccard", "mpreid_rr_jaccard_hist_bytes",
     "mpreid_rr_csc_chunks", "mpreid_rr_csc_count", "mpreid_rr_csc_fill", "mpreid_rr_jaccard_indexed",
@@ -199,6 +199,8 @@ def load():
     L.mpreid_eval_rank_positions_splits.argtypes = [vp, i64, i64, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
     L.mpreid_rank_topk.restype = i32
     L.mpreid_rank_topk.argtypes = [vp, i64, i32, i32, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.mpreid_qe_aggregate_f32.restype = i32
+    L.mpreid_qe_aggregate_f32.argtypes = [vp, i64, i32, i64, vp, vp, vp, i64, i32, f32, vp, i64, vp]
     L.mpreid_rr_dist_rows.restype = i32
     L.mpreid_rr_dist_rows.argtypes = [vp, vp, i64, i32, i64, i64, vp, i64, vp, vp, i32, vp]
     L.mpreid_rr_vcap.restype = i32

@@ -220,6 +220,93 @@ def search_topk(qf, gf, k: int, mode: int = GEMM_F32_EXACT, chunk: Optional[int]
     return out
 
 
+def _check_qe_alpha(alpha) -> float:
+    alpha = float(alpha)
+    if not np.isfinite(alpha) or alpha < 0:
+        raise ValueError(f"alpha = {alpha}: the weight exponent of query expansion is a finite number >= 0")
+    return alpha
+
+
+def _check_qe_times(times) -> int:
+    if int(times) != times or int(times) < 0:
+        raise ValueError(f"times = {times}: the number of expansion rounds is an integer >= 0")
+    return int(times)
+
+
+def qe_aggregate(src: torch.Tensor, idx: torch.Tensor, dist: torch.Tensor, cnt: torch.Tensor, alpha: float,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The aggregation of query expansion (mpreid_qe_aggregate_f32, include/mpreid.h): src fp32 [n_src, d] on the device,
+    unit column stride, any row stride; (idx int32 [rows, k], dist fp32 [rows, k], cnt int32 [rows]) as rank_topk /
+    search_topk return them.  Row i of the result is the mean of w_j * src[idx[i, j]] over the first cnt[i] entries in list
+    order, w_j = max(1 - dist[i, j] / 2, 0) ** alpha.  The CONTENTS of idx are not checked (they must index src).
+    out: an fp32 device tensor [rows, d] that does not overlap src (default: a new one).  Returns it."""
+    alpha = _check_qe_alpha(alpha)
+    for name, t, dt in (("src", src, torch.float32), ("idx", idx, torch.int32), ("dist", dist, torch.float32),
+                        ("cnt", cnt, torch.int32)):
+        if not torch.is_tensor(t) or t.dtype != dt:
+            raise ValueError(f"{name}: a {dt} tensor is expected")
+    if src.dim() != 2 or idx.dim() != 2 or tuple(dist.shape) != tuple(idx.shape) or tuple(cnt.shape) != (idx.shape[0],):
+        raise ValueError(f"src {tuple(src.shape)}, idx {tuple(idx.shape)}, dist {tuple(dist.shape)}, cnt {tuple(cnt.shape)}: "
+                         "[n_src, d], [rows, k], [rows, k] and [rows] are expected")
+    rows, k = int(idx.shape[0]), _check_topk_k(idx.shape[1])
+    n_src, d = int(src.shape[0]), int(src.shape[1])
+    if d < 1:
+        raise ValueError("src has no columns")
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (rows, d)):
+        raise ValueError(f"out: an fp32 tensor of shape {(rows, d)} is expected")
+    dev = _lib.require_gpu()
+    src = src.detach()
+    if out is None:
+        out = torch.empty((rows, d), dtype=torch.float32, device=dev)
+    assert all(t.is_cuda for t in (src, idx, dist, cnt, out)), "device tensors are expected"
+    assert idx.is_contiguous() and dist.is_contiguous() and cnt.is_contiguous()
+    assert (src.stride(1) == 1 or d == 1 or n_src == 0) and (out.stride(1) == 1 or d == 1 or rows == 0), "unit column stride"
+    if rows:
+        _lib.check(_lib.load().mpreid_qe_aggregate_f32(_ptr(src), n_src, d, max(int(src.stride(0)), d), _ptr(idx), _ptr(dist),
+                                                       _ptr(cnt), rows, k, alpha, _ptr(out), max(int(out.stride(0)), d),
+                                                       _lib.stream_ptr()), "mpreid_qe_aggregate_f32")
+    return out
+
+
+def _expand_rows(feats: torch.Tensor, k: int, alpha: float, times: int, mode: int, chunk: Optional[int]) -> torch.Tensor:
+    """`times` rounds of query expansion over the device stack feats [N, D] (arguments already validated): per round
+    l2_normalize -> search_topk of the normalised rows against themselves -> qe_aggregate over the RAW rows, ping-pong
+    between two buffers (`feats` is only read).  Returns a tensor that is never `feats` itself."""
+    if times == 0 or feats.shape[0] == 0:
+        return feats.clone()
+    cur, bufs = feats, [None, None]
+    for r in range(times):
+        unit = l2_normalize(cur)
+        idx, val, cnt = search_topk(unit, unit, k, mode=mode, chunk=chunk)
+        del unit
+        if bufs[r % 2] is None:
+            bufs[r % 2] = torch.empty_like(feats)
+        cur = qe_aggregate(cur, idx, val, cnt, alpha, out=bufs[r % 2])
+    return cur
+
+
+def expand_features(qf, gf, k: int, alpha: float = 3.0, times: int = 1, mode: int = GEMM_F32_EXACT,
+                    chunk: Optional[int] = None):
+    """Query expansion in feature space over the stack F = qf || gf (AQE on the query rows, DBA on the gallery rows): every
+    row becomes the similarity-weighted mean of its first k neighbours -- utils/metrics.py:expand_features is the host
+    definition of one round.  Per round: F^ = l2_normalize(F); the first min(k, N) neighbours of every row by exact
+    (distance, index) order from search_topk(F^, F^) -- no N x N matrix, for any N search_topk takes; `mode` / `chunk` are
+    search_topk's --; weights max(1 - d / 2, 0) ** alpha; the RAW rows are averaged (qe_aggregate).  `times` rounds repeat
+    that with F <- F' (0: copies).  Returns (qf', gf') as device tensors, not normalised."""
+    k = _check_topk_k(k)
+    alpha = _check_qe_alpha(alpha)
+    times = _check_qe_times(times)
+    shp_q, shp_g = tuple(qf.shape), tuple(gf.shape)
+    if len(shp_q) != 2 or len(shp_g) != 2 or shp_q[1] != shp_g[1] or shp_q[1] < 1:
+        raise ValueError(f"qf {shp_q} and gf {shp_g}: two matrices with the same number (>= 1) of columns are expected")
+    if shp_q[0] + shp_g[0] >= 2 ** 31:
+        raise ValueError("row indices must stay below 2^31")
+    dev = _lib.require_gpu()
+    feats = torch.cat([_dev_f32(qf, dev), _dev_f32(gf, dev)], dim=0)
+    out = _expand_rows(feats, k, alpha, times, mode, chunk)
+    return out[:shp_q[0]], out[shp_q[0]:]
+
+
 def re_ranking(q, g, k1: int, k2: int, lambda_value: float, local_distmat=None, only_local: bool = False,
                timing: bool = False, debug: bool = False, algo: int = _lib.RERANK_AUTO, ws_tag: str = "rerank"):
     """utils/reranking.py:29-100 on the GPU.  Returns (device tensor [nq, ng] fp32, stats dict)

@@ -132,7 +132,21 @@ def _configure_evaluator(cfg, evaluator):
     evaluator.remove_same_cam = bool(getattr(cfg.TEST, "REMOVE_SAME_CAM", False))
     # TEST.RANK_LIST_K (not a reference key): R1_mAP_eval also keeps every query's first K gallery items (last_rank_lists)
     evaluator.rank_list_k = int(getattr(cfg.TEST, "RANK_LIST_K", 0) or 0)
+    configure_query_expansion(cfg, evaluator)
     evaluator.reset()
+
+
+def configure_query_expansion(cfg, evaluator):
+    """TEST.QE_K / QE_ALPHA / QE_TIMES (not reference keys): query expansion in feature space before ranking
+    (utils/metrics.py:expand_features), default off; one log line when it is on"""
+    evaluator.qe_k = int(getattr(cfg.TEST, "QE_K", 0) or 0)
+    evaluator.qe_alpha = float(getattr(cfg.TEST, "QE_ALPHA", 3.0))
+    evaluator.qe_times = int(getattr(cfg.TEST, "QE_TIMES", 1))
+    if evaluator.qe_k > 0:
+        logging.getLogger("transreid.test").info(
+            "TEST.QE_K: query expansion over query + gallery before ranking -- every feature becomes the mean of its first "
+            "{} neighbours weighted by cosine ** {}, {} round(s)".format(evaluator.qe_k, evaluator.qe_alpha,
+                                                                         evaluator.qe_times))
 
 
 def rank_list_file(cfg):

@@ -19,7 +19,7 @@ import time
 import torch
 
 from mpreid import ops as _ops
-from processor.processor import ENCODE_GROUP, SAME_CAM_NOTE, grouped_batches, merge_batches
+from processor.processor import ENCODE_GROUP, SAME_CAM_NOTE, configure_query_expansion, grouped_batches, merge_batches
 from utils.metrics import R1_mAP_eval
 
 
@@ -33,6 +33,7 @@ def do_inference(cfg, model, val_loader, num_query):
     if evaluator.remove_same_cam:
         logger.info(SAME_CAM_NOTE)
     evaluator.rank_list_k = int(getattr(cfg.TEST, "RANK_LIST_K", 0) or 0)   # not a reference key: evaluator.last_rank_lists
+    configure_query_expansion(cfg, evaluator)   # TEST.QE_K / QE_ALPHA / QE_TIMES, not reference keys
     evaluator.reset()
 
     model.to(device)
@@ -80,6 +81,7 @@ def do_inference_ttpt_option_a(cfg, model, val_loader, num_query):
     if evaluator.remove_same_cam:
         logger.info(SAME_CAM_NOTE)
     evaluator.rank_list_k = int(getattr(cfg.TEST, "RANK_LIST_K", 0) or 0)   # not a reference key: evaluator.last_rank_lists
+    configure_query_expansion(cfg, evaluator)   # TEST.QE_K / QE_ALPHA / QE_TIMES, not reference keys
     evaluator.reset()
     model.eval()
 

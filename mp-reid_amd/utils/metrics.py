@@ -33,6 +33,13 @@ definition), eval_func_splits_device (one ranking launch over the resident pool 
 Ranked lists (not in the reference, which keeps np.argsort's result inside eval_func, :39): rank_lists (host definition:
 the first k entries of a stable argsort of every row, junk removed with remove_same_cam=True), rank_lists_device (the same
 on a resident matrix, mpreid_rank_topk) and ``R1_mAP_eval.rank_list_k`` / ``last_rank_lists`` (TEST.RANK_LIST_K).
+
+Query expansion in feature space (not in the reference): every row of the stack query || gallery is replaced by the
+similarity-weighted mean of its first k neighbours before distances are computed -- "average / alpha-weighted query
+expansion" on the query rows, "database-side augmentation" on the gallery rows.  expand_features / qe_aggregate (host
+definition of one round, numpy), expand_features_device (ops.expand_features: no N x N matrix) and ``R1_mAP_eval.qe_k`` /
+``qe_alpha`` / ``qe_times`` (TEST.QE_K / QE_ALPHA / QE_TIMES; also on R1_mAP_eval_splits, where every split expands its own
+query + gallery set and is therefore evaluated split by split).  Single-process.
 """
 import numpy as np
 import torch
@@ -443,6 +450,70 @@ def rank_lists_device(dist, k, q_pids=None, g_pids=None, q_camids=None, g_camids
     return idx.cpu().numpy().astype(np.int64), val.cpu().numpy(), cnt.cpu().numpy().astype(np.int64)
 
 
+def _qe_args(k, alpha, times=1):
+    """validated (k, alpha, times) of query expansion: ValueError before any device work"""
+    return _ops._check_topk_k(k), _ops._check_qe_alpha(alpha), _ops._check_qe_times(times)
+
+
+def qe_aggregate(feats, idx, dist, cnt, alpha=3.0):
+    """The aggregation of query expansion over given lists: row i of the result is the weighted mean of
+    feats[idx[i, j]] over j < min(max(cnt[i], 0), k) IN LIST ORDER, every step rounded to float32 on its own --
+    s = max(1 - 0.5 * dist[i, j], 0); w = 1 for alpha == 0 (also where s == 0), s multiplied alpha - 1 times left to right
+    for an integer alpha 1 ... 8, s ** alpha (np.power, not bit-defined) otherwise; acc = acc + w * row; acc / float32(kk)
+    at the end, zeros for an empty list.  Host, numpy: the definition mpreid_qe_aggregate_f32 is compared with bit for bit."""
+    alpha = float(np.float32(_qe_args(1, alpha)[1]))      # (the ABI takes a float)
+    feats = np.ascontiguousarray(feats, dtype=np.float32)
+    idx, dist, cnt = np.asarray(idx), np.asarray(dist, dtype=np.float32), np.asarray(cnt)
+    if feats.ndim != 2 or idx.ndim != 2 or dist.shape != idx.shape or cnt.shape != idx.shape[:1]:
+        raise ValueError(f"feats {feats.shape}, idx {idx.shape}, dist {dist.shape}, cnt {cnt.shape}: [n, d], [rows, k], "
+                         "[rows, k] and [rows] are expected")
+    rows, k = idx.shape
+    kk = np.clip(cnt.astype(np.int64), 0, k)
+    one, half, zero = np.float32(1), np.float32(0.5), np.float32(0)
+    with np.errstate(invalid="ignore", over="ignore"):      # (entries past cnt may hold anything)
+        s = np.maximum(one - half * dist, zero)
+        if alpha == 0:
+            w = np.ones_like(s)
+        elif alpha <= 8 and alpha == int(alpha):
+            w = s
+            for _ in range(int(alpha) - 1):
+                w = w * s
+        else:
+            w = np.power(s, np.float32(alpha))
+    acc = np.zeros((rows, feats.shape[1]), np.float32)
+    for j in range(int(kk.max()) if rows else 0):
+        live = np.nonzero(j < kk)[0]
+        acc[live] = acc[live] + w[live, j][:, None] * feats[idx[live, j]]
+    some = kk > 0
+    acc[some] = acc[some] / kk[some].astype(np.float32)[:, None]
+    return acc
+
+
+def expand_features(feats, distmat, k, alpha=3.0):
+    """One round of query expansion in feature space (not in the reference): every row of `feats` [N, D] -- the stack
+    query || gallery in update() order, so this is AQE on the query rows and DBA on the gallery rows -- is replaced by the
+    similarity-weighted mean of its first min(k, N) neighbours.  `distmat` [N, N] is euclidean_distance of the L2-NORMALISED
+    rows against themselves (the way rank_lists takes a matrix): the lists are rank_lists(distmat, k) -- ascending
+    (distance, index); the row itself is normally first, with its distance of +-1e-6 used as it is -- and the weights come
+    from the listed distances (qe_aggregate), while the RAW rows are averaged.  Returns float32 [N, D], not normalised.
+    Host, numpy: the definition ops.expand_features is compared with."""
+    k, alpha, _ = _qe_args(k, alpha)
+    feats, distmat = np.asarray(feats), np.asarray(distmat)
+    if feats.ndim != 2 or feats.shape[1] < 1:
+        raise ValueError(f"feats has shape {feats.shape}: an [N, D] matrix with D >= 1 is expected")
+    if distmat.shape != (feats.shape[0], feats.shape[0]):
+        raise ValueError(f"distmat has shape {distmat.shape} for {feats.shape[0]} rows: [N, N] is expected")
+    idx, val, cnt = rank_lists(distmat, k)
+    return qe_aggregate(feats, idx, val, cnt, alpha)
+
+
+def expand_features_device(qf, gf, k, alpha=3.0, times=1, mode=_ops.GEMM_F32_EXACT, chunk=None):
+    """`times` rounds of expand_features on the GPU without the N x N matrix (ops.expand_features: search_topk +
+    mpreid_qe_aggregate_f32); returns (qf', gf') as float32 numpy arrays."""
+    q, g = _ops.expand_features(_as_tensor(qf), _as_tensor(gf), k, alpha, times, mode, chunk)
+    return q.cpu().numpy(), g.cpu().numpy()
+
+
 def _check_finite(feats, collective=False):
     """An encoder whose fp16 operand halves overflowed (|activation| > 65 504 in the 'split' / 'fp16' precision modes:
     include/mpreid.h, mpreid_vit_forward) hands over NaN / inf feature rows; ranking them would print a plausible-looking
@@ -493,6 +564,15 @@ def _to_host_async(tensors):
     return hosts, ev
 
 
+def _qe_setting(ev):
+    """None when the evaluator's query expansion is off (qe_k == 0, or an evaluator made before the attribute existed), else
+    the validated (k, alpha, times): ValueError before any device work"""
+    k = int(getattr(ev, "qe_k", 0) or 0)
+    if k == 0:
+        return None
+    return _qe_args(k, getattr(ev, "qe_alpha", 3.0), getattr(ev, "qe_times", 1))
+
+
 class R1_mAP_eval():
     def __init__(self, num_query, max_rank=50, feat_norm=True, reranking=False):
         super(R1_mAP_eval, self).__init__()
@@ -506,6 +586,9 @@ class R1_mAP_eval():
         self.last_rerank_stats = None
         self.rank_list_k = 0            # > 0: compute() also keeps every query's first k gallery items (TEST.RANK_LIST_K)
         self.last_rank_lists = None     # (indices int64 [nq, k], distances float32 [nq, k], counts int64 [nq]) of rank_lists
+        # qe_k > 0: query expansion (expand_features: AQE + DBA over query || gallery) with k neighbours, weight exponent
+        # qe_alpha, qe_times rounds, before normalisation and ranking (TEST.QE_K / QE_ALPHA / QE_TIMES)
+        self.qe_k, self.qe_alpha, self.qe_times = 0, 3.0, 1
 
     def reset(self):
         self.feats = []
@@ -528,10 +611,16 @@ class R1_mAP_eval():
             _ops._check_topk_k(list_k)
             if D.sharded_active():
                 raise NotImplementedError("ranked lists are single-process")
+        qe = _qe_setting(self)
+        if qe and D.sharded_active():
+            raise NotImplementedError("query expansion is single-process")
         if D.sharded_active():
             return self._compute_sharded()
         feats = torch.cat(self.feats, dim=0)
         _check_finite(feats)
+        if qe:   # the RAW rows are expanded; what follows sees the expanded rows as if the encoder had produced them
+            print('=> Query expansion: k = {}, alpha = {}, {} round(s)'.format(*qe))
+            feats = _ops._expand_rows(feats, qe[0], qe[1], qe[2], self.distance_mode, None)
         if self.feat_norm:
             print("The test feature is normalized")
             feats = _ops.l2_normalize(feats)
@@ -663,7 +752,9 @@ class R1_mAP_eval_splits():
     evaluator computes for the same two feature rows.  With re-ranking the matrix depends on the split (the k-reciprocal
     neighbourhoods are those of the split's own query + gallery set), and a pool whose matrix would exceed a quarter of
     the device's memory has no room for it: both go split by split through the single-split code (gather the features,
-    re_ranking_device / euclidean_distance, eval_func_device).  Single-process only."""
+    re_ranking_device / euclidean_distance, eval_func_device).  Query expansion (qe_k > 0) depends on the split's own set in
+    the same way and takes the split-by-split path too; the returned feats_host stay the pool's unexpanded rows.
+    Single-process only."""
 
     def __init__(self, splits, max_rank=50, feat_norm=True, reranking=False):
         self.splits = splits
@@ -675,6 +766,7 @@ class R1_mAP_eval_splits():
         self.remove_same_cam = False
         self.last_rerank_stats = None
         self.last_dist = None          # the pooled device matrix of the last compute() (None on the split-by-split path)
+        self.qe_k, self.qe_alpha, self.qe_times = 0, 3.0, 1   # query expansion, as in R1_mAP_eval
 
     def reset(self):
         self.feats = []
@@ -693,8 +785,10 @@ class R1_mAP_eval_splits():
         from mpreid import distributed as D
         if D.sharded_active():
             raise NotImplementedError("multi-trial evaluation is single-process")
+        qe = _qe_setting(self)
         feats = torch.cat(self.feats, dim=0)
         _check_finite(feats)
+        raw = feats
         if self.feat_norm:
             print("The test feature is normalized")
             feats = _ops.l2_normalize(feats)
@@ -704,7 +798,7 @@ class R1_mAP_eval_splits():
         splits = _check_splits(self.splits, n)
         same_cam = bool(self.remove_same_cam)
         self.last_dist = None
-        if not self.reranking and _pool_matrix_fits(n):
+        if not qe and not self.reranking and _pool_matrix_fits(n):
             print('=> Computing the pool DistMat with euclidean_distance')
             dist = _ops.euclidean_distance(feats, feats, mode=self.distance_mode)
             cmcs, maps = eval_func_splits_device(dist, pids, camids, splits, self.max_rank, same_cam)
@@ -713,8 +807,15 @@ class R1_mAP_eval_splits():
             dev = feats.device
             cmcs, maps = [], np.zeros(len(splits), np.float64)
             for i, (q, g) in enumerate(splits):
-                qf = feats[torch.from_numpy(q).to(dev)]
-                gf = feats[torch.from_numpy(g).to(dev)]
+                if qe:   # the split's own query || gallery stack is expanded (raw rows), then normalised like the pool
+                    stack = _ops._expand_rows(raw[torch.from_numpy(np.concatenate([q, g])).to(dev)], qe[0], qe[1], qe[2],
+                                              self.distance_mode, None)
+                    if self.feat_norm:
+                        stack = _ops.l2_normalize(stack)
+                    qf, gf = stack[:q.size], stack[q.size:]
+                else:
+                    qf = feats[torch.from_numpy(q).to(dev)]
+                    gf = feats[torch.from_numpy(g).to(dev)]
                 if self.reranking:
                     print('=> Enter reranking')
                     dist, self.last_rerank_stats = re_ranking_device(qf, gf, k1=50, k2=15, lambda_value=0.3,
