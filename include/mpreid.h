@@ -47,6 +47,7 @@ extern "C" {
  *   rerank_overlap (-1 auto)             exact query rows in line (0) / on a side stream (1)
  *   wide_sort_lds (4096), wide_jaccard_rows (24576)   WIDE re-ranking: largest neighbour sort held in LDS (larger ones
  *                           use workspace scratch), gallery rows per Jaccard chunk -- same bits either way
+ *   pair_blocks (2048)      mpreid_pair_bucket_counts: number of workgroups the launcher aims for -- same counts
  *   verbose (0)             which attention instantiation runs (template arguments, once per device) and occupancy, on stderr;
  *                           which GEMM kernel a launch takes (128x128 / persistent 256x256 -- "(symmetric)" for the stored
  *                           distances of one tensor -- and its tile walk / two workgroups per CU), tiles and grid: one line per
@@ -290,6 +291,35 @@ int mpreid_qe_aggregate_f32(const float *src_dev, int64_t n_src, int d, int64_t 
                             const int32_t *idx_dev, const float *dist_dev, const int32_t *cnt_dev,
                             int64_t rows, int k, float alpha,
                             float *out_dev, int64_t ld_out, mpreid_stream_t stream);
+
+/* ---- verification statistics over all query x gallery pairs (not in the reference) ---------------------------------
+ * PAIRS: (i, j) with i < nq, j < ng and dist[i][j] finite (NaN and +-inf entries are no pairs).  With the camera ids given
+ * (both pointers, or both NULL: no filter) the pairs with g_pids[j] == q_pids[i] and g_camids[j] == q_camids[i] are dropped
+ * -- the junk of mpreid_eval_rank_positions_cam.  A kept pair is POSITIVE iff the pids are equal, NEGATIVE otherwise; every
+ * query contributes, with or without a positive.
+ * ORDER: distances compare through the 32-bit key u = bits(d + 0.0f); key = u >= 2^31 ? ~u : u | 2^31 -- the upper half
+ * of the ranking key of the kernels above: ascending distance, -0 equal to +0.
+ * COUNTS: bound_keys [n_bounds] are strictly ascending keys; the bucket of a kept pair is the number of bounds smaller than
+ * its key (0 ... n_bounds), so bucket b holds the pairs with bound[b-1] < key <= bound[b] and the inclusive prefix sums over
+ * the buckets are tp[b] / fp[b] = number of positive / negative pairs with d <= t_b.  counts [2][n_bounds + 1] u64:
+ * positive row, then negative row.  accumulate == 0 zeroes counts first (stream-ordered); accumulate != 0 adds, so column
+ * blocks of a matrix that is never held whole sum exactly.  Integer sums: the result does not depend on the launch
+ * geometry or on the order of the atomics.  ROC curves, TPR at a false-positive budget and the distance histograms are
+ * sums and differences of these counts (utils/metrics.py: pair_counts / tpr_at_fpr; mpreid/ops.py: pair_select).
+ * One pass over the matrix, tiled in both directions (csrc/pairstats.hip); stream-ordered, no host synchronisation.
+ * No alignment is assumed of dist_dev or ld (16-byte loads when both allow it, 4-byte loads otherwise: the same counts).
+ * nq == 0 or ng == 0: zero counts (unless accumulating), no launch.
+ * MPREID_ERR_ARG: n_bounds < 1 or > MPREID_PAIR_BOUNDS_MAX, exactly one camera pointer NULL, ld < ng, nq < 0, ng < 0, a
+ * null bounds / counts pointer.  MPREID_ERR_UNSUPPORTED: more than 2^31 - 1 tiles of the grid.
+ * LIMIT: the CONTENTS of bound_keys (strictly ascending) are device data and are NOT checked here: the caller validates
+ * them before upload (mpreid/ops.py:pair_bucket_counts does). */
+#define MPREID_PAIR_BOUNDS_MAX 4096
+int mpreid_pair_bucket_counts(const float *dist_dev, int64_t ld, int nq, int ng,
+                              const int64_t *q_pids_dev, const int64_t *g_pids_dev,
+                              const int64_t *q_cams_dev, const int64_t *g_cams_dev,   /* both NULL: no filter */
+                              const uint32_t *bound_keys_dev, int n_bounds,            /* strictly ascending keys */
+                              int accumulate, unsigned long long *counts_dev,          /* [2][n_bounds + 1] */
+                              mpreid_stream_t stream);
 
 /* ---- row-sharded re-ranking: the same kernels, phase by phase over a row range ------------
  * Rows [r_lo, r_lo+rows) of the N x N problem belong to the calling rank; between the phases the caller

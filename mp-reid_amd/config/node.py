@@ -101,6 +101,11 @@ def make_defaults():
                  # queries, DBA on the gallery rows; utils/metrics.py:expand_features) -- every feature row becomes the mean
                  # of its first QE_K neighbours (itself included; K <= 1024) weighted by cosine ** QE_ALPHA, QE_TIMES rounds
                  "QE_K": 0, "QE_ALPHA": 3.0, "QE_TIMES": 1,
+                 # not reference keys: EXTRA_METRICS True also reports mINP (how deep a query's hardest true match sits) and,
+                 # over ALL query x gallery pairs, TPR at the false-positive rates ROC_FPRS; PAIR_HIST_BINS > 0 (<= 4095) adds
+                 # the positive- / negative-pair distance histograms over PAIR_HIST_RANGE, written to
+                 # <OUTPUT_DIR>/pair_hist.npz (utils/metrics.py: eval_metrics, tpr_at_fpr, pair_counts)
+                 "EXTRA_METRICS": False, "ROC_FPRS": [1e-4, 1e-3, 1e-2], "PAIR_HIST_BINS": 0, "PAIR_HIST_RANGE": [0.0, 4.0],
                  "TRIALS": 10,   # DATASETS.PROTOCOL 'vehicleid': number of trials (the reference's loop runs 10, test.py:47)
                  # Uni-Prompt evaluation (reference config/defaults.py:331-344)
                  "TTA_ENABLED": False, "TTPT": {"ENABLED": False, "LR": 0.001, "STEPS": 5, "TEMPERATURE": 0.07}},

@@ -19,6 +19,7 @@ RERANK_AUTO, RERANK_DENSE, RERANK_SPARSE, RERANK_SPARSE_SPLIT3, RERANK_WIDE = 0,
 ERR_RETRY_DENSE = -5
 ERR_ARG, ERR_UNSUPPORTED = -1, -3
 RANK_TOPK_MAX = 1024   # MPREID_RANK_TOPK_MAX
+PAIR_BOUNDS_MAX = 4096   # MPREID_PAIR_BOUNDS_MAX
 
 #: every symbol include/mpreid.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -27,7 +28,7 @@ SYMBOLS = [
     "mpreid_euclidean_distance_f32", "mpreid_cosine_similarity_f32",
     "mpreid_rerank_workspace_bytes", "mpreid_rerank_f32", "mpreid_rerank_debug_copy",
     "mpreid_rerank_workspace_bytes_ex", "mpreid_rerank_f32_ex", "mpreid_rerank_debug_copy_ex", "mpreid_rerank_fits",
-    "mpreid_eval_rank_positions", "mpreid_eval_rank_positions_cam", "mpreid_eval_rank_positions_splits", "mpreid_rank_topk", "mpreid_qe_aggregate_f32", "mpreid_rr_dist_rows", "mpreid_rr_vcap", "mpreid_rr_krecip", "mpreid_rr_krecip_scratch_bytes",
+    "mpreid_eval_rank_positions", "mpreid_eval_rank_positions_cam", "mpreid_eval_rank_positions_splits", "mpreid_rank_topk", "mpreid_qe_aggregate_f32", "mpreid_pair_bucket_counts", "mpreid_rr_dist_rows", "mpreid_rr_vcap", "mpreid_rr_krecip", "mpreid_rr_krecip_scratch_bytes",
     "mpreid_rr_sparse_workspace_bytes", "mpreid_rr_neighbours_sparse", "mpreid_rr_krecip_sparse", "mpreid_rr_pack_rows", "mpreid_rr_rowptr", "mpreid_rr_ell_to_csr", "mpreid_rr_csr_to_ell", "mpreid_rr_qe_count",
     "mpreid_rr_qe_fill", "mpreid_rr_jaccard", "mpreid_rr_jaccard_hist_bytes",
     "mpreid_rr_csc_chunks", "mpreid_rr_csc_count", "mpreid_rr_csc_fill", "mpreid_rr_jaccard_indexed",
@@ -201,6 +202,8 @@ def load():
     L.mpreid_rank_topk.argtypes = [vp, i64, i32, i32, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     L.mpreid_qe_aggregate_f32.restype = i32
     L.mpreid_qe_aggregate_f32.argtypes = [vp, i64, i32, i64, vp, vp, vp, i64, i32, f32, vp, i64, vp]
+    L.mpreid_pair_bucket_counts.restype = i32
+    L.mpreid_pair_bucket_counts.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp]
     L.mpreid_rr_dist_rows.restype = i32
     L.mpreid_rr_dist_rows.argtypes = [vp, vp, i64, i32, i64, i64, vp, i64, vp, vp, i32, vp]
     L.mpreid_rr_vcap.restype = i32

@@ -307,6 +307,170 @@ def expand_features(qf, gf, k: int, alpha: float = 3.0, times: int = 1, mode: in
     return out[:shp_q[0]], out[shp_q[0]:]
 
 
+PAIR_BOUNDS_MAX = _lib.PAIR_BOUNDS_MAX
+PAIR_SELECT_MAX = 16   # budgets per pair_select call
+
+
+def dist_keys(d) -> np.ndarray:
+    """The 32-bit ranking key of float32 distances (include/mpreid.h, verification statistics): ascending as unsigned
+    integers = ascending distance, -0 equal to +0.  numpy in, uint32 out, same shape."""
+    d = np.asarray(d, dtype=np.float32)
+    u = np.ascontiguousarray(np.atleast_1d(d) + np.float32(0)).view(np.uint32)      # -0 + 0 = +0
+    top = np.uint32(0x80000000)
+    return np.where(u & top, ~u, u | top).astype(np.uint32).reshape(d.shape)
+
+
+def keys_to_dist(k) -> np.ndarray:
+    """the inverse of dist_keys (a zero comes back as +0)"""
+    k = np.asarray(k, dtype=np.uint32)
+    top = np.uint32(0x80000000)
+    kk = np.atleast_1d(k)
+    u = np.ascontiguousarray(np.where(kk & top, kk ^ top, ~kk).astype(np.uint32))
+    return u.view(np.float32).reshape(k.shape)
+
+
+def _check_bound_keys(bound_keys) -> np.ndarray:
+    b = np.asarray(bound_keys)
+    if b.ndim != 1 or b.dtype.kind not in "iu":
+        raise ValueError("bound_keys: a 1-D array of uint32 keys (dist_keys of the thresholds) is expected")
+    if b.size < 1 or b.size > PAIR_BOUNDS_MAX:
+        raise ValueError(f"bound_keys: {b.size} bounds; 1 ... {PAIR_BOUNDS_MAX} are supported (MPREID_PAIR_BOUNDS_MAX)")
+    if int(b.min()) < 0 or int(b.max()) > 0xFFFFFFFF:
+        raise ValueError("bound_keys: keys are 32-bit unsigned integers")
+    b = b.astype(np.uint32)
+    if b.size > 1 and not bool(np.all(b[1:] > b[:-1])):
+        raise ValueError("bound_keys must be strictly ascending")
+    return np.ascontiguousarray(b)
+
+
+def _pair_labels(nq, ng, q_pids, g_pids, q_camids, g_camids, dev):
+    """device int64 labels of the pair statistics: (qp, gp, qc, gc), the camera ids both given or both None"""
+    if (q_camids is None) != (g_camids is None):
+        raise ValueError("q_camids and g_camids go together (both, or neither)")
+    out = []
+    for name, a, n in (("q_pids", q_pids, nq), ("g_pids", g_pids, ng), ("q_camids", q_camids, nq), ("g_camids", g_camids, ng)):
+        if a is None:
+            out.append(None)
+            continue
+        if tuple(a.shape if torch.is_tensor(a) else np.shape(a)) != (n,):
+            raise ValueError(f"{name}: expected shape ({n},)")
+        out.append(_dev_i64(a, dev))
+    return out
+
+
+def pair_bucket_counts(dist: torch.Tensor, q_pids, g_pids, q_camids=None, g_camids=None, bound_keys=None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """How many positive / negative pairs of a resident matrix fall between consecutive bounds (mpreid_pair_bucket_counts,
+    include/mpreid.h): dist fp32 [nq, ng] on the device, unit column stride, any row stride and alignment; bound_keys =
+    dist_keys(thresholds), strictly ascending, at most 4096.  Returns an int64 device tensor [2, B + 1] (positive row,
+    negative row): bucket b counts the kept pairs with bound[b-1] < key <= bound[b].  With both camera id arrays the
+    same-identity same-camera pairs are dropped.  out: a tensor of an earlier call with the same bounds -- the counts are
+    ADDED to it (column blocks of a matrix that is never held whole).  No host synchronisation."""
+    if bound_keys is None:
+        raise ValueError("bound_keys is required")
+    bk = _check_bound_keys(bound_keys)
+    if not torch.is_tensor(dist) or dist.dim() != 2:
+        raise ValueError("dist: a 2-D fp32 device tensor is expected")
+    nq, ng = int(dist.shape[0]), int(dist.shape[1])
+    dev = _lib.require_gpu()
+    dist = dist.detach()
+    assert dist.is_cuda and dist.dtype == torch.float32 and (dist.stride(1) == 1 or ng <= 1 or nq == 0), \
+        "dist: fp32 on the device with unit column stride"
+    lab = _pair_labels(nq, ng, q_pids, g_pids, q_camids, g_camids, dev)
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.int64 or tuple(out.shape) != (2, bk.size + 1) or \
+                not out.is_cuda or not out.is_contiguous():
+            raise ValueError(f"out: a contiguous int64 device tensor of shape {(2, bk.size + 1)} is expected")
+    counts = out if out is not None else torch.empty((2, bk.size + 1), dtype=torch.int64, device=dev)
+    bounds = torch.from_numpy(bk.view(np.int32)).to(dev)
+    _lib.check(_lib.load().mpreid_pair_bucket_counts(_ptr(dist), max(int(dist.stride(0)), ng), nq, ng, _ptr(lab[0]),
+                                                     _ptr(lab[1]), _ptr(lab[2]), _ptr(lab[3]), _ptr(bounds), int(bk.size),
+                                                     int(out is not None), _ptr(counts), _lib.stream_ptr()),
+               "mpreid_pair_bucket_counts")
+    return counts
+
+
+def _check_budgets(budgets) -> np.ndarray:
+    b = np.asarray(budgets)
+    if b.ndim != 1 or b.size < 1 or b.size > PAIR_SELECT_MAX or b.dtype.kind not in "iu":
+        raise ValueError(f"budgets: 1 ... {PAIR_SELECT_MAX} integers are expected")
+    if int(b.min()) < 0:
+        raise ValueError("budgets: a false-positive budget is >= 0")
+    return b.astype(np.int64)
+
+
+def pair_select(dist: torch.Tensor, q_pids, g_pids, q_camids=None, g_camids=None, budgets=None, fprs=None):
+    """The exact operating points "at most m false positives" of a resident matrix (definition: include/mpreid.h and
+    utils/metrics.py:tpr_at_fpr): for every integer budget m, tau = the (m + 1)-th smallest negative distance, tp / fp =
+    the positive / negative pairs with d < tau; m >= Nn accepts everything (tau = +inf).
+    Radix refinement over the 32-bit key, digits of 12 | 12 | 8 bits, through pair_bucket_counts: one pass counts the
+    first digit of every pair; per DISTINCT selected first digit one pass counts the second digit inside it, per distinct
+    (first, second) prefix one pass counts the third -- 1 + n1 + n2 <= 1 + 2 * len(budgets) passes over the matrix, 3 when
+    all budgets share their prefixes.  The small count arrays come back to the host between the rounds (this loop is
+    Python; the ABI entry stays free of synchronisation); the positive counts below the selected bucket are summed on the
+    way, so tp needs no pass of its own.
+    budgets: up to 16 integers m >= 0; or fprs: up to 16 rates f in [0, 1], m = int(np.floor(np.float64(f) * Nn)) once the
+    first pass has counted Nn.
+    Returns a dict of numpy arrays / ints: budgets int64 [n], tau float32 [n], tp int64 [n], fp int64 [n], P, Nn."""
+    if (budgets is None) == (fprs is None):
+        raise ValueError("give budgets or fprs (one of them)")
+    if budgets is not None:
+        budgets = _check_budgets(budgets)
+    else:
+        fprs = np.atleast_1d(np.asarray(fprs, dtype=np.float64))
+        if fprs.ndim != 1 or fprs.size < 1 or fprs.size > PAIR_SELECT_MAX or not bool(np.all((fprs >= 0) & (fprs <= 1))):
+            raise ValueError(f"fprs: 1 ... {PAIR_SELECT_MAX} rates in [0, 1] are expected")
+    args = (dist, q_pids, g_pids, q_camids, g_camids)
+    full = np.uint64(0xFFFFFFFF)
+
+    def digit_counts(prefix, shift, bits, known):
+        """counts [2][2^bits] of the digit `bits` wide at `shift` among the pairs whose key has `prefix` above it; `known`
+        [2] = the pairs under the prefix (None for the first digit): the last digit's count is what is left of it"""
+        n = 1 << bits
+        top = (np.arange(n - 1, dtype=np.uint64) << np.uint64(shift)) | ((np.uint64(1) << np.uint64(shift)) - np.uint64(1))
+        keys = (np.uint64(prefix) | top) & full
+        lead = prefix > 0
+        if lead:                                    # bucket 0: everything below the prefix
+            keys = np.concatenate([[np.uint64(prefix - 1)], keys])
+        c = pair_bucket_counts(*args, bound_keys=keys.astype(np.uint32)).cpu().numpy()
+        c = c[:, 1:] if lead else c                 # [2][n]: digits 0 ... n-2, then digit n-1 together with what lies above
+        if known is not None:
+            c = c.copy()
+            c[:, n - 1] = known - c[:, :n - 1].sum(axis=1)
+        return c
+
+    c1 = digit_counts(0, 20, 12, None)
+    P, Nn = int(c1[0].sum()), int(c1[1].sum())
+    if budgets is None:
+        budgets = np.array([int(np.floor(np.float64(f) * Nn)) for f in fprs], np.int64)
+    n = budgets.size
+    tau = np.full(n, np.inf, np.float32)
+    tp = np.full(n, P, np.int64)
+    fp = np.full(n, Nn, np.int64)
+    cache = {}
+    for i, m in enumerate(budgets.tolist()):
+        if m >= Nn:
+            continue
+        prefix, rem, tpa, fpa, c, known = 0, m, 0, 0, c1, None
+        for shift, bits in ((20, 12), (8, 12), (0, 8)):
+            if c is None:
+                if (prefix, shift) not in cache:
+                    cache[(prefix, shift)] = digit_counts(prefix, shift, bits, known)
+                c = cache[(prefix, shift)]
+            cum = np.cumsum(c[1])
+            d = int(np.searchsorted(cum, rem, side="right"))      # first digit with more than rem negatives up to it
+            below = int(cum[d - 1]) if d else 0
+            tpa += int(c[0][:d].sum())
+            fpa += below
+            rem -= below
+            known = c[:, d].copy()
+            prefix |= d << shift
+            c = None
+        tau[i] = keys_to_dist(np.uint32(prefix))
+        tp[i], fp[i] = tpa, fpa
+    return {"budgets": budgets, "tau": tau, "tp": tp, "fp": fp, "P": P, "Nn": Nn}
+
+
 def re_ranking(q, g, k1: int, k2: int, lambda_value: float, local_distmat=None, only_local: bool = False,
                timing: bool = False, debug: bool = False, algo: int = _lib.RERANK_AUTO, ws_tag: str = "rerank"):
     """utils/reranking.py:29-100 on the GPU.  Returns (device tensor [nq, ng] fp32, stats dict)

@@ -133,7 +133,45 @@ def _configure_evaluator(cfg, evaluator):
     # TEST.RANK_LIST_K (not a reference key): R1_mAP_eval also keeps every query's first K gallery items (last_rank_lists)
     evaluator.rank_list_k = int(getattr(cfg.TEST, "RANK_LIST_K", 0) or 0)
     configure_query_expansion(cfg, evaluator)
+    configure_extra_metrics(cfg, evaluator)
     evaluator.reset()
+
+
+def configure_extra_metrics(cfg, evaluator):
+    """TEST.EXTRA_METRICS / ROC_FPRS / PAIR_HIST_BINS / PAIR_HIST_RANGE (not reference keys): mINP and the pair statistics
+    of utils/metrics.py, default off (R1_mAP_eval_splits takes the switch alone: per-split mINP)"""
+    evaluator.extra_metrics = bool(getattr(cfg.TEST, "EXTRA_METRICS", False))
+    if hasattr(evaluator, "roc_fprs"):
+        evaluator.roc_fprs = tuple(float(f) for f in getattr(cfg.TEST, "ROC_FPRS", (1e-4, 1e-3, 1e-2)))
+        evaluator.pair_hist_bins = int(getattr(cfg.TEST, "PAIR_HIST_BINS", 0) or 0)
+        evaluator.pair_hist_range = tuple(float(x) for x in getattr(cfg.TEST, "PAIR_HIST_RANGE", (0.0, 4.0)))
+
+
+def write_pair_hist(path, metrics):
+    """the pair-distance histograms of one evaluation (R1_mAP_eval.last_metrics) as an .npz: edges float32 [bins + 1],
+    pos / neg int64 [bins + 2] (underflow, the bins (e_{b-1}, e_b], overflow), P, Nn.  Returns the file name."""
+    import numpy as np
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    t = metrics["tpr_at_fpr"]
+    np.savez(path, edges=metrics["pair_hist_edges"], pos=metrics["pair_hist_pos"], neg=metrics["pair_hist_neg"],
+             P=np.int64(t["P"]), Nn=np.int64(t["Nn"]))
+    return path
+
+
+def report_extra_metrics(cfg, logger, evaluator):
+    """the lines after "mAP:" when TEST.EXTRA_METRICS is on -- mINP and one TPR@FPR line per rate -- and, with OUTPUT_DIR set
+    and PAIR_HIST_BINS > 0, <OUTPUT_DIR>/pair_hist.npz"""
+    m = getattr(evaluator, "last_metrics", None)
+    if not m:
+        return
+    logger.info("mINP: {:.1%}".format(m["mINP"]))
+    t = m["tpr_at_fpr"]
+    for f, tpr in zip(t["fprs"], t["tpr"]):
+        logger.info("TPR@FPR={:.0e}: {:.1%}".format(f, tpr))
+    if "pair_hist_edges" in m and cfg.OUTPUT_DIR:
+        logger.info("TEST.PAIR_HIST_BINS: pair-distance histograms -> {}".format(
+            write_pair_hist(os.path.join(cfg.OUTPUT_DIR, "pair_hist.npz"), m)))
 
 
 def configure_query_expansion(cfg, evaluator):
@@ -231,6 +269,7 @@ def do_inference(cfg, model, val_loader, num_query):
     if rank == 0:
         logger.info("Validation Results ")
         logger.info("mAP: {:.1%}".format(mAP))
+        report_extra_metrics(cfg, logger, evaluator)
         for r in [1, 5, 10]:
             logger.info("CMC curve, Rank-{:<3}:{:.1%}".format(r, cmc[r - 1]))
     return cmc[0], cmc[4]
@@ -262,6 +301,8 @@ def do_inference_trials(cfg, model, pool_loader, splits):
     for trial in range(len(cmcs)):
         logger.info("rank_1:{:.1%}, rank_5 {:.1%}, mAP {:.1%} : trial : {}".format(rank1[trial], rank5[trial], mAPs[trial],
                                                                                   trial))
+        if evaluator.last_metrics:
+            logger.info("mINP: {:.1%} : trial : {}".format(evaluator.last_metrics["mINP"][trial], trial))
     n = float(len(cmcs))
     logger.info("sum_rank_1:{:.1%}, sum_rank_5 {:.1%}, sum_mAP {:.1%}".format(rank1.sum() / n, rank5.sum() / n,
                                                                               mAPs.sum() / n))

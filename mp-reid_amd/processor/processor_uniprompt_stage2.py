@@ -19,7 +19,8 @@ import time
 import torch
 
 from mpreid import ops as _ops
-from processor.processor import ENCODE_GROUP, SAME_CAM_NOTE, configure_query_expansion, grouped_batches, merge_batches
+from processor.processor import (ENCODE_GROUP, SAME_CAM_NOTE, configure_extra_metrics, configure_query_expansion,
+                                 grouped_batches, merge_batches, report_extra_metrics)
 from utils.metrics import R1_mAP_eval
 
 
@@ -34,6 +35,7 @@ def do_inference(cfg, model, val_loader, num_query):
         logger.info(SAME_CAM_NOTE)
     evaluator.rank_list_k = int(getattr(cfg.TEST, "RANK_LIST_K", 0) or 0)   # not a reference key: evaluator.last_rank_lists
     configure_query_expansion(cfg, evaluator)   # TEST.QE_K / QE_ALPHA / QE_TIMES, not reference keys
+    configure_extra_metrics(cfg, evaluator)     # TEST.EXTRA_METRICS / ROC_FPRS / PAIR_HIST_BINS / PAIR_HIST_RANGE, likewise
     evaluator.reset()
 
     model.to(device)
@@ -54,6 +56,7 @@ def do_inference(cfg, model, val_loader, num_query):
     cmc, mAP, distmat, pids, camids, qf, gf = evaluator.compute()
     logger.info("Validation Results ")
     logger.info("mAP: {:.1%}".format(mAP))
+    report_extra_metrics(cfg, logger, evaluator)
     for r in [1, 5, 10]:
         logger.info("CMC curve, Rank-{:<3}:{:.1%}".format(r, cmc[r - 1]))
     return cmc[0], cmc[4]
@@ -82,6 +85,7 @@ def do_inference_ttpt_option_a(cfg, model, val_loader, num_query):
         logger.info(SAME_CAM_NOTE)
     evaluator.rank_list_k = int(getattr(cfg.TEST, "RANK_LIST_K", 0) or 0)   # not a reference key: evaluator.last_rank_lists
     configure_query_expansion(cfg, evaluator)   # TEST.QE_K / QE_ALPHA / QE_TIMES, not reference keys
+    configure_extra_metrics(cfg, evaluator)     # TEST.EXTRA_METRICS / ROC_FPRS / PAIR_HIST_BINS / PAIR_HIST_RANGE, likewise
     evaluator.reset()
     model.eval()
 
@@ -132,15 +136,18 @@ def do_inference_ttpt_option_a(cfg, model, val_loader, num_query):
     logger.info("Feature extraction finished in %.2f seconds." % (time.time() - start_time))
 
     cmc, mAP = evaluator.compute()[:2]
-    return _report_option_a(logger, cmc, mAP, limit=getattr(evaluator, "max_rank", 50))
+    return _report_option_a(logger, cmc, mAP, limit=getattr(evaluator, "max_rank", 50),
+                            extra=lambda: report_extra_metrics(cfg, logger, evaluator))
 
 
-def _report_option_a(logger, cmc, mAP, limit=50):
+def _report_option_a(logger, cmc, mAP, limit=50, extra=None):
     """the result lines of the TTA evaluation (same text as the reference's, processor_uniprompt_stage2.py:676-692: a rank
     that the curve does not reach is reported as such instead of indexed) and its (Rank-1, Rank-5) return value"""
     have = min(len(cmc), limit)
     logger.info("Validation Results (TTPT Option A - Image Features)")
     logger.info("mAP: {:.1%}".format(mAP))
+    if extra is not None:   # the TEST.EXTRA_METRICS lines (mINP, TPR@FPR), when on
+        extra()
     for r in (1, 5, 10):
         logger.info("CMC curve, Rank-{:<3}:{:.1%}".format(r, cmc[r - 1]) if r <= have else
                     f"Rank-{r} exceeds max_rank ({limit}) or CMC length ({len(cmc)}) ")

@@ -40,6 +40,21 @@ expansion" on the query rows, "database-side augmentation" on the gallery rows. 
 definition of one round, numpy), expand_features_device (ops.expand_features: no N x N matrix) and ``R1_mAP_eval.qe_k`` /
 ``qe_alpha`` / ``qe_times`` (TEST.QE_K / QE_ALPHA / QE_TIMES; also on R1_mAP_eval_splits, where every split expands its own
 query + gallery set and is therefore evaluated split by split).  Single-process.
+
+Extra metrics (not in the reference): mINP and verification statistics over ALL query x gallery pairs.
+  * mINP: for a valid query with R relevant items, the last of them at 0-based position p_last of the kept ranking,
+    INP = R / (p_last + 1); mINP = np.mean over the valid queries in query order.  eval_metrics (host definition) /
+    eval_metrics_device return it with the per-query AP, INP, first-hit position and validity mask.
+  * Pairs: (i, j) with distmat[i, j] finite; with remove_same_cam the same-identity same-camera pairs are dropped; a kept
+    pair is positive iff the pids are equal; P / Nn = number of kept positive / negative pairs.  Distances compare through
+    the 32-bit key of mpreid.ops.dist_keys (ascending distance, -0 equal to +0).  pair_counts: tp[b] / fp[b] = positive /
+    negative pairs with d <= t_b for ascending thresholds -- the ROC curve is (fp / Nn, tp / P), a histogram the difference
+    of consecutive counts.  tpr_at_fpr: for an integer budget m, tau = the (m + 1)-th smallest negative distance, the
+    operating point is "accept d < tau" (the most permissive threshold with at most m false positives; m >= Nn accepts
+    everything, tau = +inf); a rate f means m = int(np.floor(np.float64(f) * Nn)).  pair_counts_device / tpr_at_fpr_device
+    count on the resident matrix (mpreid_pair_bucket_counts); all counts are integers and equal the host's bit for bit.
+  * ``R1_mAP_eval.extra_metrics`` / ``roc_fprs`` / ``pair_hist_bins`` / ``pair_hist_range`` -> ``last_metrics``
+    (TEST.EXTRA_METRICS / ROC_FPRS / PAIR_HIST_BINS / PAIR_HIST_RANGE); R1_mAP_eval_splits keeps per-split mINP only.
 """
 import numpy as np
 import torch
@@ -127,11 +142,13 @@ def eval_func(distmat, q_pids, g_pids, q_camids, g_camids, max_rank=50, remove_s
 _warned_host_ranking = False
 
 
-def _finish_positions(pos, cnt, fetch_rows, q_pids, g_pids, max_rank, rcap, q_camids=None, g_camids=None):
+def _finish_positions(pos, cnt, fetch_rows, q_pids, g_pids, max_rank, rcap, q_camids=None, g_camids=None, extra=None):
     """The host tail of the device ranking, shared by the single-split and the multi-split paths: from the kernel's
     positions (pos [rows, rcap] int64 padded with -1, cnt [rows] int64) to (cmc hit counts, AP of every valid row, number of
     valid rows) in float64.  Rows handed back with cnt < 0 (more relevant items than the kernel holds in LDS) are ranked
-    here: ``fetch_rows(over)`` returns their distance rows [len(over), ng] as numpy, aligned with g_pids / g_camids."""
+    here: ``fetch_rows(over)`` returns their distance rows [len(over), ng] as numpy, aligned with g_pids / g_camids.
+    `extra`: a dict that also receives, for ALL rows, ``valid`` (bool), ``R`` (relevant items), ``first`` and ``last`` (0-based
+    position of the first / last relevant item, -1 for a row without one) -- what mINP needs; the return value is unchanged."""
     num_q = pos.shape[0]
     cam = q_camids is not None
     over = np.nonzero(cnt < 0)[0]          # queries with more relevant items than the kernel handles: host ranking
@@ -160,6 +177,12 @@ def _finish_positions(pos, cnt, fetch_rows, q_pids, g_pids, max_rank, rcap, q_ca
             cnt[qi] = p.size
     valid = cnt > 0
     num_valid = int(valid.sum())
+    if extra is not None:
+        rows = np.arange(num_q)
+        extra["valid"], extra["R"] = valid.copy(), np.where(valid, cnt, 0).astype(np.int64)
+        extra["first"] = np.where(valid, pos[:, 0], -1).astype(np.int64) if pos.shape[1] else np.full(num_q, -1, np.int64)
+        extra["last"] = np.where(valid, pos[rows, np.maximum(cnt, 1) - 1], -1).astype(np.int64) if pos.shape[1] \
+            else np.full(num_q, -1, np.int64)
     if num_valid == 0:
         return np.zeros(max_rank, np.float32), np.zeros(0, np.float64), 0
     pos, cnt = pos[valid], cnt[valid]
@@ -170,7 +193,7 @@ def _finish_positions(pos, cnt, fetch_rows, q_pids, g_pids, max_rank, rcap, q_ca
     return cmc_rows.sum(0), terms.sum(axis=1) / cnt, num_valid
 
 
-def _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch=None, q_camids=None, g_camids=None):
+def _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch=None, q_camids=None, g_camids=None, extra=None):
     """Ranking statistics of the query ROWS in `dist` (device tensor [rows, ng] fp32): (cmc hit counts [max_rank] float32
     summed over the valid rows, AP of every valid row in row order (float64), number of valid rows).  Sums of 0/1 values
     are exact in float32, so hit counts of row shards add up to the unsharded counts bit for bit.
@@ -195,6 +218,9 @@ def _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch=None, q_camid
     if num_q == 0:
         if after_launch is not None:
             after_launch()
+        if extra is not None:
+            extra.update(valid=np.zeros(0, bool), R=np.zeros(0, np.int64), first=np.zeros(0, np.int64),
+                         last=np.zeros(0, np.int64))
         return np.zeros(max_rank, np.float32), np.zeros(0, np.float64), 0
     rcap = _pid_rcap(g_pids)
     qp, gp = torch.from_numpy(q_pids).to(dev), torch.from_numpy(g_pids).to(dev)
@@ -216,11 +242,11 @@ def _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch=None, q_camid
         after_launch()
     pos, cnt = pos.cpu().numpy().astype(np.int64), cnt.cpu().numpy().astype(np.int64)
     return _finish_positions(pos, cnt, lambda over: dist[torch.from_numpy(over).to(dev)].cpu().numpy(), q_pids, g_pids,
-                             max_rank, rcap, q_camids, g_camids)
+                             max_rank, rcap, q_camids, g_camids, extra)
 
 
 def eval_func_device(dist, q_pids, g_pids, q_camids=None, g_camids=None, max_rank=50, after_launch=None,
-                     remove_same_cam=False):
+                     remove_same_cam=False, extra=None):
     """eval_func with the ranking done on the GPU (dist: device tensor [nq, ng] fp32, left on the device).
 
     Per query the kernel returns the positions of the relevant gallery items in the ascending (distance, index)
@@ -232,7 +258,10 @@ def eval_func_device(dist, q_pids, g_pids, q_camids=None, g_camids=None, max_ran
     the camera ids are unused and the call is what it was before the option existed.
 
     Under a process group (one rank per GPU) `dist` may be this rank's ROW block and q_pids its rows' pids: see
-    eval_func_sharded."""
+    eval_func_sharded.
+
+    extra: a dict that also receives the per-query statistics of the SAME ranking launch (``valid``, ``R``, ``first``,
+    ``last``: _finish_positions; ``all_AP``: the AP of the valid queries) -- eval_metrics_device builds mINP from them."""
     if remove_same_cam:
         _need_camids(q_camids, g_camids)
     num_g = dist.shape[1]
@@ -240,10 +269,12 @@ def eval_func_device(dist, q_pids, g_pids, q_camids=None, g_camids=None, max_ran
         max_rank = num_g
         print("Note: number of gallery samples is quite small, got {}".format(num_g))
     if remove_same_cam:
-        hits, ap, num_valid = _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch, q_camids, g_camids)
+        hits, ap, num_valid = _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch, q_camids, g_camids, extra)
     else:
-        hits, ap, num_valid = _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch)
+        hits, ap, num_valid = _eval_rows_device(dist, q_pids, g_pids, max_rank, after_launch, extra=extra)
     assert num_valid > 0, "Error: all query identities do not appear in gallery"
+    if extra is not None:
+        extra["all_AP"] = ap
     return hits / float(num_valid), np.mean(ap)
 
 
@@ -338,13 +369,15 @@ def _pid_rcap(pids):
     return int(min(max(np.unique(pids, return_counts=True)[1].max(), 1), 8192))   # (the kernel's LDS limit, include/mpreid.h)
 
 
-def eval_func_splits_device(dist_pool, pids, camids, splits, max_rank=50, remove_same_cam=False):
+def eval_func_splits_device(dist_pool, pids, camids, splits, max_rank=50, remove_same_cam=False, extras=None):
     """eval_func_splits with the ranking on the GPU: `dist_pool` is the pool x pool matrix as a device fp32 tensor (unit
     column stride, rows through dist_pool.stride(0); left on the device).  ONE launch of mpreid_eval_rank_positions_splits
     ranks every (split, query) pair -- a pair reads its row of the matrix through its split's gallery index list, no
     sub-matrix is gathered -- and ONE D2H copy brings the positions back; per split, CMC / AP are then finished by the
     float64 tail eval_func_device uses (_finish_positions), so a split's numbers are those of eval_func_device on its
-    sub-matrix.  Rows over the kernel's capacity are ranked on the host from the gathered row."""
+    sub-matrix.  Rows over the kernel's capacity are ranked on the host from the gathered row.
+    extras: a list that receives one dict per split with the per-query statistics of _finish_positions plus ``all_AP``
+    (host tail only: the positions are already here) -- R1_mAP_eval_splits derives the per-split mINP from them."""
     import ctypes as C
     from mpreid import _lib
     dev = _lib.require_gpu()
@@ -398,9 +431,13 @@ def eval_func_splits_device(dist_pool, pids, camids, splits, max_rank=50, remove
 
         def fetch_rows(over, q=q, g_t=g_t):
             return dist[torch.from_numpy(q[over]).to(dev)].index_select(1, g_t).cpu().numpy()
+        extra = None if extras is None else {}
         hits, ap, num_valid = _finish_positions(pos_all[lo:hi, :w].copy(), cnt_all[lo:hi].copy(), fetch_rows, pids[q],
-                                                g_pids, mr, w, camids[q] if cam else None, camids[g] if cam else None)
+                                                g_pids, mr, w, camids[q] if cam else None, camids[g] if cam else None, extra)
         assert num_valid > 0, f"split {i}: Error: all query identities do not appear in gallery"
+        if extras is not None:
+            extra["all_AP"] = ap
+            extras.append(extra)
         cmcs.append(hits / float(num_valid))
         maps[i] = np.mean(ap)
     return cmcs, maps
@@ -514,6 +551,180 @@ def expand_features_device(qf, gf, k, alpha=3.0, times=1, mode=_ops.GEMM_F32_EXA
     return q.cpu().numpy(), g.cpu().numpy()
 
 
+DEFAULT_ROC_FPRS = (1e-4, 1e-3, 1e-2)
+
+
+def _pair_classes(distmat, q_pids, g_pids, q_camids, g_camids, remove_same_cam):
+    """(keys uint32 [nq, ng], positive mask, negative mask) of the kept pairs (module docstring, "Pairs")"""
+    distmat = np.asarray(distmat, dtype=np.float32)
+    if distmat.ndim != 2:
+        raise ValueError(f"distmat has shape {distmat.shape}: a [nq, ng] matrix is expected")
+    q_pids, g_pids = np.asarray(q_pids), np.asarray(g_pids)
+    if q_pids.shape != (distmat.shape[0],) or g_pids.shape != (distmat.shape[1],):
+        raise ValueError("q_pids / g_pids do not match the matrix")
+    kept = np.isfinite(distmat)
+    same = q_pids[:, None] == g_pids[None, :]
+    if remove_same_cam:
+        _need_camids(q_camids, g_camids)
+        kept &= ~(same & (np.asarray(q_camids)[:, None] == np.asarray(g_camids)[None, :]))
+    return _ops.dist_keys(distmat), kept & same, kept & ~same
+
+
+def _threshold_keys(thresholds):
+    t = np.asarray(thresholds, dtype=np.float32)
+    if t.ndim != 1 or t.size < 1 or np.isnan(t).any():
+        raise ValueError("thresholds: a non-empty 1-D list of numbers is expected")
+    k = _ops.dist_keys(t)
+    if k.size > 1 and not bool(np.all(k[1:] > k[:-1])):
+        raise ValueError("thresholds must be strictly ascending (as float32, -0 equal to +0)")
+    return k
+
+
+def pair_counts(distmat, thresholds, q_pids, g_pids, q_camids=None, g_camids=None, remove_same_cam=False):
+    """Verification counts over all query x gallery pairs (module docstring): for ascending thresholds t_0 < ... < t_{B-1}
+    returns {"tp": int64 [B], "fp": int64 [B], "P": int, "Nn": int} with tp[b] / fp[b] = positive / negative pairs with
+    d <= t_b (through the key order).  ROC: (fp / Nn, tp / P).  Host, numpy: the definition."""
+    tk = _threshold_keys(thresholds)
+    keys, pos, neg = _pair_classes(distmat, q_pids, g_pids, q_camids, g_camids, remove_same_cam)
+    pk, nk = np.sort(keys[pos]), np.sort(keys[neg])
+    return {"tp": np.searchsorted(pk, tk, side="right").astype(np.int64),
+            "fp": np.searchsorted(nk, tk, side="right").astype(np.int64), "P": int(pk.size), "Nn": int(nk.size)}
+
+
+def pair_histograms(counts):
+    """(positive, negative) histograms int64 [B + 1] of a pair_counts result over its B thresholds taken as bin edges:
+    entry 0 = underflow (d <= t_0), entry b = pairs with t_{b-1} < d <= t_b, entry B = overflow (d > t_{B-1}); they sum
+    to P and Nn."""
+    out = []
+    for c, total in ((counts["tp"], counts["P"]), (counts["fp"], counts["Nn"])):
+        out.append(np.diff(np.concatenate([[0], np.asarray(c, np.int64), [total]])).astype(np.int64))
+    return out[0], out[1]
+
+
+def _budgets(fprs, max_fp, Nn):
+    """(budgets int64, fprs float64 or None): integer false-positive budgets from rates (floor(f * Nn)) or given directly"""
+    if max_fp is not None:
+        if fprs is not None:
+            raise ValueError("give fprs or max_fp, not both")
+        return _ops._check_budgets(np.atleast_1d(np.asarray(max_fp))), None
+    fprs = np.atleast_1d(np.asarray(DEFAULT_ROC_FPRS if fprs is None else fprs, dtype=np.float64))
+    if fprs.ndim != 1 or fprs.size < 1 or fprs.size > _ops.PAIR_SELECT_MAX or not bool(np.all((fprs >= 0) & (fprs <= 1))):
+        raise ValueError(f"fprs: 1 ... {_ops.PAIR_SELECT_MAX} rates in [0, 1] are expected")
+    return np.array([int(np.floor(np.float64(f) * Nn)) for f in fprs], np.int64), fprs
+
+
+def _operating_points(budgets, fprs, tau, tp, fp, P, Nn):
+    with np.errstate(invalid="ignore", divide="ignore"):
+        tpr = np.asarray(tp, np.float64) / np.float64(P) if P else np.full(len(tp), np.nan)
+        fpr = np.asarray(fp, np.float64) / np.float64(Nn) if Nn else np.full(len(fp), np.nan)
+    return {"budgets": np.asarray(budgets, np.int64), "fprs": fprs, "tau": np.asarray(tau, np.float32),
+            "tp": np.asarray(tp, np.int64), "fp": np.asarray(fp, np.int64), "P": int(P), "Nn": int(Nn), "tpr": tpr,
+            "fpr": fpr}
+
+
+def tpr_at_fpr(distmat, q_pids, g_pids, q_camids=None, g_camids=None, remove_same_cam=False, fprs=None, max_fp=None):
+    """TPR at a false-positive budget (module docstring): per budget m (``max_fp``: integers; or ``fprs``: rates, m =
+    int(np.floor(np.float64(f) * Nn)); default rates 1e-4, 1e-3, 1e-2) tau = the (m + 1)-th smallest negative distance
+    counted with multiplicity, tp / fp = positive / negative pairs with d < tau, everything accepted (tau = +inf) when
+    m >= Nn.  Returns a dict: budgets, fprs (None with max_fp), tau (float32: the entry's bits, a zero as +0), tp, fp, P, Nn,
+    tpr = tp / P (nan if P == 0), fpr = fp / Nn (the realised rate; nan if Nn == 0).  Host, numpy: the definition."""
+    keys, pos, neg = _pair_classes(distmat, q_pids, g_pids, q_camids, g_camids, remove_same_cam)
+    pk, nk = np.sort(keys[pos]), np.sort(keys[neg])
+    P, Nn = int(pk.size), int(nk.size)
+    budgets, fprs = _budgets(fprs, max_fp, Nn)
+    tau = np.full(budgets.size, np.inf, np.float32)
+    tp, fp = np.full(budgets.size, P, np.int64), np.full(budgets.size, Nn, np.int64)
+    for i, m in enumerate(budgets.tolist()):
+        if m < Nn:
+            tk = nk[m]
+            tau[i] = _ops.keys_to_dist(tk)
+            tp[i] = np.searchsorted(pk, tk, side="left")
+            fp[i] = np.searchsorted(nk, tk, side="left")
+    return _operating_points(budgets, fprs, tau, tp, fp, P, Nn)
+
+
+def _metrics_dict(cmc, mAP, all_AP, extra):
+    valid = extra["valid"]
+    inp = extra["R"][valid].astype(np.float64) / (extra["last"][valid].astype(np.float64) + 1.0)
+    return {"cmc": cmc, "mAP": mAP, "mINP": np.mean(inp), "all_AP": all_AP, "all_INP": inp,
+            "first_hit": extra["first"], "valid": valid}
+
+
+def eval_metrics(distmat, q_pids, g_pids, q_camids, g_camids, max_rank=50, remove_same_cam=False):
+    """eval_func plus mINP and the per-query statistics: {"cmc", "mAP": eval_func's own return values, to the bit;
+    "mINP": np.mean of INP = R / (p_last + 1) over the valid queries in query order; "all_AP", "all_INP": float64 per VALID
+    query; "first_hit": int64 [nq], 0-based position of the first relevant item in the kept ranking (-1: none); "valid":
+    bool [nq]}.  all_AP sums a query's precision terms over its relevant items alone (the order eval_func_device uses), so
+    np.mean(all_AP) may differ from eval_func's mAP -- a sum over the dense row -- in the last bit.  Host, numpy: the
+    definition."""
+    distmat = np.asarray(distmat)
+    q_pids, g_pids = np.asarray(q_pids), np.asarray(g_pids)
+    cmc, mAP = eval_func(distmat, q_pids, g_pids, q_camids, g_camids, max_rank, remove_same_cam)
+    num_q, num_g = distmat.shape
+    max_rank = min(max_rank, num_g)
+    cam = bool(remove_same_cam)
+    q_c, g_c = (np.asarray(q_camids), np.asarray(g_camids)) if cam else (None, None)
+    rcap = _pid_rcap(g_pids)
+    order = np.argsort(distmat, axis=1, kind="stable")
+    pos = np.full((num_q, rcap), -1, np.int64)
+    cnt = np.zeros(num_q, np.int64)
+    for i in range(num_q):
+        match = g_pids[order[i]] == q_pids[i]
+        if int(match.sum()) > rcap:
+            cnt[i] = -1                      # over the device kernel's capacity: the shared tail ranks the row itself
+            continue
+        if cam:
+            junk = match & (g_c[order[i]] == q_c[i])
+            p = (np.cumsum(~junk) - 1)[match & ~junk]
+        else:
+            p = np.nonzero(match)[0]
+        pos[i, :p.size] = p
+        cnt[i] = p.size
+    extra = {}
+    _, ap, _ = _finish_positions(pos, cnt, lambda over: distmat[over], q_pids, g_pids, max_rank, rcap, q_c, g_c, extra)
+    return _metrics_dict(cmc, mAP, ap, extra)
+
+
+def eval_metrics_device(dist, q_pids, g_pids, q_camids=None, g_camids=None, max_rank=50, remove_same_cam=False,
+                        after_launch=None):
+    """eval_metrics on a RESIDENT matrix: ONE ranking launch (eval_func_device's; rows over the kernel's capacity go through
+    its host ranking), the same float64 tail, so cmc / mAP are eval_func_device's bits and mINP / all_AP / all_INP /
+    first_hit / valid equal eval_metrics' on the same matrix."""
+    extra = {}
+    cmc, mAP = eval_func_device(dist, q_pids, g_pids, q_camids, g_camids, max_rank, after_launch, remove_same_cam, extra)
+    return _metrics_dict(cmc, mAP, extra.pop("all_AP"), extra)
+
+
+def _cam_args(q_camids, g_camids, remove_same_cam):
+    if not remove_same_cam:
+        return None, None
+    _need_camids(q_camids, g_camids)
+    return q_camids, g_camids
+
+
+def pair_counts_device(dist, thresholds, q_pids, g_pids, q_camids=None, g_camids=None, remove_same_cam=False):
+    """pair_counts on a RESIDENT matrix (device fp32 tensor [nq, ng], left on the device): one pass of
+    mpreid_pair_bucket_counts, at most 4096 thresholds per call; the same dict, equal as integers."""
+    tk = _threshold_keys(thresholds)
+    qc, gc = _cam_args(q_camids, g_camids, remove_same_cam)
+    c = _ops.pair_bucket_counts(dist, q_pids, g_pids, qc, gc, bound_keys=tk).cpu().numpy()
+    return {"tp": np.cumsum(c[0])[:-1].astype(np.int64), "fp": np.cumsum(c[1])[:-1].astype(np.int64),
+            "P": int(c[0].sum()), "Nn": int(c[1].sum())}
+
+
+def tpr_at_fpr_device(dist, q_pids, g_pids, q_camids=None, g_camids=None, remove_same_cam=False, fprs=None, max_fp=None):
+    """tpr_at_fpr on a RESIDENT matrix through ops.pair_select (exact radix selection over the keys; no sort of the
+    nq * ng scores): the same dict, the counts equal as integers and tau as bytes."""
+    qc, gc = _cam_args(q_camids, g_camids, remove_same_cam)
+    if max_fp is not None:
+        budgets, fprs = _budgets(fprs, max_fp, 0)
+        r = _ops.pair_select(dist, q_pids, g_pids, qc, gc, budgets=budgets)
+    else:
+        _, fprs = _budgets(fprs, None, 0)
+        r = _ops.pair_select(dist, q_pids, g_pids, qc, gc, fprs=fprs)
+    return _operating_points(r["budgets"], fprs, r["tau"], r["tp"], r["fp"], r["P"], r["Nn"])
+
+
 def _check_finite(feats, collective=False):
     """An encoder whose fp16 operand halves overflowed (|activation| > 65 504 in the 'split' / 'fp16' precision modes:
     include/mpreid.h, mpreid_vit_forward) hands over NaN / inf feature rows; ranking them would print a plausible-looking
@@ -573,6 +784,20 @@ def _qe_setting(ev):
     return _qe_args(k, getattr(ev, "qe_alpha", 3.0), getattr(ev, "qe_times", 1))
 
 
+def _hist_edges(bins, rng):
+    """None for bins == 0, else the float32 edges [bins + 1] of the pair-distance histograms: ValueError before device work"""
+    if int(bins) != bins or int(bins) < 0 or int(bins) + 1 > _ops.PAIR_BOUNDS_MAX:
+        raise ValueError(f"pair_hist_bins = {bins}: an integer 0 ... {_ops.PAIR_BOUNDS_MAX - 1} is expected")
+    if int(bins) == 0:
+        return None
+    lo, hi = (float(x) for x in rng)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError(f"pair_hist_range = {tuple(rng)}: finite lo < hi is expected")
+    edges = np.linspace(lo, hi, int(bins) + 1).astype(np.float32)
+    _threshold_keys(edges)      # (too many bins for the range in float32: not strictly ascending)
+    return edges
+
+
 class R1_mAP_eval():
     def __init__(self, num_query, max_rank=50, feat_norm=True, reranking=False):
         super(R1_mAP_eval, self).__init__()
@@ -589,6 +814,16 @@ class R1_mAP_eval():
         # qe_k > 0: query expansion (expand_features: AQE + DBA over query || gallery) with k neighbours, weight exponent
         # qe_alpha, qe_times rounds, before normalisation and ranking (TEST.QE_K / QE_ALPHA / QE_TIMES)
         self.qe_k, self.qe_alpha, self.qe_times = 0, 3.0, 1
+        # extra_metrics: compute() also fills last_metrics -- the eval_metrics dict (mINP, per-query AP / INP / first hit)
+        # from the SAME ranking launch, "tpr_at_fpr" (the tpr_at_fpr dict at roc_fprs) and, with pair_hist_bins > 0,
+        # "pair_hist_edges" (float32 [bins + 1] over pair_hist_range) / "pair_hist_pos" / "pair_hist_neg" (int64 [bins + 2]:
+        # underflow, the bins (e_{b-1}, e_b], overflow; pair_histograms) -- of the matrix behind `distmat`, while it is
+        # resident (TEST.EXTRA_METRICS / ROC_FPRS / PAIR_HIST_BINS / PAIR_HIST_RANGE)
+        self.extra_metrics = False
+        self.roc_fprs = DEFAULT_ROC_FPRS
+        self.pair_hist_bins = 0
+        self.pair_hist_range = (0.0, 4.0)
+        self.last_metrics = None
 
     def reset(self):
         self.feats = []
@@ -614,6 +849,13 @@ class R1_mAP_eval():
         qe = _qe_setting(self)
         if qe and D.sharded_active():
             raise NotImplementedError("query expansion is single-process")
+        extra_on = bool(getattr(self, "extra_metrics", False))
+        self.last_metrics = None
+        if extra_on:
+            if D.sharded_active():
+                raise NotImplementedError("extra metrics are single-process")
+            hist_edges = _hist_edges(getattr(self, "pair_hist_bins", 0), getattr(self, "pair_hist_range", (0.0, 4.0)))
+            roc_fprs = _budgets(getattr(self, "roc_fprs", None), None, 0)[1]
         if D.sharded_active():
             return self._compute_sharded()
         feats = torch.cat(self.feats, dim=0)
@@ -654,12 +896,21 @@ class R1_mAP_eval():
 
         def start_copy():
             box["h"], box["ev"] = _to_host_async([dist])
+        extra = {} if extra_on else None     # the per-query statistics of the ONE ranking launch below
         if os.environ.get("MPREID_EVAL_D2H") == "behind":
             cmc, mAP = eval_func_device(dist, q_pids, g_pids, q_camids, g_camids, after_launch=start_copy,
-                                        remove_same_cam=same_cam)
+                                        remove_same_cam=same_cam, extra=extra)
         else:
             start_copy()
-            cmc, mAP = eval_func_device(dist, q_pids, g_pids, q_camids, g_camids, remove_same_cam=same_cam)
+            cmc, mAP = eval_func_device(dist, q_pids, g_pids, q_camids, g_camids, remove_same_cam=same_cam, extra=extra)
+        if extra_on:   # the pair statistics count over the same resident matrix
+            m = _metrics_dict(cmc, mAP, extra.pop("all_AP"), extra)
+            m["tpr_at_fpr"] = tpr_at_fpr_device(dist, q_pids, g_pids, q_camids, g_camids, same_cam, fprs=roc_fprs)
+            if hist_edges is not None:
+                c = pair_counts_device(dist, hist_edges, q_pids, g_pids, q_camids, g_camids, same_cam)
+                m["pair_hist_edges"] = hist_edges
+                m["pair_hist_pos"], m["pair_hist_neg"] = pair_histograms(c)
+            self.last_metrics = m
         if list_k:   # the lists of the matrix behind `distmat` (Euclidean or re-ranked), while it is resident
             self.last_rank_lists = rank_lists_device(dist, list_k, q_pids, g_pids, q_camids, g_camids, same_cam)
         (h_dist,), copied = box["h"], box["ev"]
@@ -767,6 +1018,10 @@ class R1_mAP_eval_splits():
         self.last_rerank_stats = None
         self.last_dist = None          # the pooled device matrix of the last compute() (None on the split-by-split path)
         self.qe_k, self.qe_alpha, self.qe_times = 0, 3.0, 1   # query expansion, as in R1_mAP_eval
+        # extra_metrics: compute() also fills last_metrics = {"mINP": float64 [S], "all_INP": list of S arrays} from the
+        # positions it copies back anyway (host tail only; pair statistics are not built for splits)
+        self.extra_metrics = False
+        self.last_metrics = None
 
     def reset(self):
         self.feats = []
@@ -786,6 +1041,8 @@ class R1_mAP_eval_splits():
         if D.sharded_active():
             raise NotImplementedError("multi-trial evaluation is single-process")
         qe = _qe_setting(self)
+        extras = [] if getattr(self, "extra_metrics", False) else None
+        self.last_metrics = None
         feats = torch.cat(self.feats, dim=0)
         _check_finite(feats)
         raw = feats
@@ -801,7 +1058,7 @@ class R1_mAP_eval_splits():
         if not qe and not self.reranking and _pool_matrix_fits(n):
             print('=> Computing the pool DistMat with euclidean_distance')
             dist = _ops.euclidean_distance(feats, feats, mode=self.distance_mode)
-            cmcs, maps = eval_func_splits_device(dist, pids, camids, splits, self.max_rank, same_cam)
+            cmcs, maps = eval_func_splits_device(dist, pids, camids, splits, self.max_rank, same_cam, extras)
             self.last_dist = dist
         else:
             dev = feats.device
@@ -823,11 +1080,17 @@ class R1_mAP_eval_splits():
                     _ops.release_workspaces("rerank")
                 else:
                     dist = _ops.euclidean_distance(qf, gf, mode=self.distance_mode)
+                extra = None if extras is None else {}
                 try:
                     cmc, maps[i] = eval_func_device(dist, pids[q], pids[g], camids[q], camids[g], self.max_rank,
-                                                    remove_same_cam=same_cam)
+                                                    remove_same_cam=same_cam, extra=extra)
                 except AssertionError as e:
                     raise AssertionError(f"split {i}: {e}") from None
                 cmcs.append(cmc)
+                if extras is not None:
+                    extras.append(extra)
+        if extras is not None:
+            inps = [_metrics_dict(None, None, e["all_AP"], e)["all_INP"] for e in extras]
+            self.last_metrics = {"mINP": np.array([np.mean(x) for x in inps], np.float64), "all_INP": inps}
         feats_copied.synchronize()
         return cmcs, maps, self.pids, self.camids, h_feats
