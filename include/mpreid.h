@@ -475,39 +475,11 @@ typedef struct { /* device pointers */
     float conv_s;                               /* SPLIT mode: 2^-e of conv_w */
 } mpreid_vit_weights;
 
-size_t mpreid_vit_workspace_bytes(const mpreid_vit_cfg *cfg, int batch);
-/* img_dev [B][3][img_h][img_w] fp32 (already mean/std normalised); cv_emb_dev NULL or [B][width]
- * (SIE_COE * cv_embed[idx], model/make_model.py:89-96); out_dev [B][width+out_dim] fp32. */
-int mpreid_vit_forward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const float *img_dev, int batch,
-                       const float *cv_emb_dev, float *out_dev, void *ws_dev, size_t ws_bytes,
-                       mpreid_stream_t stream);
-
-/* All-fp32 mode of the same encoder (parity / debugging; SURVEY.md section 7 hard part 5): activations and weights
- * fp32, linear layers on the exact fp32 matrix instruction, attention on fp32 vector FMAs -- relative feature error
- * ~1e-6 against the fp32 CPU path instead of ~4e-4, at ~1/8 of the throughput.  The structs are the ones above,
- * but conv_w and every layer's *_w point to FP32 [out][in] matrices.  Head dimension 64 only. */
-size_t mpreid_vit_workspace_bytes_f32(const mpreid_vit_cfg *cfg, int batch);
-int mpreid_vit_forward_f32(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w_f32, const float *img_dev, int batch,
-                           const float *cv_emb_dev, float *out_dev, void *ws_dev, size_t ws_bytes,
-                           mpreid_stream_t stream);
-/* the all-fp32 mode on uint8 input and / or one test-time-augmentation view (MPREID_VIEW_* below): exactly one of
- * img_f32_dev ([B][3][H][W], already normalised) and img_hwc_u8_dev ([B][H][W][3] + pixel_mean3 / pixel_std3 host arrays) is
- * non-NULL; ToTensor + Normalize and the view transform happen inside the patch gather, in the reference's arithmetic */
-int mpreid_vit_forward_f32_view(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w_f32, const float *img_f32_dev,
-                                const uint8_t *img_hwc_u8_dev, const float *pixel_mean3, const float *pixel_std3, int view,
-                                int batch, const float *cv_emb_dev, float *out_dev, void *ws_dev, size_t ws_bytes,
-                                mpreid_stream_t stream);
-
-/* same, from uint8 images [B][img_h][img_w][3] (HWC, after Resize): ToTensor (x/255) and Normalize
- * ((x - pixel_mean)/pixel_std, host arrays of 3 floats: INPUT.PIXEL_MEAN / PIXEL_STD) of the reference's
- * val_transforms (datasets/make_dataloader.py:57-61) are fused into the patch gather; 4x fewer input bytes. */
-int mpreid_vit_forward_u8(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const uint8_t *img_hwc_dev,
-                          const float *pixel_mean3, const float *pixel_std3, int batch, const float *cv_emb_dev,
-                          float *out_dev, void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
-
-/* Test-time-augmentation views of the reference's Uni-Prompt evaluation ("option A",
- * processor/processor_uniprompt_stage2.py:605-633), applied while the patches are gathered instead of
- * materialising a transformed [B,3,H,W] tensor per view. */
+/* ---- the image batch every encoder forward takes ----------------------------------------------------------------
+ * Test-time-augmentation views of the reference's Uni-Prompt evaluation ("option A",
+ * processor/processor_uniprompt_stage2.py:605-633), applied to the NORMALISED pixels while the first kernel of a tower
+ * reads them (the ViT's patch gather, the RN50 stem's first convolution) instead of materialising a transformed
+ * [B,3,H,W] tensor per view: the same bits as the view tensor materialised on the host. */
 #define MPREID_VIEW_ORIGINAL 0
 #define MPREID_VIEW_FLIP 1        /* torch.flip(img, [3]) */
 #define MPREID_VIEW_PSEUDO_IR 2   /* img.mean(dim=1, keepdim=True).repeat(1, 3, 1, 1) -- in the HOST arithmetic of torch.mean,
@@ -516,12 +488,36 @@ int mpreid_vit_forward_u8(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w
                                    * features of a device-materialised view agree to ~1e-6, not to the bit
                                    * (tests/test_gpu_preprocess.py::test_pseudo_ir_view_against_a_device_materialised_view) */
 #define MPREID_VIEW_PSEUDO_RGB 3  /* img[:, 0:1].repeat(1, 3, 1, 1) */
-/* mpreid_vit_forward / mpreid_vit_forward_u8 on one view: exactly one of img_f32_dev ([B][3][H][W], already
- * normalised) and img_hwc_u8_dev ([B][H][W][3] + pixel_mean3 / pixel_std3 host arrays) is non-NULL. */
-int mpreid_vit_forward_view(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const float *img_f32_dev,
-                            const uint8_t *img_hwc_u8_dev, const float *pixel_mean3, const float *pixel_std3, int view,
-                            int batch, const float *cv_emb_dev, float *out_dev, void *ws_dev, size_t ws_bytes,
-                            mpreid_stream_t stream);
+/* A HOST struct.  EXACTLY ONE of the two pointers is non-NULL:
+ *   f32_dev     [B][3][img_h][img_w] fp32, val_transforms applied (already mean / std normalised)
+ *   u8_hwc_dev  [B][img_h][img_w][3] uint8, what the loader has after Resize (4x fewer input bytes): ToTensor and Normalize
+ *               of val_transforms (datasets/make_dataloader.py:57-61) run inside the first kernel, in the reference's order
+ *               and rounding, (x / 255 - mean[c]) / std[c] with two correctly rounded divisions -- the same bits as the
+ *               host-transformed fp32 tensor, no intermediate tensor
+ * mean / std (INPUT.PIXEL_MEAN / PIXEL_STD) are read only with uint8 input.  view is one of MPREID_VIEW_* (0 for a plain
+ * forward).  NULL, both or neither pointer, or a view outside 0..3: MPREID_ERR_ARG, before anything is launched. */
+typedef struct {
+    const float *f32_dev;
+    const uint8_t *u8_hwc_dev;
+    float mean[3], std[3];
+    int32_t view;
+} mpreid_image_in;
+
+size_t mpreid_vit_workspace_bytes(const mpreid_vit_cfg *cfg, int batch);
+/* img: the batch (above); cv_emb_dev NULL or [B][width] (SIE_COE * cv_embed[idx], model/make_model.py:89-96);
+ * out_dev [B][width+out_dim] fp32. */
+int mpreid_vit_forward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_image_in *img, int batch,
+                       const float *cv_emb_dev, float *out_dev, void *ws_dev, size_t ws_bytes,
+                       mpreid_stream_t stream);
+
+/* All-fp32 mode of the same encoder (parity / debugging; SURVEY.md section 7 hard part 5): activations and weights
+ * fp32, linear layers on the exact fp32 matrix instruction, attention on fp32 vector FMAs -- relative feature error
+ * ~1e-6 against the fp32 CPU path instead of ~4e-4, at ~1/8 of the throughput.  The structs are the ones above,
+ * but conv_w and every layer's *_w point to FP32 [out][in] matrices.  Head dimension 64 only. */
+size_t mpreid_vit_workspace_bytes_f32(const mpreid_vit_cfg *cfg, int batch);
+int mpreid_vit_forward_f32(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w_f32, const mpreid_image_in *img, int batch,
+                           const float *cv_emb_dev, float *out_dev, void *ws_dev, size_t ws_bytes,
+                           mpreid_stream_t stream);
 /* processor/processor_uniprompt_stage2.py:636-640: out[rows][dim] = mean over the views of
  * feats[n_views][rows][dim] (sequential sum in view order, true division), then F.normalize(p=2, dim=1,
  * eps=1e-12) when normalize != 0. */
@@ -532,7 +528,7 @@ int mpreid_tta_mean_f32(const float *feats_dev, int n_views, int64_t rows, int d
  * uint8 RGB images: bit-exact with PIL.Image.resize((out_w, out_h), BILINEAR) (Pillow 8-bit two-pass resample,
  * which is what torchvision's Resize calls for PIL inputs).  Image b is src_dev[offsets_dev[b] ...] as [h][w][3]
  * with (h, w) = hw_dev[2b], hw_dev[2b+1]; max_in_h >= every h.  dst_dev is [batch][out_h][out_w][3], the input
- * layout of mpreid_vit_forward_u8. */
+ * layout of mpreid_image_in.u8_hwc_dev. */
 size_t mpreid_resize_workspace_bytes(int batch, int max_in_h, int out_w);
 int mpreid_resize_bilinear_u8(const uint8_t *src_dev, const int64_t *offsets_dev, const int32_t *hw_dev, int batch,
                               int max_in_h, int out_h, int out_w, uint8_t *dst_dev, void *ws_dev, size_t ws_bytes,
@@ -580,18 +576,16 @@ typedef struct { /* device pointers unless noted */
 } mpreid_rn50_weights;
 
 size_t mpreid_rn50_workspace_bytes(const mpreid_rn50_cfg *cfg, int batch);
-/* exactly one of img_f32_dev ([B][3][H][W] fp32, val_transforms applied) and img_hwc_u8_dev ([B][H][W][3] uint8 +
- * pixel_mean3 / pixel_std3 host arrays: ToTensor + Normalize fused into the first convolution) is non-NULL;
- * out_dev [B][32*width + out_dim] fp32. */
-int mpreid_rn50_forward(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights *w, const float *img_f32_dev,
-                        const uint8_t *img_hwc_u8_dev, const float *pixel_mean3, const float *pixel_std3, int batch,
+/* img: the batch (mpreid_image_in above); this tower has no in-kernel view: view != 0 -> MPREID_ERR_UNSUPPORTED (the split
+ * and fp32 towers below take every view).  out_dev [B][32*width + out_dim] fp32. */
+int mpreid_rn50_forward(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights *w, const mpreid_image_in *img, int batch,
                         float *out_dev, void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
 
 /* All-fp32 mode of the RN50 tower (MODEL.NAME 'RN50' + MODEL.ENCODER_PRECISION 'fp32'; the reference runs the tower in
  * fp32): fp32 NHWC activations, every convolution a GEMM on the exact fp32 matrix instruction (3x3: im2col, k order
  * (kh, kw, c)), BatchNorm folded on the host, fp32 attention pool -- relative feature error ~1e-6 against the fp32 CPU path
  * instead of the fp16 tower's 2.6e-3, at ~1/10 of its throughput.  Weight matrices are fp32 [cout][taps*cin] with the REAL
- * channel counts (no padding); input fp32 NCHW only. */
+ * channel counts (no padding). */
 typedef struct { const float *w; const float *bias; int32_t cin, cout, taps; } mpreid_rn50_conv_f32;
 typedef struct { mpreid_rn50_conv_f32 conv1, conv2, conv3, down; int32_t stride; } mpreid_rn50_block_f32;  /* down.w NULL: none */
 typedef struct {
@@ -604,14 +598,8 @@ typedef struct {
     const float *bn_scale, *bn_shift;            /* eval BN necks folded, [E + out_dim], or NULL */
 } mpreid_rn50_weights_f32;
 size_t mpreid_rn50_workspace_bytes_f32(const mpreid_rn50_cfg *cfg, int batch);
-int mpreid_rn50_forward_f32(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_f32 *w, const float *img_f32_dev, int batch,
+int mpreid_rn50_forward_f32(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_f32 *w, const mpreid_image_in *img, int batch,
                             float *out_dev, void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
-/* the same tower fed with uint8 [batch][H][W][3] images (after Resize): ToTensor + Normalize of
- * datasets/make_dataloader.py:57-61, (x / 255 - mean[c]) / std[c] with correctly rounded divisions, inside the stem's first
- * convolution -- same bits as the host-transformed fp32 tensor, a quarter of the input bytes, no intermediate tensor */
-int mpreid_rn50_forward_f32_u8(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_f32 *w, const uint8_t *img_u8_hwc_dev,
-                               const float *mean3, const float *std3, int batch, float *out_dev, void *ws_dev, size_t ws_bytes,
-                               mpreid_stream_t stream);
 
 /* SPLIT-precision mode of the RN50 tower (MODEL.NAME 'RN50' + MODEL.ENCODER_PRECISION 'split', the default): fp32 NHWC
  * activations; the convolutions of layer1-4 and the attention pool's k / v projections run on the fp16 matrix cores over
@@ -634,20 +622,8 @@ typedef struct {
     mpreid_rn50_conv_split stem2, stem3;         /* the stem's second and third convolution (f32.stem2 / stem3 are not read) */
 } mpreid_rn50_weights_split;
 size_t mpreid_rn50_workspace_bytes_split(const mpreid_rn50_cfg *cfg, int batch);
-int mpreid_rn50_forward_split(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_split *w, const float *img_f32_dev, int batch,
+int mpreid_rn50_forward_split(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_split *w, const mpreid_image_in *img, int batch,
                               float *out_dev, void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
-int mpreid_rn50_forward_split_u8(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_split *w, const uint8_t *img_u8_hwc_dev,
-                                 const float *mean3, const float *std3, int batch, float *out_dev, void *ws_dev, size_t ws_bytes,
-                                 mpreid_stream_t stream);   /* uint8 input, as mpreid_rn50_forward_f32_u8 */
-/* one test-time-augmentation view (MPREID_VIEW_*) of fp32 [B][3][H][W] or uint8 [B][H][W][3] input (exactly one pointer
- * non-NULL), the view transform applied to the normalised pixels inside the stem's first convolution: the same bits as the
- * materialised view tensor of processor/processor_uniprompt_stage2.py:605-633 */
-int mpreid_rn50_forward_split_view(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_split *w, const float *img_f32_dev,
-                                   const uint8_t *img_u8_hwc_dev, const float *mean3, const float *std3, int view, int batch,
-                                   float *out_dev, void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
-int mpreid_rn50_forward_f32_view(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_f32 *w, const float *img_f32_dev,
-                                 const uint8_t *img_u8_hwc_dev, const float *mean3, const float *std3, int view, int batch,
-                                 float *out_dev, void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
 
 /* One convolution layer of the RN50 tower as the encoder runs it (unit tests, micro-benchmarks):
  * NHWC fp16 in [batch][h][w][cin] (cin % 64 == 0), stride 1, taps = 1 (1x1) or 9 (3x3, pad 1); weights fp16

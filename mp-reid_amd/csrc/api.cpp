@@ -51,7 +51,7 @@ int mpreid_tune(const char *key, int dflt) {
     return dflt;
 }
 
-extern "C" int mpreid_version(void) { return 100; } /* 0.1.0 */
+extern "C" int mpreid_version(void) { return 101; } /* 0.1.1: mpreid/_lib.py (VERSION) loads exactly this one */
 
 // 1 for a library compiled with -DMPREID_ABLATION (timing-ablation switches honoured: WRONG RESULTS by design), else 0
 extern "C" int mpreid_is_ablation_build(void) {

@@ -30,6 +30,32 @@ void mpreid_set_error(const char *fmt, ...);
         }                                                                                           \
     } while (0)
 
+// The one check of a caller's image batch (include/mpreid.h: mpreid_image_in), run by every encoder forward before its
+// first HIP runtime call.  *in receives what the kernels take BY VALUE: the caller's struct, with mean 0 / std 1 in place
+// of whatever an fp32 batch left there (those fields are read only with uint8 input).
+static inline int mpreid_check_image_in(const mpreid_image_in *img, mpreid_image_in *in) {
+    if (!img) {
+        mpreid_set_error("bad argument: the image descriptor (mpreid_image_in) is NULL");
+        return MPREID_ERR_ARG;
+    }
+    if ((img->f32_dev != nullptr) == (img->u8_hwc_dev != nullptr)) {
+        mpreid_set_error("bad argument: mpreid_image_in needs exactly one of f32_dev and u8_hwc_dev (%s are set)",
+                         img->f32_dev ? "both" : "neither");
+        return MPREID_ERR_ARG;
+    }
+    if (img->view < MPREID_VIEW_ORIGINAL || img->view > MPREID_VIEW_PSEUDO_RGB) {
+        mpreid_set_error("bad argument: mpreid_image_in.view = %d is none of MPREID_VIEW_* (0..3)", (int)img->view);
+        return MPREID_ERR_ARG;
+    }
+    *in = *img;
+    if (img->f32_dev)
+        for (int c = 0; c < 3; ++c) {
+            in->mean[c] = 0.f;
+            in->std[c] = 1.f;
+        }
+    return MPREID_OK;
+}
+
 __host__ __device__ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Timing-ablation switches (MPREID_GEMM_DBG, MPREID_ATT_DBG, MPREID_CAND_DBG, MPREID_JACCARD_DBG: kernels that skip loads,

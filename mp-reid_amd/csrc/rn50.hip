@@ -472,14 +472,18 @@ extern "C" size_t mpreid_rn50_workspace_bytes(const mpreid_rn50_cfg *cfg, int ba
     return rn50_layout(cfg, batch).total;
 }
 
-extern "C" int mpreid_rn50_forward(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights *w, const float *img,
-                                   const uint8_t *img8, const float *mean3, const float *std3, int B, float *out,
-                                   void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
+extern "C" int mpreid_rn50_forward(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights *w, const mpreid_image_in *img, int B,
+                                   float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
     int rc = rn50_check_cfg(cfg);
     if (rc) return rc;
+    mpreid_image_in in;
+    if ((rc = mpreid_check_image_in(img, &in))) return rc;
+    if (in.view != MPREID_VIEW_ORIGINAL) {
+        mpreid_set_error("the fp16 RN50 tower has no in-kernel view (view = %d): use mpreid_rn50_forward_split or "
+                         "mpreid_rn50_forward_f32, or pass a materialised view tensor", (int)in.view);
+        return MPREID_ERR_UNSUPPORTED;
+    }
     ARG_CHECK(w && out && B > 0 && w->blocks && w->stem1_w && w->stem1_b && w->kt_w && w->v_w && w->v_b && w->q_w);
-    ARG_CHECK((img != nullptr) != (img8 != nullptr));
-    ARG_CHECK(!img8 || (mean3 && std3));
     const Rn50Layout v = rn50_layout(cfg, B);
     if (!ws || ws_bytes < v.total) {
         mpreid_set_error("rn50 workspace too small: %zu < %zu", ws_bytes, v.total);
@@ -497,13 +501,13 @@ extern "C" int mpreid_rn50_forward(const mpreid_rn50_cfg *cfg, const mpreid_rn50
     {
         const int64_t threads = (int64_t)B * H * W;   // one per output pixel
         const dim3 grid((unsigned)((threads + 255) / 256));
-        if (img8)
-            hipLaunchKernelGGL(rn50_stem1_kernel<true>, grid, dim3(256), 0, stream, nullptr, img8, mean3[0], mean3[1],
-                               mean3[2], std3[0], std3[1], std3[2], w->stem1_w, w->stem1_b, cfg->width / 2, B, cfg->img_h,
-                               cfg->img_w, buf[0]);
-        else
-            hipLaunchKernelGGL(rn50_stem1_kernel<false>, grid, dim3(256), 0, stream, img, nullptr, 0.f, 0.f, 0.f, 1.f, 1.f,
-                               1.f, w->stem1_w, w->stem1_b, cfg->width / 2, B, cfg->img_h, cfg->img_w, buf[0]);
+#define MPREID_STEM1(U8)   /* (`in` holds NULL for the absent form and mean 0 / std 1 with fp32 input) */                 \
+        hipLaunchKernelGGL(rn50_stem1_kernel<U8>, grid, dim3(256), 0, stream, in.f32_dev, in.u8_hwc_dev, in.mean[0],       \
+                           in.mean[1], in.mean[2], in.std[0], in.std[1], in.std[2], w->stem1_w, w->stem1_b, cfg->width / 2, \
+                           B, cfg->img_h, cfg->img_w, buf[0])
+        if (in.u8_hwc_dev) MPREID_STEM1(true);
+        else MPREID_STEM1(false);
+#undef MPREID_STEM1
         LAUNCH_CHECK();
     }
     if ((rc = run_conv(w->stem2, buf[0], B, H, W, nullptr, 1, buf[1], zero, stream))) return rc;

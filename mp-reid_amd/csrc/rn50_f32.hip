@@ -22,25 +22,14 @@ enum { F32_LIN = 2, F32_LIN_RES = 4, F32_LIN_RELU = 5, F32_LIN_RES_RELU = 6 };  
 
 namespace {
 
-// The stem's input: fp32 [B][3][H][W] (val_transforms applied), or -- img8 != NULL -- uint8 [B][H][W][3] (what the loader has
-// after Resize) with ToTensor + Normalize of datasets/make_dataloader.py:57-61 applied on the fly, in the reference's order and
-// rounding: (x / 255 - mean) / std with two correctly rounded divisions (same bits as the host-transformed fp32 tensor).
-// view: the test-time-augmentation views of processor/processor_uniprompt_stage2.py:605-633 applied to the NORMALISED image while
-// it is read (0 original, 1 torch.flip(img, [3]), 2 pseudo-IR img.mean(dim=1) in all channels = ((c0 + c1) + c2) / 3, 3 pseudo-RGB
-// channel 0 in all channels) -- what include/mpreid.h calls MPREID_VIEW_*; same bits as the view tensor materialised on the
-// HOST (torch CPU: sum, then a true division -- the reference's CPU path); torch's DEVICE mean multiplies by a rounded 1/3 and
-// is up to one ulp apart per pseudo-IR pixel (include/mpreid.h, MPREID_VIEW_PSEUDO_IR).
-struct StemIn {
-    const float *img;
-    const uint8_t *img8;
-    float mean[3], sd[3];
-    int view;
-};
-__device__ __forceinline__ float stem_px_raw(const StemIn &in, int b, int c, int iy, int ix, int H, int W) {
-    if (in.img8) return __fdiv_rn(__fdiv_rn((float)in.img8[(((int64_t)b * H + iy) * W + ix) * 3 + c], 255.0f) - in.mean[c], in.sd[c]);
-    return in.img[(((int64_t)b * 3 + c) * H + iy) * W + ix];
+// The stem's input is the image batch of include/mpreid.h (mpreid_image_in, as mpreid_check_image_in returns it): ToTensor +
+// Normalize of uint8 input and the test-time-augmentation view are applied while the pixels are read.
+__device__ __forceinline__ float stem_px_raw(const mpreid_image_in &in, int b, int c, int iy, int ix, int H, int W) {
+    if (in.u8_hwc_dev)
+        return __fdiv_rn(__fdiv_rn((float)in.u8_hwc_dev[(((int64_t)b * H + iy) * W + ix) * 3 + c], 255.0f) - in.mean[c], in.std[c]);
+    return in.f32_dev[(((int64_t)b * 3 + c) * H + iy) * W + ix];
 }
-__device__ __forceinline__ float stem_px(const StemIn &in, int b, int c, int iy, int ix, int H, int W) {
+__device__ __forceinline__ float stem_px(const mpreid_image_in &in, int b, int c, int iy, int ix, int H, int W) {
     if (in.view == 0) return stem_px_raw(in, b, c, iy, ix, H, W);
     const int x = in.view == 1 ? W - 1 - ix : ix;
     if (in.view == 2)
@@ -49,7 +38,7 @@ __device__ __forceinline__ float stem_px(const StemIn &in, int b, int c, int iy,
 }
 
 // stem conv1 + bn1 + relu: [B][3][H][W] fp32 -> [B][H/2][W/2][cout] fp32 (stride 2, pad 1); w [cout][c][kh][kw] folded
-__global__ __launch_bounds__(256) void stem1_f32_kernel(const StemIn img, const float *__restrict__ w,
+__global__ __launch_bounds__(256) void stem1_f32_kernel(const mpreid_image_in img, const float *__restrict__ w,
                                                         const float *__restrict__ bias, int cout, int B, int H, int W,
                                                         float *__restrict__ out) {
     const int OH = H / 2, OW = W / 2;
@@ -75,7 +64,7 @@ __global__ __launch_bounds__(256) void stem1_f32_kernel(const StemIn img, const 
 // contiguous run.  Same arithmetic per output (fmaf chain over (c, kh, kw) ascending, + bias, ReLU): same bits as
 // stem1_f32_kernel, which stays for channel counts other than 32 / 16 / 8.
 template <int COUT>
-__global__ __launch_bounds__(256) void stem1_px_kernel(const StemIn img, const float *__restrict__ w,
+__global__ __launch_bounds__(256) void stem1_px_kernel(const mpreid_image_in img, const float *__restrict__ w,
                                                        const float *__restrict__ bias, int B, int H, int W,
                                                        float *__restrict__ out) {
     __shared__ float ws[27 * COUT + COUT];
@@ -144,7 +133,7 @@ __global__ __launch_bounds__(256) void stem1_px_kernel(const StemIn img, const f
     }
 }
 
-static int launch_stem1(const StemIn &img, const float *w, const float *bias, int c1, int B, int H, int W, float *out,
+static int launch_stem1(const mpreid_image_in &img, const float *w, const float *bias, int c1, int B, int H, int W, float *out,
                         hipStream_t stream) {
     const int64_t px = (int64_t)B * (H / 2) * (W / 2);
     const dim3 gp((unsigned)((px + 255) / 256));
@@ -335,21 +324,13 @@ extern "C" size_t mpreid_rn50_workspace_bytes_f32(const mpreid_rn50_cfg *cfg, in
     return layout_f32(cfg, batch).total;
 }
 
-static StemIn stem_in(const float *img, const uint8_t *img8, const float *mean, const float *sd, int view = 0) {
-    StemIn s{img, img8, {0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}, view};
-    if (img8)
-        for (int c = 0; c < 3; ++c) {
-            s.mean[c] = mean[c];
-            s.sd[c] = sd[c];
-        }
-    return s;
-}
-
-static int rn50_forward_f32_impl(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_f32 *w, const StemIn &img, int B,
-                                 float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
+extern "C" int mpreid_rn50_forward_f32(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_f32 *w, const mpreid_image_in *img, int B,
+                                       float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
     int rc = check_cfg_f32(cfg);
     if (rc) return rc;
-    ARG_CHECK(w && (img.img || img.img8) && out && B > 0 && w->blocks && w->stem1_w && w->stem1_b && w->q_w && w->k_w && w->v_w && w->c_w);
+    mpreid_image_in in;
+    if ((rc = mpreid_check_image_in(img, &in))) return rc;
+    ARG_CHECK(w && out && B > 0 && w->blocks && w->stem1_w && w->stem1_b && w->q_w && w->k_w && w->v_w && w->c_w);
     const LayoutF32 v = layout_f32(cfg, B);
     if (!ws || ws_bytes < v.total) {
         mpreid_set_error("rn50 fp32 workspace too small: %zu < %zu", ws_bytes, v.total);
@@ -363,7 +344,7 @@ static int rn50_forward_f32_impl(const mpreid_rn50_cfg *cfg, const mpreid_rn50_w
 
     // ---- stem (model/clip/model.py:128-134) ----
     int H = cfg->img_h / 2, W = cfg->img_w / 2;
-    if ((rc = launch_stem1(img, w->stem1_w, w->stem1_b, cfg->width / 2, B, cfg->img_h, cfg->img_w, buf[0], stream))) return rc;
+    if ((rc = launch_stem1(in, w->stem1_w, w->stem1_b, cfg->width / 2, B, cfg->img_h, cfg->img_w, buf[0], stream))) return rc;
     ARG_CHECK(w->stem2.taps == 9 && w->stem3.taps == 9 && w->stem2.cin % 4 == 0 && w->stem3.cin % 4 == 0);
     if ((rc = conv_f32(w->stem2, buf[0], B, H, W, 1, 0, buf[1], col, stream))) return rc;
     if ((rc = conv_f32(w->stem3, buf[1], B, H, W, 1, 0, buf[0], col, stream))) return rc;
@@ -429,26 +410,6 @@ static int rn50_forward_f32_impl(const mpreid_rn50_cfg *cfg, const mpreid_rn50_w
     hipLaunchKernelGGL(head_f32_kernel, dim3(B), dim3(256), 0, stream, mean, proj, v.E, cfg->out_dim, w->bn_scale, w->bn_shift, out);
     LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int mpreid_rn50_forward_f32(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_f32 *w, const float *img, int B,
-                                       float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
-    ARG_CHECK(img);
-    return rn50_forward_f32_impl(cfg, w, stem_in(img, nullptr, nullptr, nullptr), B, out, ws, ws_bytes, stream_);
-}
-
-extern "C" int mpreid_rn50_forward_f32_u8(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_f32 *w, const uint8_t *img_hwc,
-                                          const float *mean, const float *stdv, int B, float *out, void *ws, size_t ws_bytes,
-                                          mpreid_stream_t stream_) {
-    ARG_CHECK(img_hwc && mean && stdv);
-    return rn50_forward_f32_impl(cfg, w, stem_in(nullptr, img_hwc, mean, stdv), B, out, ws, ws_bytes, stream_);
-}
-
-extern "C" int mpreid_rn50_forward_f32_view(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_f32 *w, const float *img_f32,
-                                            const uint8_t *img_hwc, const float *mean, const float *stdv, int view, int B,
-                                            float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
-    ARG_CHECK((img_f32 != nullptr) != (img_hwc != nullptr) && (!img_hwc || (mean && stdv)) && view >= 0 && view <= 3);
-    return rn50_forward_f32_impl(cfg, w, stem_in(img_f32, img_hwc, mean, stdv, view), B, out, ws, ws_bytes, stream_);
 }
 
 
@@ -677,11 +638,13 @@ extern "C" size_t mpreid_rn50_workspace_bytes_split(const mpreid_rn50_cfg *cfg, 
     return layout_split(cfg, batch).total;
 }
 
-static int rn50_forward_split_impl(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_split *w, const StemIn &img, int B,
-                                   float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
+extern "C" int mpreid_rn50_forward_split(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_split *w, const mpreid_image_in *img, int B,
+                                         float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
     int rc = check_cfg_f32(cfg);
     if (rc) return rc;
-    ARG_CHECK(w && (img.img || img.img8) && out && B > 0 && w->blocks && w->f32.stem1_w && w->f32.stem1_b && w->f32.q_w && w->f32.c_w && w->k.w && w->v.w &&
+    mpreid_image_in in;
+    if ((rc = mpreid_check_image_in(img, &in))) return rc;
+    ARG_CHECK(w && out && B > 0 && w->blocks && w->f32.stem1_w && w->f32.stem1_b && w->f32.q_w && w->f32.c_w && w->k.w && w->v.w &&
               w->stem2.w && w->stem3.w);
     const LayoutSplit v = layout_split(cfg, B);
     if (!ws || ws_bytes < v.total) {
@@ -699,7 +662,7 @@ static int rn50_forward_split_impl(const mpreid_rn50_cfg *cfg, const mpreid_rn50
 
     // ---- stem on the exact fp32 path (ReLU applied by its GEMM epilogues) ----
     int H = cfg->img_h / 2, W = cfg->img_w / 2;
-    if ((rc = launch_stem1(img, wf.stem1_w, wf.stem1_b, cfg->width / 2, B, cfg->img_h, cfg->img_w, buf[0], stream))) return rc;
+    if ((rc = launch_stem1(in, wf.stem1_w, wf.stem1_b, cfg->width / 2, B, cfg->img_h, cfg->img_w, buf[0], stream))) return rc;
     // stem conv2 / conv3 (3x3 over width/2 channels): pair GEMMs like the layers' (their outputs are stored with a channel
     // stride of 128; on the exact fp32 path these two narrow layers -- N = 32 and 64 in 128-wide tiles -- cost 4.7 ms of a
     // 25 ms forward at B = 256)
@@ -837,26 +800,6 @@ static int rn50_forward_split_impl(const mpreid_rn50_cfg *cfg, const mpreid_rn50
     hipLaunchKernelGGL(head_f32_kernel, dim3(B), dim3(256), 0, stream, mean, proj, v.f.E, cfg->out_dim, wf.bn_scale, wf.bn_shift, out);
     LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int mpreid_rn50_forward_split(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_split *w, const float *img, int B,
-                                         float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
-    ARG_CHECK(img);
-    return rn50_forward_split_impl(cfg, w, stem_in(img, nullptr, nullptr, nullptr), B, out, ws, ws_bytes, stream_);
-}
-
-extern "C" int mpreid_rn50_forward_split_u8(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_split *w, const uint8_t *img_hwc,
-                                            const float *mean, const float *stdv, int B, float *out, void *ws, size_t ws_bytes,
-                                            mpreid_stream_t stream_) {
-    ARG_CHECK(img_hwc && mean && stdv);
-    return rn50_forward_split_impl(cfg, w, stem_in(nullptr, img_hwc, mean, stdv), B, out, ws, ws_bytes, stream_);
-}
-
-extern "C" int mpreid_rn50_forward_split_view(const mpreid_rn50_cfg *cfg, const mpreid_rn50_weights_split *w, const float *img_f32,
-                                              const uint8_t *img_hwc, const float *mean, const float *stdv, int view, int B,
-                                              float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
-    ARG_CHECK((img_f32 != nullptr) != (img_hwc != nullptr) && (!img_hwc || (mean && stdv)) && view >= 0 && view <= 3);
-    return rn50_forward_split_impl(cfg, w, stem_in(img_f32, img_hwc, mean, stdv, view), B, out, ws, ws_bytes, stream_);
 }
 
 // unit-test / micro-benchmark entry: ONE convolution of the split tower, every operand and output form conv_split has

@@ -1437,12 +1437,13 @@ static int attention_dispatch(const _Float16 *qkv, int B, int L, int W, int head
     return launch_attention<16, 8, true>(qkv, B, L, W, heads, out, q_tiles, stream);   // kt is 15 or 16: always EXACT
 }
 
-static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const float *img,
-                            const unsigned char *img_u8, const float *mean3, const float *std3, int view, int B,
-                            const float *cv_emb, float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
+extern "C" int mpreid_vit_forward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_image_in *img, int B,
+                                  const float *cv_emb, float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
     int rc = vit_check_cfg(cfg);
     if (rc) return rc;
-    ARG_CHECK(w && (img || img_u8) && out && B > 0 && w->layers && view >= 0 && view <= 3);
+    mpreid_image_in in;
+    if ((rc = mpreid_check_image_in(img, &in))) return rc;
+    ARG_CHECK(w && out && B > 0 && w->layers);
     const VitLayout v = vit_layout(cfg, B);
     if (!ws || ws_bytes < v.total) {
         mpreid_set_error("vit workspace too small: %zu < %zu", ws_bytes, v.total);
@@ -1478,18 +1479,18 @@ static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights 
         const int64_t threads = (int64_t)v.MPpad * (v.Kp / 8);
         const dim3 grid((unsigned)((threads + 255) / 256));
 #define MPREID_IM2COL_S(V, S)                                                                                          \
-        if (img_u8)                                                                                                    \
-            hipLaunchKernelGGL((im2col_u8_kernel<V, S>), grid, dim3(256), 0, stream, img_u8, B, cfg->img_h, cfg->img_w, \
-                               cfg->patch, cfg->stride, cfg->h_res, cfg->w_res, mean3[0], mean3[1], mean3[2], std3[0], \
-                               std3[1], std3[2], patches, v.MPpad);                                                    \
+        if (in.u8_hwc_dev)                                                                                             \
+            hipLaunchKernelGGL((im2col_u8_kernel<V, S>), grid, dim3(256), 0, stream, in.u8_hwc_dev, B, cfg->img_h,     \
+                               cfg->img_w, cfg->patch, cfg->stride, cfg->h_res, cfg->w_res, in.mean[0], in.mean[1],    \
+                               in.mean[2], in.std[0], in.std[1], in.std[2], patches, v.MPpad);                         \
         else                                                                                                           \
-            hipLaunchKernelGGL((im2col_kernel<V, S>), grid, dim3(256), 0, stream, img, B, cfg->img_h, cfg->img_w,      \
-                               cfg->patch, cfg->stride, cfg->h_res, cfg->w_res, patches, v.MPpad);
+            hipLaunchKernelGGL((im2col_kernel<V, S>), grid, dim3(256), 0, stream, in.f32_dev, B, cfg->img_h,           \
+                               cfg->img_w, cfg->patch, cfg->stride, cfg->h_res, cfg->w_res, patches, v.MPpad);
 #define MPREID_IM2COL(V)                                                                                               \
     case V:                                                                                                            \
         if (split) { MPREID_IM2COL_S(V, true) } else { MPREID_IM2COL_S(V, false) }                                     \
         break;
-        switch (view) {
+        switch (in.view) {
             MPREID_IM2COL(0) MPREID_IM2COL(1) MPREID_IM2COL(2) MPREID_IM2COL(3)
         }
 #undef MPREID_IM2COL
@@ -1595,20 +1596,15 @@ int mpreid_gemm_f32_linear(const float *A, const float *Wt, int64_t M, int64_t N
                            int64_t ldc, int epi, hipStream_t stream);
 enum { F32_LIN = 2, F32_LIN_GELU = 3, F32_LIN_RES = 4 };   // distance.hip: EPI_LIN*
 
-// img [B][3][H][W] fp32 (or img8 [B][H][W][3] uint8 with ToTensor + Normalize applied on the fly, as in im2col_u8_kernel)
-// -> patches [B*P][3*p*p] fp32, inner order (c, kh, kw); view = the test-time-augmentation views of im2col_kernel (run-time
-// here: the all-fp32 mode is the parity / debugging mode, not a throughput path)
-struct F32In {
-    const float *img;
-    const unsigned char *img8;
-    float mean[3], sd[3];
-    int view;
-};
-__device__ __forceinline__ float f32in_px(const F32In &in, int b, int c, int y, int x, int H, int Wd) {
-    if (in.img8) return __fdiv_rn(__fdiv_rn((float)in.img8[(((int64_t)b * H + y) * Wd + x) * 3 + c], 255.0f) - in.mean[c], in.sd[c]);
-    return in.img[(((int64_t)b * 3 + c) * H + y) * Wd + x];
+// the image batch (include/mpreid.h: mpreid_image_in, as mpreid_check_image_in returns it) -> patches [B*P][3*p*p] fp32, inner
+// order (c, kh, kw); view = the test-time-augmentation views of im2col_kernel (run-time here: the all-fp32 mode is the parity /
+// debugging mode, not a throughput path)
+__device__ __forceinline__ float f32in_px(const mpreid_image_in &in, int b, int c, int y, int x, int H, int Wd) {
+    if (in.u8_hwc_dev)
+        return __fdiv_rn(__fdiv_rn((float)in.u8_hwc_dev[(((int64_t)b * H + y) * Wd + x) * 3 + c], 255.0f) - in.mean[c], in.std[c]);
+    return in.f32_dev[(((int64_t)b * 3 + c) * H + y) * Wd + x];
 }
-__global__ __launch_bounds__(256) void im2col_f32_kernel(const F32In in, int B, int H, int Wd, int p, int stride,
+__global__ __launch_bounds__(256) void im2col_f32_kernel(const mpreid_image_in in, int B, int H, int Wd, int p, int stride,
                                                          int h_res, int w_res, float *__restrict__ out) {
     const int Kp = 3 * p * p, P = h_res * w_res;
     const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1759,11 +1755,13 @@ extern "C" size_t mpreid_vit_workspace_bytes_f32(const mpreid_vit_cfg *cfg, int 
     return vit_layout_f32(cfg, batch).total;
 }
 
-static int vit_forward_f32_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const F32In &img, int B,
-                                const float *cv_emb, float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
+extern "C" int mpreid_vit_forward_f32(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_image_in *img, int B,
+                                      const float *cv_emb, float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
     int rc = vit_check_cfg(cfg);
     if (rc) return rc;
-    ARG_CHECK(w && (img.img || img.img8) && img.view >= 0 && img.view <= 3 && out && B > 0 && w->layers);
+    mpreid_image_in in;
+    if ((rc = mpreid_check_image_in(img, &in))) return rc;
+    ARG_CHECK(w && out && B > 0 && w->layers);
     if (cfg->width / cfg->heads != 64) {
         mpreid_set_error("fp32 attention: head dimension %d != 64", cfg->width / cfg->heads);
         return MPREID_ERR_UNSUPPORTED;
@@ -1780,7 +1778,7 @@ static int vit_forward_f32_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weig
     float *qkv = (float *)(base + v.qkv), *hbuf = (float *)(base + v.hbuf), *y_cls = (float *)(base + v.y_cls);
     {
         const int64_t n = (int64_t)B * v.P * v.Kp;
-        hipLaunchKernelGGL(im2col_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, img, B, cfg->img_h,
+        hipLaunchKernelGGL(im2col_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, B, cfg->img_h,
                            cfg->img_w, cfg->patch, cfg->stride, cfg->h_res, cfg->w_res, patches);
         LAUNCH_CHECK();
         if ((rc = mpreid_gemm_f32_linear(patches, (const float *)w->conv_w, (int64_t)B * v.P, W, v.Kp, nullptr, a, W, F32_LIN,
@@ -1834,47 +1832,4 @@ static int vit_forward_f32_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weig
                        neck ? w->bn_proj_scale : nullptr, neck ? w->bn_proj_shift : nullptr, out);
     LAUNCH_CHECK();
     return MPREID_OK;
-}
-
-extern "C" int mpreid_vit_forward_f32(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const float *img, int B,
-                                      const float *cv_emb, float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
-    ARG_CHECK(img);
-    const F32In in{img, nullptr, {0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}, 0};
-    return vit_forward_f32_impl(cfg, w, in, B, cv_emb, out, ws, ws_bytes, stream_);
-}
-
-extern "C" int mpreid_vit_forward_f32_view(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const float *img_f32,
-                                           const uint8_t *img_u8, const float *mean, const float *stdv, int view, int B,
-                                           const float *cv_emb, float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
-    ARG_CHECK((img_f32 != nullptr) != (img_u8 != nullptr) && (!img_u8 || (mean && stdv)));
-    F32In in{img_f32, img_u8, {0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}, view};
-    if (img_u8)
-        for (int c = 0; c < 3; ++c) {
-            in.mean[c] = mean[c];
-            in.sd[c] = stdv[c];
-        }
-    return vit_forward_f32_impl(cfg, w, in, B, cv_emb, out, ws, ws_bytes, stream_);
-}
-
-extern "C" int mpreid_vit_forward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const float *img, int B,
-                                  const float *cv_emb, float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream) {
-    ARG_CHECK(img);
-    return vit_forward_impl(cfg, w, img, nullptr, nullptr, nullptr, 0, B, cv_emb, out, ws, ws_bytes, stream);
-}
-
-extern "C" int mpreid_vit_forward_u8(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const uint8_t *img_hwc,
-                                     const float *pixel_mean3, const float *pixel_std3, int B, const float *cv_emb,
-                                     float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream) {
-    ARG_CHECK(img_hwc && pixel_mean3 && pixel_std3);
-    return vit_forward_impl(cfg, w, nullptr, img_hwc, pixel_mean3, pixel_std3, 0, B, cv_emb, out, ws, ws_bytes, stream);
-}
-
-extern "C" int mpreid_vit_forward_view(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const float *img_f32,
-                                       const uint8_t *img_hwc_u8, const float *pixel_mean3, const float *pixel_std3,
-                                       int view, int B, const float *cv_emb, float *out, void *ws, size_t ws_bytes,
-                                       mpreid_stream_t stream) {
-    ARG_CHECK((img_f32 != nullptr) != (img_hwc_u8 != nullptr));
-    ARG_CHECK(!img_hwc_u8 || (pixel_mean3 && pixel_std3));
-    return vit_forward_impl(cfg, w, img_f32, img_hwc_u8, pixel_mean3, pixel_std3, view, B, cv_emb, out, ws, ws_bytes,
-                            stream);
 }

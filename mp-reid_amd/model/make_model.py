@@ -153,7 +153,7 @@ class build_transformer(nn.Module):
             x = _ops.resize_bilinear_u8(x, self.img_hw)
         if self.model_name == 'RN50':
             if view != 0 and self.precision in ("split", "fp32"):
-                # (round 5) the view transform happens inside the stem's first convolution (mpreid_rn50_forward_*_view)
+                # (round 5) the view transform happens inside the stem's first convolution (mpreid_image_in.view)
                 return enc.forward_view(x, view, None, self.pixel_mean, self.pixel_std)
             if view != 0:
                 # the fp16 throughput tower: the view tensor is materialised on the device the way the reference does it

@@ -21,29 +21,6 @@ ERR_ARG, ERR_UNSUPPORTED = -1, -3
 RANK_TOPK_MAX = 1024   # MPREID_RANK_TOPK_MAX
 PAIR_BOUNDS_MAX = 4096   # MPREID_PAIR_BOUNDS_MAX
 
-#: every symbol include/mpreid.h declares (tests check the library exports all of them)
-SYMBOLS = [
-    "mpreid_version", "mpreid_is_ablation_build", "mpreid_last_error", "mpreid_device_count", "mpreid_device_info",
-    "mpreid_sqnorm_f32", "mpreid_l2_normalize_f32", "mpreid_distance_workspace_bytes",
-    "mpreid_euclidean_distance_f32", "mpreid_cosine_similarity_f32",
-    "mpreid_rerank_workspace_bytes", "mpreid_rerank_f32", "mpreid_rerank_debug_copy",
-    "mpreid_rerank_workspace_bytes_ex", "mpreid_rerank_f32_ex", "mpreid_rerank_debug_copy_ex", "mpreid_rerank_fits",
-    "mpreid_eval_rank_positions", "mpreid_eval_rank_positions_cam", "mpreid_eval_rank_positions_splits", "mpreid_rank_topk", "mpreid_qe_aggregate_f32", "mpreid_pair_bucket_counts", "mpreid_rr_dist_rows", "mpreid_rr_vcap", "mpreid_rr_krecip", "mpreid_rr_krecip_scratch_bytes",
-    "mpreid_rr_sparse_workspace_bytes", "mpreid_rr_neighbours_sparse", "mpreid_rr_krecip_sparse", "mpreid_rr_pack_rows", "mpreid_rr_rowptr", "mpreid_rr_ell_to_csr", "mpreid_rr_csr_to_ell", "mpreid_rr_qe_count",
-    "mpreid_rr_qe_fill", "mpreid_rr_jaccard", "mpreid_rr_jaccard_hist_bytes",
-    "mpreid_rr_csc_chunks", "mpreid_rr_csc_count", "mpreid_rr_csc_fill", "mpreid_rr_jaccard_indexed",
-    "mpreid_vit_workspace_bytes", "mpreid_vit_forward", "mpreid_vit_forward_u8", "mpreid_vit_forward_view",
-    "mpreid_vit_workspace_bytes_f32", "mpreid_vit_forward_f32", "mpreid_vit_forward_f32_view",
-    "mpreid_tta_mean_f32", "mpreid_resize_workspace_bytes", "mpreid_resize_bilinear_u8", "mpreid_conv_f16_nhwc",
-    "mpreid_rn50_conv_split_layer",
-    "mpreid_rn50_workspace_bytes", "mpreid_rn50_forward", "mpreid_rn50_workspace_bytes_f32", "mpreid_rn50_forward_f32",
-    "mpreid_rn50_workspace_bytes_split", "mpreid_rn50_forward_split", "mpreid_rn50_forward_f32_u8", "mpreid_rn50_forward_split_u8",
-    "mpreid_rn50_forward_f32_view", "mpreid_rn50_forward_split_view",
-    "mpreid_gemm_f16_nt", "mpreid_gemm_f16_nt_ex", "mpreid_gemm_f16_split_nt", "mpreid_split_pack_f32",
-    "mpreid_cast_f32_to_f16", "mpreid_profile_enable", "mpreid_profile_reset", "mpreid_profile_query",
-]
-
-
 class RerankStats(C.Structure):
     _fields_ = [("n", C.c_int64), ("k1", C.c_int32), ("k2", C.c_int32), ("half_k1", C.c_int32),
                 ("v_cap", C.c_int32), ("vqe_cap", C.c_int32), ("v_nnz", C.c_int64), ("vqe_nnz", C.c_int64),
@@ -72,6 +49,12 @@ class VitWeights(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("conv_w", "class_emb", "pos_emb", "ln_pre_g", "ln_pre_b", "ln_post_g",
                                           "ln_post_b", "proj", "bn_scale", "bn_shift", "bn_proj_scale",
                                           "bn_proj_shift")] + [("layers", C.POINTER(VitLayer)), ("conv_s", C.c_float)]
+
+
+class ImageIn(C.Structure):
+    """mpreid_image_in: the image batch of every encoder forward; exactly one of the two pointers is non-NULL"""
+    _fields_ = [("f32_dev", C.c_void_p), ("u8_hwc_dev", C.c_void_p), ("mean", C.c_float * 3), ("std", C.c_float * 3),
+                ("view", C.c_int32)]
 
 
 class Rn50Conv(C.Structure):
@@ -136,6 +119,85 @@ GEMM_EPILOGUE_NAMES = {0: "f32", 1: "qkv_bias_f16", 2: "bias_residual", 3: "fc_b
                        13: "split_patch_embed"}
 VIT_F16, VIT_SPLIT = 0, 1
 
+#: mpreid_version() of the library this binding was written for: signatures change under unchanged names, so no other loads
+VERSION = 101
+
+vp, i64, i32, f32, f64, sz, P = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_size_t, C.POINTER
+_DIST = [vp, vp, i64, i64, i32, vp, i64, i32, vp, sz, vp]
+_RERANK = [vp, vp, i64, i64, i32, i32, i32, f64, vp, i32, vp, i64, vp, sz, vp, P(RerankStats), i32]
+_CSR = [vp, vp, vp, i64, i32, vp, vp, vp]
+#: every function include/mpreid.h declares, once: name -> (restype, argtypes); load() applies it
+PROTOTYPES = {
+    "mpreid_version": (i32, []),
+    "mpreid_is_ablation_build": (i32, []),
+    "mpreid_last_error": (C.c_char_p, []),
+    "mpreid_device_count": (i32, []),
+    "mpreid_device_info": (i32, [C.c_char_p, i32, P(i32), P(sz)]),
+    "mpreid_sqnorm_f32": (i32, [vp, i64, i32, vp, vp]),
+    "mpreid_l2_normalize_f32": (i32, [vp, i64, i32, f32, vp, vp]),
+    "mpreid_distance_workspace_bytes": (sz, [i64, i64, i32, i32]),
+    "mpreid_euclidean_distance_f32": (i32, _DIST),
+    "mpreid_cosine_similarity_f32": (i32, _DIST),
+    "mpreid_rerank_workspace_bytes": (sz, [i64, i64, i32, i32, i32, i32]),
+    "mpreid_rerank_f32": (i32, _RERANK),
+    "mpreid_rerank_debug_copy": (i32, [vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "mpreid_rerank_workspace_bytes_ex": (sz, [i64, i64, i32, i32, i32, i32, i32]),
+    "mpreid_rerank_fits": (i32, [i64, i64, i32, i32, i32, i32, i32]),
+    "mpreid_rerank_f32_ex": (i32, _RERANK + [i32]),
+    "mpreid_rerank_debug_copy_ex": (i32, [vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, i32]),
+    "mpreid_eval_rank_positions": (i32, [vp, i64, i32, i32, vp, vp, i32, vp, vp, vp]),
+    "mpreid_eval_rank_positions_cam": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]),
+    "mpreid_eval_rank_positions_splits": (i32, [vp, i64, i64, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]),
+    "mpreid_rank_topk": (i32, [vp, i64, i32, i32, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "mpreid_qe_aggregate_f32": (i32, [vp, i64, i32, i64, vp, vp, vp, i64, i32, f32, vp, i64, vp]),
+    "mpreid_pair_bucket_counts": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "mpreid_rr_dist_rows": (i32, [vp, vp, i64, i32, i64, i64, vp, i64, vp, vp, i32, vp]),
+    "mpreid_rr_vcap": (i32, [i64, i32]),
+    "mpreid_rr_krecip_scratch_bytes": (sz, [i64]),
+    "mpreid_rr_krecip": (i32, [vp, i64, i64, vp, vp, i32, i32, i64, i64, vp, vp, vp, vp, vp]),
+    "mpreid_rr_sparse_workspace_bytes": (sz, [i64, i32, i64, i32]),
+    "mpreid_rr_neighbours_sparse": (i32, [vp, vp, i64, i32, i64, i64, i32, vp, vp, vp, vp, sz, vp]),
+    "mpreid_rr_krecip_sparse": (i32, [vp, vp, i64, i32, vp, vp, vp, i32, i32, i64, i64, vp, vp, vp, vp, vp]),
+    "mpreid_rr_pack_rows": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp]),
+    "mpreid_rr_rowptr": (i32, [vp, i64, vp, vp]),
+    "mpreid_rr_ell_to_csr": (i32, _CSR),
+    "mpreid_rr_csr_to_ell": (i32, _CSR),
+    "mpreid_rr_qe_count": (i32, [i64, vp, i32, i32, i64, i64, vp, vp, i32, vp, vp]),
+    "mpreid_rr_qe_fill": (i32, [i64, vp, i32, i32, i64, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "mpreid_rr_jaccard": (i32, [i64, i64, i64, i64, vp, i64, vp, vp, vp, vp, i32, f64, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "mpreid_rr_jaccard_hist_bytes": (sz, [i64]),
+    "mpreid_rr_csc_chunks": (i32, [i64, i64]),
+    "mpreid_rr_csc_count": (i32, [i64, i64, vp, vp, i32, i64, i64, vp, vp, vp]),
+    "mpreid_rr_csc_fill": (i32, [i64, i64, vp, vp, vp, i32, i64, i64, vp, vp, vp, vp, vp, vp]),
+    "mpreid_rr_jaccard_indexed": (i32, [i64, i64, i64, i64, vp, i64, vp, vp, vp, vp, i32, f64, vp, vp, vp, vp, i64, vp]),
+    # the encoders: (cfg, weights, image batch, B, [cv_emb,] out, workspace, workspace bytes, stream)
+    "mpreid_vit_workspace_bytes": (sz, [P(VitCfg), i32]),
+    "mpreid_vit_forward": (i32, [P(VitCfg), P(VitWeights), P(ImageIn), i32, vp, vp, vp, sz, vp]),
+    "mpreid_vit_workspace_bytes_f32": (sz, [P(VitCfg), i32]),
+    "mpreid_vit_forward_f32": (i32, [P(VitCfg), P(VitWeights), P(ImageIn), i32, vp, vp, vp, sz, vp]),
+    "mpreid_tta_mean_f32": (i32, [vp, i32, i64, i32, i32, vp, vp]),
+    "mpreid_resize_workspace_bytes": (sz, [i32, i32, i32]),
+    "mpreid_resize_bilinear_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
+    "mpreid_rn50_workspace_bytes": (sz, [P(Rn50Cfg), i32]),
+    "mpreid_rn50_forward": (i32, [P(Rn50Cfg), P(Rn50Weights), P(ImageIn), i32, vp, vp, sz, vp]),
+    "mpreid_rn50_workspace_bytes_f32": (sz, [P(Rn50Cfg), i32]),
+    "mpreid_rn50_forward_f32": (i32, [P(Rn50Cfg), P(Rn50WeightsF32), P(ImageIn), i32, vp, vp, sz, vp]),
+    "mpreid_rn50_workspace_bytes_split": (sz, [P(Rn50Cfg), i32]),
+    "mpreid_rn50_forward_split": (i32, [P(Rn50Cfg), P(Rn50WeightsSplit), P(ImageIn), i32, vp, vp, sz, vp]),
+    "mpreid_conv_f16_nhwc": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp]),
+    "mpreid_rn50_conv_split_layer": (i32, [P(Rn50ConvSplit), vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp]),
+    "mpreid_gemm_f16_nt": (i32, [vp, vp, vp, i64, i64, i64, vp]),
+    "mpreid_gemm_f16_nt_ex": (i32, [vp, vp, vp, vp, i64, i64, i64, i32, vp]),
+    "mpreid_gemm_f16_split_nt": (i32, [vp, vp, vp, vp, i64, i64, i64, f32, i32, vp]),
+    "mpreid_split_pack_f32": (i32, [vp, i64, i32, f32, vp, vp]),
+    "mpreid_cast_f32_to_f16": (i32, [vp, vp, i64, vp]),
+    "mpreid_profile_enable": (i32, [i32]),
+    "mpreid_profile_reset": (i32, []),
+    "mpreid_profile_query": (i32, [P(ProfileEntry), i32]),
+}
+#: every symbol include/mpreid.h declares (tests check the library exports all of them)
+SYMBOLS = list(PROTOTYPES)
+
 _lib = None
 
 
@@ -155,159 +217,21 @@ def load():
     L = C.CDLL(LIB_PATH)
     # MPREID_LIB may point at any build of the library.  One compiled with -DMPREID_ABLATION skips work on request (wrong
     # results by design): it must say so itself, and is refused unless the caller asked for exactly that.
-    if not hasattr(L, "mpreid_is_ablation_build"):
-        raise RuntimeError(f"{LIB_PATH} does not export mpreid_is_ablation_build: a stale build; rebuild it")
-    L.mpreid_is_ablation_build.restype = C.c_int
+    for name in ("mpreid_is_ablation_build", "mpreid_version"):
+        if not hasattr(L, name):
+            raise RuntimeError(f"{LIB_PATH} does not export {name}: a stale build; rebuild it")
+        getattr(L, name).restype, getattr(L, name).argtypes = PROTOTYPES[name]
     if L.mpreid_is_ablation_build() and os.environ.get("MPREID_ALLOW_ABLATION") != "1":
         raise RuntimeError(f"{LIB_PATH} is a timing-ablation build (-DMPREID_ABLATION: wrong results by design); "
                            "set MPREID_ALLOW_ABLATION=1 to load it for a measurement")
-    vp, i64, i32, f32, f64, sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_size_t
-    L.mpreid_version.restype = i32
-    L.mpreid_last_error.restype = C.c_char_p
-    L.mpreid_device_count.restype = i32
-    L.mpreid_device_info.restype = i32
-    L.mpreid_device_info.argtypes = [C.c_char_p, i32, C.POINTER(i32), C.POINTER(sz)]
-    L.mpreid_sqnorm_f32.restype = i32
-    L.mpreid_sqnorm_f32.argtypes = [vp, i64, i32, vp, vp]
-    L.mpreid_l2_normalize_f32.restype = i32
-    L.mpreid_l2_normalize_f32.argtypes = [vp, i64, i32, f32, vp, vp]
-    L.mpreid_distance_workspace_bytes.restype = sz
-    L.mpreid_distance_workspace_bytes.argtypes = [i64, i64, i32, i32]
-    for f in (L.mpreid_euclidean_distance_f32, L.mpreid_cosine_similarity_f32):
-        f.restype = i32
-        f.argtypes = [vp, vp, i64, i64, i32, vp, i64, i32, vp, sz, vp]
-    L.mpreid_rerank_workspace_bytes.restype = sz
-    L.mpreid_rerank_workspace_bytes.argtypes = [i64, i64, i32, i32, i32, i32]
-    L.mpreid_rerank_f32.restype = i32
-    L.mpreid_rerank_f32.argtypes = [vp, vp, i64, i64, i32, i32, i32, f64, vp, i32, vp, i64, vp, sz, vp,
-                                    C.POINTER(RerankStats), i32]
-    L.mpreid_rerank_debug_copy.restype = i32
-    L.mpreid_rerank_debug_copy.argtypes = [vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp]
-    L.mpreid_rerank_workspace_bytes_ex.restype = sz
-    L.mpreid_rerank_workspace_bytes_ex.argtypes = [i64, i64, i32, i32, i32, i32, i32]
-    L.mpreid_rerank_fits.restype = i32
-    L.mpreid_rerank_fits.argtypes = [i64, i64, i32, i32, i32, i32, i32]
-    L.mpreid_rerank_f32_ex.restype = i32
-    L.mpreid_rerank_f32_ex.argtypes = [vp, vp, i64, i64, i32, i32, i32, f64, vp, i32, vp, i64, vp, sz, vp,
-                                       C.POINTER(RerankStats), i32, i32]
-    L.mpreid_rerank_debug_copy_ex.restype = i32
-    L.mpreid_rerank_debug_copy_ex.argtypes = [vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, i32]
-    L.mpreid_eval_rank_positions.restype = i32
-    L.mpreid_eval_rank_positions.argtypes = [vp, i64, i32, i32, vp, vp, i32, vp, vp, vp]
-    L.mpreid_eval_rank_positions_cam.restype = i32
-    L.mpreid_eval_rank_positions_cam.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]
-    L.mpreid_eval_rank_positions_splits.restype = i32
-    L.mpreid_eval_rank_positions_splits.argtypes = [vp, i64, i64, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
-    L.mpreid_rank_topk.restype = i32
-    L.mpreid_rank_topk.argtypes = [vp, i64, i32, i32, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
-    L.mpreid_qe_aggregate_f32.restype = i32
-    L.mpreid_qe_aggregate_f32.argtypes = [vp, i64, i32, i64, vp, vp, vp, i64, i32, f32, vp, i64, vp]
-    L.mpreid_pair_bucket_counts.restype = i32
-    L.mpreid_pair_bucket_counts.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp]
-    L.mpreid_rr_dist_rows.restype = i32
-    L.mpreid_rr_dist_rows.argtypes = [vp, vp, i64, i32, i64, i64, vp, i64, vp, vp, i32, vp]
-    L.mpreid_rr_vcap.restype = i32
-    L.mpreid_rr_vcap.argtypes = [i64, i32]
-    L.mpreid_rr_krecip_scratch_bytes.restype = sz
-    L.mpreid_rr_krecip_scratch_bytes.argtypes = [i64]
-    L.mpreid_rr_krecip.restype = i32
-    L.mpreid_rr_krecip.argtypes = [vp, i64, i64, vp, vp, i32, i32, i64, i64, vp, vp, vp, vp, vp]
-    L.mpreid_rr_sparse_workspace_bytes.restype = sz
-    L.mpreid_rr_sparse_workspace_bytes.argtypes = [i64, i32, i64, i32]
-    L.mpreid_rr_neighbours_sparse.restype = i32
-    L.mpreid_rr_neighbours_sparse.argtypes = [vp, vp, i64, i32, i64, i64, i32, vp, vp, vp, vp, sz, vp]
-    L.mpreid_rr_krecip_sparse.restype = i32
-    L.mpreid_rr_krecip_sparse.argtypes = [vp, vp, i64, i32, vp, vp, vp, i32, i32, i64, i64, vp, vp, vp, vp, vp]
-    L.mpreid_rr_pack_rows.restype = i32
-    L.mpreid_rr_pack_rows.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
-    L.mpreid_rr_rowptr.restype = i32
-    L.mpreid_rr_rowptr.argtypes = [vp, i64, vp, vp]
-    for f in (L.mpreid_rr_ell_to_csr, L.mpreid_rr_csr_to_ell):
-        f.restype = i32
-        f.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp]
-    L.mpreid_rr_qe_count.restype = i32
-    L.mpreid_rr_qe_count.argtypes = [i64, vp, i32, i32, i64, i64, vp, vp, i32, vp, vp]
-    L.mpreid_rr_qe_fill.restype = i32
-    L.mpreid_rr_qe_fill.argtypes = [i64, vp, i32, i32, i64, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp]
-    L.mpreid_rr_jaccard.restype = i32
-    L.mpreid_rr_jaccard.argtypes = [i64, i64, i64, i64, vp, i64, vp, vp, vp, vp, i32, f64, vp, vp, vp, vp, vp, vp, i64, vp]
-    L.mpreid_rr_jaccard_hist_bytes.restype = sz
-    L.mpreid_rr_jaccard_hist_bytes.argtypes = [i64]
-    L.mpreid_rr_csc_chunks.restype = i32
-    L.mpreid_rr_csc_chunks.argtypes = [i64, i64]
-    L.mpreid_rr_csc_count.restype = i32
-    L.mpreid_rr_csc_count.argtypes = [i64, i64, vp, vp, i32, i64, i64, vp, vp, vp]
-    L.mpreid_rr_csc_fill.restype = i32
-    L.mpreid_rr_csc_fill.argtypes = [i64, i64, vp, vp, vp, i32, i64, i64, vp, vp, vp, vp, vp, vp]
-    L.mpreid_rr_jaccard_indexed.restype = i32
-    L.mpreid_rr_jaccard_indexed.argtypes = [i64, i64, i64, i64, vp, i64, vp, vp, vp, vp, i32, f64, vp, vp, vp, vp, i64, vp]
-    L.mpreid_vit_workspace_bytes.restype = sz
-    L.mpreid_vit_workspace_bytes.argtypes = [C.POINTER(VitCfg), i32]
-    L.mpreid_vit_forward.restype = i32
-    L.mpreid_vit_forward.argtypes = [C.POINTER(VitCfg), C.POINTER(VitWeights), vp, i32, vp, vp, vp, sz, vp]
-    L.mpreid_vit_workspace_bytes_f32.restype = sz
-    L.mpreid_vit_workspace_bytes_f32.argtypes = [C.POINTER(VitCfg), i32]
-    L.mpreid_vit_forward_f32.restype = i32
-    L.mpreid_vit_forward_f32.argtypes = [C.POINTER(VitCfg), C.POINTER(VitWeights), vp, i32, vp, vp, vp, sz, vp]
-    L.mpreid_vit_forward_f32_view.restype = i32
-    L.mpreid_vit_forward_f32_view.argtypes = [C.POINTER(VitCfg), C.POINTER(VitWeights), vp, vp, C.POINTER(C.c_float),
-                                              C.POINTER(C.c_float), i32, i32, vp, vp, vp, sz, vp]
-    L.mpreid_vit_forward_u8.restype = i32
-    L.mpreid_vit_forward_u8.argtypes = [C.POINTER(VitCfg), C.POINTER(VitWeights), vp, C.POINTER(C.c_float),
-                                        C.POINTER(C.c_float), i32, vp, vp, vp, sz, vp]
-    L.mpreid_vit_forward_view.restype = i32
-    L.mpreid_vit_forward_view.argtypes = [C.POINTER(VitCfg), C.POINTER(VitWeights), vp, vp, C.POINTER(C.c_float),
-                                          C.POINTER(C.c_float), i32, i32, vp, vp, vp, sz, vp]
-    L.mpreid_tta_mean_f32.restype = i32
-    L.mpreid_tta_mean_f32.argtypes = [vp, i32, i64, i32, i32, vp, vp]
-    L.mpreid_resize_workspace_bytes.restype = sz
-    L.mpreid_resize_workspace_bytes.argtypes = [i32, i32, i32]
-    L.mpreid_resize_bilinear_u8.restype = i32
-    L.mpreid_resize_bilinear_u8.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]
-    L.mpreid_rn50_workspace_bytes.restype = sz
-    L.mpreid_rn50_workspace_bytes.argtypes = [C.POINTER(Rn50Cfg), i32]
-    L.mpreid_rn50_forward.restype = i32
-    L.mpreid_rn50_forward.argtypes = [C.POINTER(Rn50Cfg), C.POINTER(Rn50Weights), vp, vp, C.POINTER(C.c_float),
-                                      C.POINTER(C.c_float), i32, vp, vp, sz, vp]
-    L.mpreid_rn50_workspace_bytes_f32.restype = sz
-    L.mpreid_rn50_workspace_bytes_f32.argtypes = [C.POINTER(Rn50Cfg), i32]
-    L.mpreid_rn50_forward_f32.restype = i32
-    L.mpreid_rn50_forward_f32.argtypes = [C.POINTER(Rn50Cfg), C.POINTER(Rn50WeightsF32), vp, i32, vp, vp, sz, vp]
-    L.mpreid_rn50_workspace_bytes_split.restype = sz
-    L.mpreid_rn50_workspace_bytes_split.argtypes = [C.POINTER(Rn50Cfg), i32]
-    L.mpreid_rn50_forward_split.restype = i32
-    L.mpreid_rn50_forward_split.argtypes = [C.POINTER(Rn50Cfg), C.POINTER(Rn50WeightsSplit), vp, i32, vp, vp, sz, vp]
-    L.mpreid_rn50_forward_f32_u8.restype = i32
-    L.mpreid_rn50_forward_f32_u8.argtypes = [C.POINTER(Rn50Cfg), C.POINTER(Rn50WeightsF32), vp, C.POINTER(C.c_float),
-                                             C.POINTER(C.c_float), i32, vp, vp, sz, vp]
-    L.mpreid_rn50_forward_split_u8.restype = i32
-    L.mpreid_rn50_forward_split_u8.argtypes = [C.POINTER(Rn50Cfg), C.POINTER(Rn50WeightsSplit), vp, C.POINTER(C.c_float),
-                                               C.POINTER(C.c_float), i32, vp, vp, sz, vp]
-    L.mpreid_rn50_forward_f32_view.restype = i32
-    L.mpreid_rn50_forward_f32_view.argtypes = [C.POINTER(Rn50Cfg), C.POINTER(Rn50WeightsF32), vp, vp, C.POINTER(C.c_float),
-                                               C.POINTER(C.c_float), i32, i32, vp, vp, sz, vp]
-    L.mpreid_rn50_forward_split_view.restype = i32
-    L.mpreid_rn50_forward_split_view.argtypes = [C.POINTER(Rn50Cfg), C.POINTER(Rn50WeightsSplit), vp, vp, C.POINTER(C.c_float),
-                                                 C.POINTER(C.c_float), i32, i32, vp, vp, sz, vp]
-    L.mpreid_conv_f16_nhwc.restype = i32
-    L.mpreid_conv_f16_nhwc.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp]
-    L.mpreid_rn50_conv_split_layer.restype = i32
-    L.mpreid_rn50_conv_split_layer.argtypes = [C.POINTER(Rn50ConvSplit), vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp]
-    L.mpreid_gemm_f16_nt.restype = i32
-    L.mpreid_gemm_f16_nt.argtypes = [vp, vp, vp, i64, i64, i64, vp]
-    L.mpreid_gemm_f16_nt_ex.restype = i32
-    L.mpreid_gemm_f16_nt_ex.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, vp]
-    L.mpreid_gemm_f16_split_nt.restype = i32
-    L.mpreid_gemm_f16_split_nt.argtypes = [vp, vp, vp, vp, i64, i64, i64, f32, i32, vp]
-    L.mpreid_split_pack_f32.restype = i32
-    L.mpreid_split_pack_f32.argtypes = [vp, i64, i32, f32, vp, vp]
-    L.mpreid_cast_f32_to_f16.restype = i32
-    L.mpreid_cast_f32_to_f16.argtypes = [vp, vp, i64, vp]
-    L.mpreid_profile_enable.restype = i32
-    L.mpreid_profile_enable.argtypes = [i32]
-    L.mpreid_profile_reset.restype = i32
-    L.mpreid_profile_query.restype = i32
-    L.mpreid_profile_query.argtypes = [C.POINTER(ProfileEntry), i32]
+    # the prototypes below are those of ONE version of include/mpreid.h: a library of another version may export the same
+    # names with other arguments
+    if L.mpreid_version() != VERSION:
+        raise RuntimeError(f"{LIB_PATH} reports version {L.mpreid_version()}, this binding is written for {VERSION}: "
+                           "a stale build; rebuild it")
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 

@@ -628,6 +628,55 @@ def resize_bilinear_u8(images, out_hw) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------------------------
+# The image batch of every encoder forward (include/mpreid.h: mpreid_image_in)
+# ----------------------------------------------------------------------------------------------
+#: (encoder, precision) -> (forward, workspace query, weights attribute, workspace-tag suffix, images per call).  The towers with
+#: fp32 activations (and, RN50 fp32, an im2col matrix) take 4x-36x the bytes per image and run in chunks; None = the whole batch
+_TOWERS = {
+    ("vit", "fp16"): ("mpreid_vit_forward", "mpreid_vit_workspace_bytes", "c_w", "", None),
+    ("vit", "split"): ("mpreid_vit_forward", "mpreid_vit_workspace_bytes", "c_w", "", None),
+    ("vit", "fp32"): ("mpreid_vit_forward_f32", "mpreid_vit_workspace_bytes_f32", "c_w", "_f32", 64),
+    ("rn50", "fp16"): ("mpreid_rn50_forward", "mpreid_rn50_workspace_bytes", "c_w", "", None),
+    ("rn50", "split"): ("mpreid_rn50_forward_split", "mpreid_rn50_workspace_bytes_split", "c_ws", "_split", 256),
+    ("rn50", "fp32"): ("mpreid_rn50_forward_f32", "mpreid_rn50_workspace_bytes_f32", "c_w", "_f32", 64),
+}
+
+
+@torch.no_grad()
+def _forward_images(enc, img, u8: bool, view: int = 0, cv_emb=None, pixel_mean=(0.5, 0.5, 0.5), pixel_std=(0.5, 0.5, 0.5),
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The one path from an image batch to a tower: img is fp32 [B,3,H,W] (val_transforms applied) or, u8, uint8 [B,H,W,3]
+    (after Resize; ToTensor + Normalize with pixel_mean / pixel_std and the view run inside the tower's first kernel).
+    cv_emb: None or [B, width] (ViT only).  Validates, stages on enc's device, runs the tower chunk by chunk into out."""
+    L = _lib.load()
+    fwd, ws_query, weights, tag, step = _TOWERS[enc.tower, enc.precision]
+    if u8:
+        img = img.detach().to(device=enc.device, dtype=torch.uint8).contiguous()
+        assert tuple(img.shape[1:]) == enc.img_hw + (3,), img.shape
+    else:
+        img = _dev_f32(img, enc.device)
+        assert tuple(img.shape[1:]) == (3,) + enc.img_hw, img.shape
+    B = img.shape[0]
+    cv = None
+    if cv_emb is not None:
+        cv = _dev_f32(cv_emb, enc.device)
+        assert tuple(cv.shape) == (B, enc.cfg["width"]), cv.shape
+    if out is None:
+        out = torch.empty((B, enc.feat_dim), dtype=torch.float32, device=enc.device)
+    assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, enc.feat_dim)
+    desc = _lib.ImageIn(mean=(C.c_float * 3)(*[float(x) for x in pixel_mean]),
+                        std=(C.c_float * 3)(*[float(x) for x in pixel_std]), view=int(view))
+    for s in range(0, B, step) if step else (0,):
+        n = min(B, s + step) - s if step else B
+        ws = _workspace(enc.ws_tag + tag, getattr(L, ws_query)(C.byref(enc.c_cfg), n), enc.device)
+        desc.f32_dev, desc.u8_hwc_dev = (None, img[s:].data_ptr()) if u8 else (img[s:].data_ptr(), None)
+        cv_arg = [_ptr(None if cv is None else cv[s:s + n])] if enc.tower == "vit" else []
+        _lib.check(getattr(L, fwd)(C.byref(enc.c_cfg), C.byref(getattr(enc, weights)), C.byref(desc), n, *cv_arg, _ptr(out[s:]),
+                                   _ptr(ws), ws.numel(), _lib.stream_ptr()), fwd)
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # ViT image encoder
 # ----------------------------------------------------------------------------------------------
 class VitEncoder:
@@ -647,6 +696,7 @@ class VitEncoder:
         relative feature error ~4e-4: misses the bound on hard data); 'fp32' = every weight and activation fp32, exact
         fp32 matrix instruction (~1e-6, ~1/8 of the fp16 throughput; mpreid_vit_forward_f32)."""
         assert precision in ("fp16", "fp32", "split"), precision
+        self.tower = "vit"
         if ln_fold:
             raise ValueError("ln_fold: the folded-LayerNorm form of the split mode was removed in round 4 (0.5 % slower than the plain "
                              "split mode and not reproducible run to run at small batches: include/mpreid.h)")
@@ -736,118 +786,24 @@ class VitEncoder:
         self.c_w.layers = C.cast(layers, C.POINTER(_lib.VitLayer))
         self.feat_dim = w + cfg["out_dim"]
 
-    @torch.no_grad()
     def forward(self, img: torch.Tensor, cv_emb: Optional[torch.Tensor] = None,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        L = _lib.load()
-        img = _dev_f32(img, self.device)
-        B = img.shape[0]
-        assert tuple(img.shape[1:]) == (3,) + self.img_hw, img.shape
-        cv = None
-        if cv_emb is not None:
-            cv = _dev_f32(cv_emb, self.device)
-            assert tuple(cv.shape) == (B, self.cfg["width"])
-        if out is None:
-            out = torch.empty((B, self.feat_dim), dtype=torch.float32, device=self.device)
-        assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, self.feat_dim)
-        if self.precision == "fp32":
-            step = 64   # fp32 activations: 4x the bytes per token
-            for s in range(0, B, step):
-                e = min(B, s + step)
-                ws = _workspace(self.ws_tag + "_f32", L.mpreid_vit_workspace_bytes_f32(C.byref(self.c_cfg), e - s), self.device)
-                _lib.check(L.mpreid_vit_forward_f32(C.byref(self.c_cfg), C.byref(self.c_w), _ptr(img[s:e]), e - s,
-                                                    _ptr(None if cv is None else cv[s:e].contiguous()), _ptr(out[s:e]), _ptr(ws),
-                                                    ws.numel(), _lib.stream_ptr()), "mpreid_vit_forward_f32")
-            return out
-        wsb = L.mpreid_vit_workspace_bytes(C.byref(self.c_cfg), B)
-        ws = _workspace(self.ws_tag, wsb, self.device)
-        _lib.check(L.mpreid_vit_forward(C.byref(self.c_cfg), C.byref(self.c_w), _ptr(img), B, _ptr(cv), _ptr(out),
-                                        _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_vit_forward")
-        return out
+        return _forward_images(self, img, False, cv_emb=cv_emb, out=out)
 
     __call__ = forward
 
-    def _forward_f32_view(self, img, view, cv_emb, pixel_mean, pixel_std, out):
-        """the all-fp32 mode on fp32 [B,3,H,W] or uint8 [B,H,W,3] input, one view: ToTensor + Normalize and the view transform
-        inside the patch gather (mpreid_vit_forward_f32_view)"""
-        L = _lib.load()
-        u8 = img.dtype == torch.uint8
-        if u8:
-            img = img.detach().to(device=self.device).contiguous()
-            assert tuple(img.shape[1:]) == self.img_hw + (3,), img.shape
-        else:
-            img = _dev_f32(img, self.device)
-            assert tuple(img.shape[1:]) == (3,) + self.img_hw, img.shape
-        B = img.shape[0]
-        cv = None
-        if cv_emb is not None:
-            cv = _dev_f32(cv_emb, self.device)
-            assert tuple(cv.shape) == (B, self.cfg["width"])
-        if out is None:
-            out = torch.empty((B, self.feat_dim), dtype=torch.float32, device=self.device)
-        assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, self.feat_dim)
-        mean = (C.c_float * 3)(*[float(x) for x in pixel_mean])
-        std = (C.c_float * 3)(*[float(x) for x in pixel_std])
-        step = 64   # fp32 activations: 4x the bytes per token
-        for s in range(0, B, step):
-            e = min(B, s + step)
-            ws = _workspace(self.ws_tag + "_f32", L.mpreid_vit_workspace_bytes_f32(C.byref(self.c_cfg), e - s), self.device)
-            _lib.check(L.mpreid_vit_forward_f32_view(C.byref(self.c_cfg), C.byref(self.c_w), None if u8 else _ptr(img[s:e]),
-                                                     _ptr(img[s:e]) if u8 else None, mean, std, int(view), e - s,
-                                                     _ptr(None if cv is None else cv[s:e].contiguous()), _ptr(out[s:e]), _ptr(ws),
-                                                     ws.numel(), _lib.stream_ptr()), "mpreid_vit_forward_f32_view")
-        return out
-
-    @torch.no_grad()
     def forward_u8(self, img_hwc: torch.Tensor, pixel_mean=(0.5, 0.5, 0.5), pixel_std=(0.5, 0.5, 0.5),
                    cv_emb: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """uint8 images [B, H, W, 3] (after Resize); ToTensor + Normalize run inside the patch-gather kernel."""
-        if self.precision == "fp32":
-            return self._forward_f32_view(img_hwc.to(torch.uint8), VIEW_ORIGINAL, cv_emb, pixel_mean, pixel_std, out)
-        L = _lib.load()
-        img = img_hwc.detach().to(device=self.device, dtype=torch.uint8).contiguous()
-        B = img.shape[0]
-        assert tuple(img.shape[1:]) == self.img_hw + (3,), img.shape
-        cv = None if cv_emb is None else _dev_f32(cv_emb, self.device)
-        if out is None:
-            out = torch.empty((B, self.feat_dim), dtype=torch.float32, device=self.device)
-        mean = (C.c_float * 3)(*[float(x) for x in pixel_mean])
-        std = (C.c_float * 3)(*[float(x) for x in pixel_std])
-        wsb = L.mpreid_vit_workspace_bytes(C.byref(self.c_cfg), B)
-        ws = _workspace(self.ws_tag, wsb, self.device)
-        _lib.check(L.mpreid_vit_forward_u8(C.byref(self.c_cfg), C.byref(self.c_w), _ptr(img), mean, std, B, _ptr(cv),
-                                           _ptr(out), _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_vit_forward_u8")
-        return out
+        return _forward_images(self, img_hwc, True, VIEW_ORIGINAL, cv_emb, pixel_mean, pixel_std, out)
 
-    @torch.no_grad()
     def forward_view(self, img: torch.Tensor, view: int, cv_emb: Optional[torch.Tensor] = None,
                      pixel_mean=(0.5, 0.5, 0.5), pixel_std=(0.5, 0.5, 0.5),
                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One test-time-augmentation view (VIEW_ORIGINAL / VIEW_FLIP / VIEW_PSEUDO_IR / VIEW_PSEUDO_RGB) of a batch:
         img is either fp32 [B,3,H,W] (already normalised) or uint8 [B,H,W,3].  The view transform of
-        processor/processor_uniprompt_stage2.py:605-633 happens inside the patch gather."""
-        L = _lib.load()
-        if self.precision == "fp32":   # (round 5: inside the fp32 patch gather too, no materialised view tensor)
-            return self._forward_f32_view(img, view, cv_emb, pixel_mean, pixel_std, out)
-        u8 = img.dtype == torch.uint8
-        if u8:
-            img = img.detach().to(device=self.device).contiguous()
-            assert tuple(img.shape[1:]) == self.img_hw + (3,), img.shape
-        else:
-            img = _dev_f32(img, self.device)
-            assert tuple(img.shape[1:]) == (3,) + self.img_hw, img.shape
-        B = img.shape[0]
-        cv = None if cv_emb is None else _dev_f32(cv_emb, self.device)
-        if out is None:
-            out = torch.empty((B, self.feat_dim), dtype=torch.float32, device=self.device)
-        assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, self.feat_dim)
-        mean = (C.c_float * 3)(*[float(x) for x in pixel_mean])
-        std = (C.c_float * 3)(*[float(x) for x in pixel_std])
-        ws = _workspace(self.ws_tag, L.mpreid_vit_workspace_bytes(C.byref(self.c_cfg), B), self.device)
-        _lib.check(L.mpreid_vit_forward_view(C.byref(self.c_cfg), C.byref(self.c_w), None if u8 else _ptr(img),
-                                             _ptr(img) if u8 else None, mean, std, int(view), B, _ptr(cv), _ptr(out),
-                                             _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_vit_forward_view")
-        return out
+        processor/processor_uniprompt_stage2.py:605-633 happens inside the patch gather (all three precisions)."""
+        return _forward_images(self, img, img.dtype == torch.uint8, view, cv_emb, pixel_mean, pixel_std, out)
 
     @torch.no_grad()
     def forward_tta(self, img: torch.Tensor, cv_emb: Optional[torch.Tensor] = None, views=(0, 1, 2, 3),
@@ -1000,6 +956,46 @@ def conv_split_layer(conv, B: int, H: int, W: int, x: Optional[torch.Tensor] = N
     return out, pair_out
 
 
+def _np_getter(state_dict):
+    """name -> numpy array of a ModifiedResNet state dict (keys optionally prefixed 'image_encoder.', numpy or torch)"""
+    def get(name):
+        for k in (name, "image_encoder." + name):
+            if k in state_dict:
+                v = state_dict[k]
+                return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        raise KeyError(name)
+    return get
+
+
+def _rn50_blocks(struct, conv, width: int, layers):
+    """The Bottlenecks of layer1..4 in order (model/clip/model.py:117-146) as a ctypes array of `struct`;
+    conv(conv name, BatchNorm name) builds one folded convolution of the tower's kind."""
+    blocks = []
+    inplanes = width
+    for li, (planes, nb, stride) in enumerate(zip((width, width * 2, width * 4, width * 8), layers, (1, 2, 2, 1)), 1):
+        for b in range(nb):
+            pre = f"layer{li}.{b}"
+            blk = struct()
+            blk.conv1, blk.conv2, blk.conv3 = (conv(f"{pre}.conv{i}", f"{pre}.bn{i}") for i in (1, 2, 3))
+            blk.stride = stride if b == 0 else 1
+            if blk.stride > 1 or inplanes != planes * 4:
+                blk.down = conv(pre + ".downsample.0", pre + ".downsample.1")
+            blocks.append(blk)
+            inplanes = planes * 4
+    return (struct * len(blocks))(*blocks)
+
+
+def _fold_necks(bn: dict):
+    """the eval BatchNorm necks (bottleneck over the pooled features, bottleneck_proj over the projected ones) as one
+    y = x * scale + shift over the concatenated feature row: float64 (scale, shift), rounded once by the caller"""
+    parts = []
+    for name in ("bottleneck", "bottleneck_proj"):
+        w_, b_, m_, v_ = (_np64(a) for a in bn[name])
+        s_ = w_ / np.sqrt(v_ + 1e-5)
+        parts.append((s_, b_ - m_ * s_))
+    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
+
 class Rn50Encoder:
     """Device-resident CLIP RN50 image encoder + the RN50 eval head of build_transformer.
 
@@ -1017,7 +1013,7 @@ class Rn50Encoder:
         k / v projections over fp16 PAIRS on the fp16 matrix cores (mpreid_rn50_forward_split: fp32-grade features -- the
         parity-grade mode that is also fast)."""
         assert precision in ("fp16", "fp32", "split"), precision
-        self.precision = precision
+        self.tower, self.precision = "rn50", precision
         self.device = dev = device or _lib.require_gpu()
         self.ws_tag, self.cfg, self.img_hw = ws_tag, dict(cfg), tuple(img_hw)
         width, layers = cfg["width"], tuple(cfg["layers"])
@@ -1026,21 +1022,16 @@ class Rn50Encoder:
             self._init_f32(cfg, state_dict, neck_after, bn, split=precision == "split")
             return
 
-        def get(name):
-            for k in (name, "image_encoder." + name):
-                if k in state_dict:
-                    v = state_dict[k]
-                    return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-            raise KeyError(name)
+        get = _np_getter(state_dict)
 
         def bn_of(prefix):
             return tuple(get(f"{prefix}.{a}") for a in ("weight", "bias", "running_mean", "running_var"))
 
         self._keep = []
 
-        def conv(cname, bname, taps):
+        def conv(cname, bname):
             w = get(cname + ".weight")
-            cout, cin = w.shape[0], w.shape[1]
+            cout, cin, taps = w.shape[0], w.shape[1], w.shape[2] * w.shape[3]
             cs_in, cs_out = _pad_to(cin, 64), _pad_to(cout, 64)
             wk, bk = fold_conv_bn(w, bn_of(bname), cin_pad=cs_in)
             if wk.shape[0] < _pad_to(cs_out, 128):  # never: fold pads cout to 128 already
@@ -1055,21 +1046,7 @@ class Rn50Encoder:
         s1w = torch.from_numpy((get("conv1.weight").astype(np.float64) * sc[:, None, None, None]).astype(np.float32)).to(dev)
         s1b = torch.from_numpy((b1 - m1 * sc).astype(np.float32)).to(dev)
         self._keep += [s1w, s1b]
-        blocks = []
-        inplanes = width
-        for li, (planes, nb, stride) in enumerate(zip((width, width * 2, width * 4, width * 8), layers, (1, 2, 2, 1)), 1):
-            for b in range(nb):
-                pre = f"layer{li}.{b}"
-                blk = _lib.Rn50Block()
-                blk.conv1 = conv(pre + ".conv1", pre + ".bn1", 1)
-                blk.conv2 = conv(pre + ".conv2", pre + ".bn2", 9)
-                blk.conv3 = conv(pre + ".conv3", pre + ".bn3", 1)
-                blk.stride = stride if b == 0 else 1
-                if blk.stride > 1 or inplanes != planes * 4:
-                    blk.down = conv(pre + ".downsample.0", pre + ".downsample.1", 1)
-                blocks.append(blk)
-                inplanes = planes * 4
-        self.c_blocks = (_lib.Rn50Block * len(blocks))(*blocks)
+        self.c_blocks = _rn50_blocks(_lib.Rn50Block, conv, width, layers)
         E, od = width * 32, cfg["out_dim"]
         self.feat_dim = E + od
 
@@ -1096,18 +1073,12 @@ class Rn50Encoder:
         scale = shift = None
         if neck_after:
             assert bn is not None
-            parts = []
-            for name in ("bottleneck", "bottleneck_proj"):
-                w_, b_, m_, v_ = (_np64(a) for a in bn[name])
-                s_ = w_ / np.sqrt(v_ + 1e-5)
-                parts.append((s_, b_ - m_ * s_))
-            scale = torch.from_numpy(np.concatenate([p[0] for p in parts]).astype(np.float32)).to(dev)
-            shift = torch.from_numpy(np.concatenate([p[1] for p in parts]).astype(np.float32)).to(dev)
+            scale, shift = (torch.from_numpy(a.astype(np.float32)).to(dev) for a in _fold_necks(bn))
             self._keep += [scale, shift]
-        self.c_cfg = _lib.Rn50Cfg(self.img_hw[0], self.img_hw[1], width, len(blocks), cfg["heads"], od)
+        self.c_cfg = _lib.Rn50Cfg(self.img_hw[0], self.img_hw[1], width, len(self.c_blocks), cfg["heads"], od)
         self.c_w = _lib.Rn50Weights()
         self.c_w.stem1_w, self.c_w.stem1_b = _ptr(s1w), _ptr(s1b)
-        self.c_w.stem2, self.c_w.stem3 = conv("conv2", "bn2", 9), conv("conv3", "bn3", 9)
+        self.c_w.stem2, self.c_w.stem3 = conv("conv2", "bn2"), conv("conv3", "bn3")
         self.c_w.blocks = C.cast(self.c_blocks, C.POINTER(_lib.Rn50Block))
         self.c_w.pos_emb = _ptr(pos)
         self.c_w.kt_w, self.c_w.v_w, self.c_w.v_b = _ptr(ktw), _ptr(vw), _ptr(vb)
@@ -1122,13 +1093,7 @@ class Rn50Encoder:
         dev = self.device
         width, layers = cfg["width"], tuple(cfg["layers"])
 
-        def get(name):
-            for k in (name, "image_encoder." + name):
-                if k in state_dict:
-                    v = state_dict[k]
-                    return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-            raise KeyError(name)
-
+        get = _np_getter(state_dict)
         self._keep = []
 
         def dev32(a):
@@ -1166,39 +1131,13 @@ class Rn50Encoder:
             return pairs_of_(w.transpose(0, 2, 3, 1).reshape(cout, kh * kw * cin), b, cin, kh * kw)
 
         s1w, s1b = fold("conv1", "bn1")
-        blocks = []
-        inplanes = width
-        for li, (planes, nb, stride) in enumerate(zip((width, width * 2, width * 4, width * 8), layers, (1, 2, 2, 1)), 1):
-            for b in range(nb):
-                pre = f"layer{li}.{b}"
-                blk = _lib.Rn50BlockF32()
-                blk.conv1, blk.conv2, blk.conv3 = conv(pre + ".conv1", pre + ".bn1"), conv(pre + ".conv2", pre + ".bn2"), \
-                    conv(pre + ".conv3", pre + ".bn3")
-                blk.stride = stride if b == 0 else 1
-                if blk.stride > 1 or inplanes != planes * 4:
-                    blk.down = conv(pre + ".downsample.0", pre + ".downsample.1")
-                blocks.append(blk)
-                inplanes = planes * 4
-        self.c_blocks = (_lib.Rn50BlockF32 * len(blocks))(*blocks)
+        self.c_blocks = _rn50_blocks(_lib.Rn50BlockF32, conv, width, layers)
         E, od = width * 32, cfg["out_dim"]
         self.feat_dim = E + od
-        self.c_cfg = _lib.Rn50Cfg(self.img_hw[0], self.img_hw[1], width, len(blocks), cfg["heads"], od)
+        self.c_cfg = _lib.Rn50Cfg(self.img_hw[0], self.img_hw[1], width, len(self.c_blocks), cfg["heads"], od)
         cw = self.c_w = _lib.Rn50WeightsF32()
         if split:
-            sblocks = []
-            inpl = width
-            for li, (planes, nb, stride) in enumerate(zip((width, width * 2, width * 4, width * 8), layers, (1, 2, 2, 1)), 1):
-                for b in range(nb):
-                    pre = f"layer{li}.{b}"
-                    sb = _lib.Rn50BlockSplit()
-                    sb.conv1, sb.conv2, sb.conv3 = conv_s(pre + ".conv1", pre + ".bn1"), conv_s(pre + ".conv2", pre + ".bn2"), \
-                        conv_s(pre + ".conv3", pre + ".bn3")
-                    sb.stride = stride if b == 0 else 1
-                    if sb.stride > 1 or inpl != planes * 4:
-                        sb.down = conv_s(pre + ".downsample.0", pre + ".downsample.1")
-                    sblocks.append(sb)
-                    inpl = planes * 4
-            self.c_sblocks = (_lib.Rn50BlockSplit * len(sblocks))(*sblocks)
+            self.c_sblocks = _rn50_blocks(_lib.Rn50BlockSplit, conv_s, width, layers)
             self.c_ws = _lib.Rn50WeightsSplit()
             cw = self.c_ws.f32
             self.c_ws.blocks = C.cast(self.c_sblocks, C.POINTER(_lib.Rn50BlockSplit))
@@ -1215,87 +1154,15 @@ class Rn50Encoder:
             setattr(cw, n + "_b", _ptr(dev32(get(f"attnpool.{n}_proj.bias"))))
         if neck_after:
             assert bn is not None
-            parts = []
-            for name in ("bottleneck", "bottleneck_proj"):
-                w_, b_, m_, v_ = (_np64(a) for a in bn[name])
-                s_ = w_ / np.sqrt(v_ + 1e-5)
-                parts.append((s_, b_ - m_ * s_))
-            cw.bn_scale = _ptr(dev32(np.concatenate([p[0] for p in parts])))
-            cw.bn_shift = _ptr(dev32(np.concatenate([p[1] for p in parts])))
+            cw.bn_scale, cw.bn_shift = (_ptr(dev32(a)) for a in _fold_necks(bn))
 
-    @torch.no_grad()
     def forward(self, img: torch.Tensor, cv_emb=None, pixel_mean=(0.5, 0.5, 0.5), pixel_std=(0.5, 0.5, 0.5),
                 out: Optional[torch.Tensor] = None, view: int = 0) -> torch.Tensor:
         """img: fp32 [B,3,H,W] (val_transforms applied) or uint8 [B,H,W,3] (after Resize).  cv_emb is ignored: the
         reference's RN50 branch has no SIE embedding (model/make_model.py:82-86).  view (split / fp32 towers): a
-        test-time-augmentation view applied inside the stem's first convolution (mpreid_rn50_forward_*_view)."""
-        L = _lib.load()
+        test-time-augmentation view applied inside the stem's first convolution."""
         assert view == 0 or self.precision in ("fp32", "split"), "the fp16 tower takes materialised view tensors"
-        if self.precision in ("fp32", "split"):
-            split = self.precision == "split"
-            u8 = img.dtype == torch.uint8    # ToTensor + Normalize inside the stem's first convolution (mpreid_rn50_forward_*_u8)
-            if u8:
-                img = img.detach().to(device=self.device).contiguous()
-                assert tuple(img.shape[1:]) == self.img_hw + (3,), img.shape
-                mean = (C.c_float * 3)(*[float(x) for x in pixel_mean])
-                std = (C.c_float * 3)(*[float(x) for x in pixel_std])
-            else:
-                img = _dev_f32(img, self.device)
-                assert tuple(img.shape[1:]) == (3,) + self.img_hw, img.shape
-            B = img.shape[0]
-            if out is None:
-                out = torch.empty((B, self.feat_dim), dtype=torch.float32, device=self.device)
-            step = 256 if split else 64    # fp32 activations and the im2col matrix: 4x-36x the bytes per image
-            for s0 in range(0, B, step):
-                e0 = min(B, s0 + step)
-                if split:
-                    ws = _workspace(self.ws_tag + "_split", L.mpreid_rn50_workspace_bytes_split(C.byref(self.c_cfg), e0 - s0), self.device)
-                    if view:
-                        _lib.check(L.mpreid_rn50_forward_split_view(C.byref(self.c_cfg), C.byref(self.c_ws), None if u8 else _ptr(img[s0:e0]),
-                                                                    _ptr(img[s0:e0]) if u8 else None, mean if u8 else None,
-                                                                    std if u8 else None, int(view), e0 - s0, _ptr(out[s0:e0]), _ptr(ws),
-                                                                    ws.numel(), _lib.stream_ptr()), "mpreid_rn50_forward_split_view")
-                    elif u8:
-                        _lib.check(L.mpreid_rn50_forward_split_u8(C.byref(self.c_cfg), C.byref(self.c_ws), _ptr(img[s0:e0]), mean, std,
-                                                                  e0 - s0, _ptr(out[s0:e0]), _ptr(ws), ws.numel(), _lib.stream_ptr()),
-                                   "mpreid_rn50_forward_split_u8")
-                    else:
-                        _lib.check(L.mpreid_rn50_forward_split(C.byref(self.c_cfg), C.byref(self.c_ws), _ptr(img[s0:e0]), e0 - s0,
-                                                               _ptr(out[s0:e0]), _ptr(ws), ws.numel(), _lib.stream_ptr()),
-                                   "mpreid_rn50_forward_split")
-                    continue
-                ws = _workspace(self.ws_tag + "_f32", L.mpreid_rn50_workspace_bytes_f32(C.byref(self.c_cfg), e0 - s0), self.device)
-                if view:
-                    _lib.check(L.mpreid_rn50_forward_f32_view(C.byref(self.c_cfg), C.byref(self.c_w), None if u8 else _ptr(img[s0:e0]),
-                                                              _ptr(img[s0:e0]) if u8 else None, mean if u8 else None, std if u8 else None,
-                                                              int(view), e0 - s0, _ptr(out[s0:e0]), _ptr(ws), ws.numel(),
-                                                              _lib.stream_ptr()), "mpreid_rn50_forward_f32_view")
-                elif u8:
-                    _lib.check(L.mpreid_rn50_forward_f32_u8(C.byref(self.c_cfg), C.byref(self.c_w), _ptr(img[s0:e0]), mean, std,
-                                                            e0 - s0, _ptr(out[s0:e0]), _ptr(ws), ws.numel(), _lib.stream_ptr()),
-                               "mpreid_rn50_forward_f32_u8")
-                else:
-                    _lib.check(L.mpreid_rn50_forward_f32(C.byref(self.c_cfg), C.byref(self.c_w), _ptr(img[s0:e0]), e0 - s0,
-                                                         _ptr(out[s0:e0]), _ptr(ws), ws.numel(), _lib.stream_ptr()),
-                               "mpreid_rn50_forward_f32")
-            return out
-        u8 = img.dtype == torch.uint8
-        if u8:
-            img = img.detach().to(device=self.device).contiguous()
-            assert tuple(img.shape[1:]) == self.img_hw + (3,), img.shape
-        else:
-            img = _dev_f32(img, self.device)
-            assert tuple(img.shape[1:]) == (3,) + self.img_hw, img.shape
-        B = img.shape[0]
-        if out is None:
-            out = torch.empty((B, self.feat_dim), dtype=torch.float32, device=self.device)
-        mean = (C.c_float * 3)(*[float(x) for x in pixel_mean])
-        std = (C.c_float * 3)(*[float(x) for x in pixel_std])
-        ws = _workspace(self.ws_tag, L.mpreid_rn50_workspace_bytes(C.byref(self.c_cfg), B), self.device)
-        _lib.check(L.mpreid_rn50_forward(C.byref(self.c_cfg), C.byref(self.c_w), None if u8 else _ptr(img),
-                                         _ptr(img) if u8 else None, mean, std, B, _ptr(out), _ptr(ws), ws.numel(),
-                                         _lib.stream_ptr()), "mpreid_rn50_forward")
-        return out
+        return _forward_images(self, img, img.dtype == torch.uint8, view, None, pixel_mean, pixel_std, out)
 
     __call__ = forward
 

@@ -166,11 +166,12 @@ def test_ablation_build_is_refused_unless_asked_for(tmp_path):
     pkg = os.path.join(ROOT, "mp-reid_amd", "mpreid")
     assert [f for f in os.listdir(pkg) if f.endswith(".so")] == ["libmpreid_hip.so"]
     src = tmp_path / "fake.c"
-    src.write_text("int mpreid_is_ablation_build(void) { return 1; }\nint mpreid_version(void) { return 100; }\n")
+    version_c = "int mpreid_version(void) { return %d; }\n" % _lib.VERSION    # (past the version guard: test below)
+    src.write_text("int mpreid_is_ablation_build(void) { return 1; }\n" + version_c)
     fake = tmp_path / "libfake_abl.so"
     subprocess.run(["gcc", "-shared", "-fPIC", "-o", str(fake), str(src)], check=True)
     stale = tmp_path / "libfake_stale.so"
-    (tmp_path / "stale.c").write_text("int mpreid_version(void) { return 100; }\n")
+    (tmp_path / "stale.c").write_text(version_c)
     subprocess.run(["gcc", "-shared", "-fPIC", "-o", str(stale), str(tmp_path / "stale.c")], check=True)
     code = ("import sys; sys.path.insert(0, %r)\nfrom mpreid import _lib\ntry:\n    _lib.load()\nexcept RuntimeError as e:\n"
             "    print('REFUSED', e)\nexcept AttributeError as e:\n    print('LOADED-PAST-GUARD')\n" % os.path.join(ROOT, "mp-reid_amd"))
@@ -182,3 +183,76 @@ def test_ablation_build_is_refused_unless_asked_for(tmp_path):
     r = subprocess.run([sys.executable, "-c", code], env=dict(env, MPREID_LIB=str(fake), MPREID_ALLOW_ABLATION="1"),
                        capture_output=True, text=True)
     assert "LOADED-PAST-GUARD" in r.stdout, r.stdout + r.stderr     # (the fake exports nothing else: the prototypes fail)
+
+
+def test_library_of_another_version_is_refused(tmp_path):
+    """the prototypes of mpreid._lib are those of ONE version of include/mpreid.h (signatures change under unchanged names):
+    load() refuses a library that reports another one, before it declares anything"""
+    import subprocess
+    import sys
+    assert _lib.load().mpreid_version() == _lib.VERSION == 101
+    (tmp_path / "old.c").write_text("int mpreid_is_ablation_build(void) { return 0; }\nint mpreid_version(void) { return 100; }\n")
+    old = tmp_path / "libfake_v100.so"
+    subprocess.run(["gcc", "-shared", "-fPIC", "-o", str(old), str(tmp_path / "old.c")], check=True)
+    code = ("import sys; sys.path.insert(0, %r)\nfrom mpreid import _lib\ntry:\n    _lib.load()\nexcept RuntimeError as e:\n"
+            "    print('REFUSED', e)\nexcept AttributeError as e:\n    print('LOADED-PAST-GUARD')\n" % os.path.join(ROOT, "mp-reid_amd"))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MPREID_LIB=str(old)), capture_output=True, text=True)
+    assert "REFUSED" in r.stdout and "version 100" in r.stdout and "stale build" in r.stdout, r.stdout + r.stderr
+
+
+def _forward_calls():
+    """every encoder forward as call(image descriptor or None) on a valid small configuration, with weights whose required
+    pointers are non-NULL dummies (nothing is dereferenced before the checks under test)"""
+    L = _lib.load()
+    dummy = ctypes.c_void_p(0x1000)
+    vit_cfg = _lib.VitCfg(64, 32, 16, 16, 4, 2, 128, 2, 2, 64, 0, 1, _lib.VIT_SPLIT)
+    vit_layers = (_lib.VitLayer * 2)()
+    vit_w = _lib.VitWeights(layers=ctypes.cast(vit_layers, ctypes.POINTER(_lib.VitLayer)))
+    rn_cfg = _lib.Rn50Cfg(64, 32, 16, 5, 8, 64)
+    rn_w = _lib.Rn50Weights(blocks=(_lib.Rn50Block * 5)())
+    rn_wf = _lib.Rn50WeightsF32(blocks=(_lib.Rn50BlockF32 * 5)())
+    rn_ws = _lib.Rn50WeightsSplit(blocks=(_lib.Rn50BlockSplit * 5)())
+    for w, names in ((rn_w, ("stem1_w", "stem1_b", "kt_w", "v_w", "v_b", "q_w")), (rn_wf, ("stem1_w", "stem1_b", "q_w", "k_w", "v_w", "c_w")),
+                     (rn_ws.f32, ("stem1_w", "stem1_b", "q_w", "c_w"))):
+        for n in names:
+            setattr(w, n, dummy)
+    for conv in (rn_ws.k, rn_ws.v, rn_ws.stem2, rn_ws.stem3):
+        conv.w = dummy
+
+    def call(fn, cfg, w, cv):
+        def run(img):
+            args = [ctypes.byref(cfg), ctypes.byref(w), None if img is None else ctypes.byref(img), 2] + cv + [dummy, None, 0, None]
+            return getattr(L, fn)(*args)
+        return run
+    return {"mpreid_vit_forward": call("mpreid_vit_forward", vit_cfg, vit_w, [None]),
+            "mpreid_vit_forward_f32": call("mpreid_vit_forward_f32", vit_cfg, vit_w, [None]),
+            "mpreid_rn50_forward": call("mpreid_rn50_forward", rn_cfg, rn_w, []),
+            "mpreid_rn50_forward_f32": call("mpreid_rn50_forward_f32", rn_cfg, rn_wf, []),
+            "mpreid_rn50_forward_split": call("mpreid_rn50_forward_split", rn_cfg, rn_ws, [])}
+
+
+@pytest.mark.parametrize("fn", ["mpreid_vit_forward", "mpreid_vit_forward_f32", "mpreid_rn50_forward", "mpreid_rn50_forward_f32",
+                                "mpreid_rn50_forward_split"])
+def test_forward_refuses_a_bad_image_descriptor_without_a_gpu(fn):
+    """the one validator of mpreid_image_in runs in every forward ahead of the first HIP runtime call: a NULL descriptor, both
+    pointers, neither pointer and a view outside 0..3 are MPREID_ERR_ARG with a message; a VALID descriptor gets past it (to
+    the workspace check, still without a device)"""
+    L = _lib.load()
+    run = _forward_calls()[fn]
+    p, q = 0x2000, 0x3000
+    bad = {"NULL descriptor": None, "both pointers": _lib.ImageIn(f32_dev=p, u8_hwc_dev=q), "neither pointer": _lib.ImageIn(),
+           "view 4": _lib.ImageIn(f32_dev=p, view=4), "view -1": _lib.ImageIn(u8_hwc_dev=q, view=-1)}
+    for what, img in bad.items():
+        assert run(img) == _lib.ERR_ARG, what
+        msg = L.mpreid_last_error().decode()
+        assert msg and ("mpreid_image_in" in msg), (what, msg)
+    for img in (_lib.ImageIn(f32_dev=p), _lib.ImageIn(u8_hwc_dev=q, view=3 if fn != "mpreid_rn50_forward" else 0)):
+        assert run(img) == -2 and "workspace too small" in L.mpreid_last_error().decode()   # MPREID_ERR_WORKSPACE
+
+
+def test_fp16_rn50_tower_refuses_a_view_and_names_the_towers_that_take_one():
+    L = _lib.load()
+    run = _forward_calls()["mpreid_rn50_forward"]
+    assert run(_lib.ImageIn(f32_dev=0x2000, view=1)) == _lib.ERR_UNSUPPORTED
+    msg = L.mpreid_last_error().decode()
+    assert "mpreid_rn50_forward_split" in msg and "mpreid_rn50_forward_f32" in msg, msg

@@ -327,7 +327,7 @@ def test_rn50_image_to_map_parity():
 @pytest.mark.parametrize("precision", ["split", "fp32"])
 def test_rn50_views_inside_the_stem_match_materialised_tensors(precision):
     """the test-time-augmentation views (processor/processor_uniprompt_stage2.py:605-633) inside the stem's first convolution
-    (mpreid_rn50_forward_split_view / _f32_view, round 5) == the view tensors the reference materialises (torch ops) through the
+    (mpreid_rn50_forward_split / _f32 with mpreid_image_in.view, round 5) == the view tensors the reference materialises (torch ops) through the
     plain entry point, bit for bit -- fp32 and uint8 input, all three views; and through make_model's _encode"""
     from mpreid import ops, synth
     rng = np.random.default_rng(3)

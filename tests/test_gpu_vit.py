@@ -275,7 +275,7 @@ def test_split_vit_uint8_and_views_match_float_path():
 
 
 def test_fp32_vit_uint8_and_views_match_materialised_tensors():
-    """the all-fp32 mode (round 5: mpreid_vit_forward_f32_view): uint8 input and all three test-time-augmentation views inside
+    """the all-fp32 mode (mpreid_vit_forward_f32): uint8 input and all three test-time-augmentation views inside
     the fp32 patch gather == the tensors the reference materialises (torch ops: ToTensor + Normalize,
     processor/processor_uniprompt_stage2.py:605-633) through the plain fp32 entry point, bit for bit; 70 images = two
     workspace chunks of 64"""
