@@ -509,6 +509,16 @@ size_t mpreid_vit_workspace_bytes(const mpreid_vit_cfg *cfg, int batch);
 int mpreid_vit_forward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_image_in *img, int batch,
                        const float *cv_emb_dev, float *out_dev, void *ws_dev, size_t ws_bytes,
                        mpreid_stream_t stream);
+/* The encoder's attention step alone, for unit tests and tools: the dispatchers mpreid_vit_forward calls, on the caller's
+ * buffers.  qkv_dev [batch * tokens][3 * width] = q | k | v per token row, head h in columns h * 64 .. h * 64 + 63 of each
+ * third, 16-byte aligned; fp32 with precision MPREID_VIT_SPLIT, fp16 with MPREID_VIT_F16.  out_dev, fp16:
+ *   MPREID_VIT_F16     [batch * tokens][width]        softmax(q k^T / 8) v
+ *   MPREID_VIT_SPLIT   [batch * tokens][2 * width]    [hi(width) | lo(width)], hi = fp16(o), lo = fp16(o - hi)
+ * q_tiles 0: every token row of every image is written; q_tiles n > 0: the first min(16 n, tokens) rows of every image
+ * (the forward's last block asks for 1: the CLS row's tile) and no other byte of out_dev.  width = 64 * heads,
+ * 2 <= tokens <= MPREID_VIT_MAX_TOKENS; anything else is MPREID_ERR_ARG before a launch. */
+int mpreid_vit_attention(const void *qkv_dev, int precision, int batch, int tokens, int width, int heads, int q_tiles,
+                         void *out_dev, mpreid_stream_t stream);
 
 /* All-fp32 mode of the same encoder (parity / debugging; SURVEY.md section 7 hard part 5): activations and weights
  * fp32, linear layers on the exact fp32 matrix instruction, attention on fp32 vector FMAs -- relative feature error

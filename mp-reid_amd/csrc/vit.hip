@@ -465,6 +465,16 @@ __device__ __forceinline__ float4 buffer_load_nt_f4(const RS &rs, unsigned voff,
     const att_f4 v = __builtin_bit_cast(att_f4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, soff, 2));
     return make_float4(v[0], v[1], v[2], v[3]);
 }
+template <typename RS>
+__device__ __forceinline__ float4 buffer_load_f4(const RS &rs, unsigned voff, int soff) {   // the same, cached as a plain load
+    const att_f4 v = __builtin_bit_cast(att_f4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, soff, 0));
+    return make_float4(v[0], v[1], v[2], v[3]);
+}
+template <typename RS>
+__device__ __forceinline__ void buffer_store_nt16(const RS &rs, unsigned voff, int soff, const uint4 &v) {
+    const att_u4 nv = {v.x, v.y, v.z, v.w};
+    __builtin_amdgcn_raw_buffer_store_b128(nv, rs, (int)voff, soff, 2);
+}
 __device__ __forceinline__ void split4(const float4 &v, h4_t &hi, h4_t &lo) {
     const float x[4] = {v.x, v.y, v.z, v.w};
     split_pairs<4>(x, hi, lo);   // (common.h: three instructions per two values)
@@ -483,10 +493,14 @@ __device__ __forceinline__ void split4(const float4 &v, h4_t &hi, h4_t &lo) {
         const int rc_ = row_ < L ? row_ : L - 1;                                                     \
         koff##i = (unsigned)(rc_ * (int)ld + c_ * 4) * 4u;                                           \
     }
+// XKEY (no row is clamped): iteration i is iteration 0 moved down by NT / 16 rows, a uniform distance that goes into the
+// scalar offset -- one lane offset register instead of K_ITERS
+#define ATS_VOFF(i) (XKEY ? koff0 : koff##i)
+#define ATS_SOFF(i) (XKEY ? i * (NT / 16) * (int)ld * 4 : 0)
 #define ATS_LOAD(i)                                                                                  \
     if constexpr (K_ITERS > i) {                                                                     \
-        k##i = buffer_load_nt_f4(prs_, koff##i, pso_);                                               \
-        v##i = buffer_load_nt_f4(prs_, koff##i, pso_ + W * 4);                                       \
+        k##i = buffer_load_nt_f4(prs_, ATS_VOFF(i), pso_ + ATS_SOFF(i));                             \
+        v##i = buffer_load_nt_f4(prs_, ATS_VOFF(i), pso_ + ATS_SOFF(i) + W * 4);                     \
     }
 #define ATS_STORE(i)                                                                                 \
     if constexpr (K_ITERS > i) {                                                                     \
@@ -504,6 +518,19 @@ __device__ __forceinline__ void split4(const float4 &v, h4_t &hi, h4_t &lo) {
             *reinterpret_cast<h4_t *>(Vl + vo_) = lo_;                                               \
         }                                                                                            \
     }
+#define ATS_LOAD_K(i)                                                                                \
+    if constexpr (K_ITERS > i) k##i = buffer_load_nt_f4(prs_, ATS_VOFF(i), pso_ + ATS_SOFF(i));
+#define ATS_LOAD_V(i)                                                                                \
+    if constexpr (K_ITERS > i) v##i = buffer_load_nt_f4(prs_, ATS_VOFF(i), pso_ + ATS_SOFF(i) + W * 4);
+// the K rows or the V rows alone (XKEY requests them at two places of the compute phase)
+#define ATS_PREFETCH_PART(pr, PART)                                                                  \
+    {                                                                                                \
+        const int pb_ = (pr) / heads, ph_ = (pr) - pb_ * heads;                                      \
+        const auto prs_ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(qkv + (int64_t)pb_ * L * ld), 0,   \
+                                                             (int)(L * (int)ld * 4), 0x00020000);   \
+        const int pso_ = (ph_ * 64 + W) * 4;                                                         \
+        ATS_FOR_EACH_ITER(PART)                                                                      \
+    }
 #define ATS_PREFETCH(pr)                                                                             \
     {                                                                                                \
         const int pb_ = (pr) / heads, ph_ = (pr) - pb_ * heads;                                      \
@@ -515,7 +542,8 @@ __device__ __forceinline__ void split4(const float4 &v, h4_t &hi, h4_t &lo) {
 
 // XKEY (L == 16 * KTP + 1, i.e. ViT-B/16 at 256 x 128: L = 129 = 8 key tiles + ONE token): the tiles cover keys 0 .. L-2
 // exactly and the last token is handled as an extra key OUTSIDE the matrix instructions -- its K / V rows sit in LDS as
-// fp32; its score is 16 fp32 FMAs per lane on the raw Q values + one cross-group sum, its P x V contribution 16 FMAs on the
+// fp32 (its Q row beside them: the tail query's operand, staged with them instead of held in registers); its score is 16
+// fp32 FMAs per lane on the raw Q values + one cross-group sum, its P x V contribution 16 FMAs on the
 // O accumulators.  Without it the one odd key costs two of ten key tiles (the PV step is 32 keys wide): 20 % of the QK
 // products, a fifth PV step, 20 % of the softmax and 16 KB of LDS -- and with 64 + 1 KB of K / V pairs instead of 80 a
 // 256-thread workgroup fits a CU TWICE, so one workgroup's loads / staging / barriers overlap the other's compute.
@@ -537,11 +565,12 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8 || XKEY) ? 2 : 1) void attention_
     constexpr int NT = 64 * NW;
     constexpr int K_ITERS = (KEYS * 16 + NT - 1) / NT;
     static_assert(K_ITERS <= 8, "extend ATS_FOR_EACH_ITER");
+    static_assert(!XKEY || KEYS * 16 == K_ITERS * NT, "ATS_SOFF: every staging iteration is whole and below row L - 1");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char *Kh = smem, *Kl = smem + KEYS * 128, *Vh = smem + 2 * KEYS * 128, *Vl = smem + 3 * KEYS * 128;
     constexpr int OS = 72;
     _Float16 *Ot = reinterpret_cast<_Float16 *>(smem + 4 * KEYS * 128);   // [NW][16][OS]
-    float *Xk = reinterpret_cast<float *>(smem + 4 * KEYS * 128 + NW * 16 * OS * 2);   // XKEY: [64] K row, [64] V row of token L-1 (fp32)
+    float *Xk = reinterpret_cast<float *>(smem + 4 * KEYS * 128 + NW * 16 * OS * 2);   // XKEY: [64] K, [64] V, [64] Q row of token L-1 (fp32)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fq = lane >> 4;
     const int64_t ld = 3 * (int64_t)W;
@@ -550,21 +579,33 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8 || XKEY) ? 2 : 1) void attention_
 
     ATS_FOR_EACH_ITER(ATS_DECL)
     ATS_FOR_EACH_ITER(ATS_OFFS)
+    // XKEY: byte offsets inside an image's slab of this lane's Q chunk in the wave's two main tiles (wave, wave + NW) and of
+    // its 16-byte piece of the wave's first output tile (row wave * 16 + (lane >> 3), chunk lane & 7)
+    unsigned xq_off[2] = {0u, 0u}, xo_off = 0u;
+    if constexpr (XKEY) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int q = (wave + t * NW) * 16 + fr;
+            xq_off[t] = (unsigned)((q < L ? q : L - 1) * (int)ld + fq * 8) * 4u;
+        }
+        xo_off = (unsigned)((wave * 16 + (lane >> 3)) * 2 * W + (lane & 7) * 8) * 2u;
+    }
 
-    float4 xrow = make_float4(0.f, 0.f, 0.f, 0.f);   // XKEY: lanes 0-15 of wave 0 hold the K row of token L-1, lanes 16-31 its V row
+    // XKEY: lanes 0-15 of wave 0 hold the K row of token L-1, lanes 16-31 its V row, lanes 32-47 its Q row (the tail query)
+    float4 xrow = make_float4(0.f, 0.f, 0.f, 0.f);
     auto x_request = [&](int pr) {
         if constexpr (XKEY) {
-            if (tid < 32) {
+            if (tid < 48) {
                 const int pb = pr / heads, ph = pr - pb * heads;
-                xrow = load_nt_f4(qkv + ((int64_t)pb * L + (L - 1)) * ld + ph * 64 + (tid < 16 ? W : 2 * W) + (tid & 15) * 4);
+                xrow = load_nt_f4(qkv + ((int64_t)pb * L + (L - 1)) * ld + ph * 64 + (tid < 16 ? W : tid < 32 ? 2 * W : 0) + (tid & 15) * 4);
             }
         }
     };
     // dbg (MPREID_ATT_DBG in an MPREID_ABLATION build; timing ablations only, wrong results): 1 no K / V loads, 2 no compute,
-    // 4 no output stores, 8 no PV, 16 no O write-out, 32 no QK products.  Round-3 ablation at B = 508, L = 129 (us per
-    // layer-batch): full 263; loads + staging only 100; compute on stale LDS 220 = QK 40 + PV 60 + O write-out 26 + the
-    // rest 102 (softmax and the P pairs ~60: ~400 VALU instructions per tile, K / V staging, two barriers per pair, the
-    // 9 tiles over 8 waves).
+    // 4 no output stores, 8 no PV, 16 no O write-out, 32 no QK products.  Ablation of <8,4,XKEY> at B = 508, L = 129 (us per
+    // launch, tools/attention_bench.py, profiles/attention_split_ablation.log) with one pass over K / V per query tile:
+    // full 210; loads + staging only 85; compute on stale LDS 134; without stores 200, PV 185, O write-out 187, QK 183.
+    // With one pass for both of a wave's tiles and the LDS reads a step ahead (xkey_tiles): full 169.
     int pair = blockIdx.x;
     if (pair >= total_pairs) return;
     if (!(dbg & 1)) {
@@ -577,7 +618,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8 || XKEY) ? 2 : 1) void attention_
         __syncthreads(); // every wave is done reading the previous pair from LDS
         ATS_FOR_EACH_ITER(ATS_STORE)
         if constexpr (XKEY) {
-            if (tid < 32) *reinterpret_cast<float4 *>(Xk + tid * 4) = xrow;
+            if (tid < 48) *reinterpret_cast<float4 *>(Xk + tid * 4) = xrow;
         }
         // Q of this wave's first query tile (B operand: B[k = d][col = query]; 8 consecutive d per lane and 32-wide k step),
         // requested BEFORE the barrier so that its round trip is hidden behind it; the next tile's Q (a wave has a second
@@ -594,14 +635,32 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8 || XKEY) ? 2 : 1) void attention_
                 qraw[2 * ks + 1] = *reinterpret_cast<const float4 *>(qp + 4);
             }
         };
-        q_request(wave < nqt ? wave : 0);
+        // XKEY: Q through the descriptor of the image's q | k | v slab and the output through one of its output slab, both with
+        // lane offsets computed once per kernel (xq_off, xo_off) and everything that changes per pair or tile in the scalar
+        // offset -- no per-lane 64-bit address arithmetic in the tile body.  A wave's two main tiles (wave, wave + NW) are
+        // requested together and computed in ONE pass over K / V (xkey_tiles below).
+        float4 qx[2][4];
+        const auto xq_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(qkv + (int64_t)b * L * ld), 0, (int)(L * (int)ld * 4),
+                                                             0x00020000);
+        const auto xo_rs = __builtin_amdgcn_make_buffer_rsrc(out + (int64_t)b * L * 2 * W, 0, (int)(L * 2 * W * 2), 0x00020000);
+        auto xq_request = [&](float4 *dst, unsigned voff) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) dst[c] = buffer_load_f4(xq_rs, voff, h * 256 + (c >> 1) * 128 + (c & 1) * 16);
+        };
+        const int x_ntq = !XKEY ? 0 : (wave + NW < (nqt == KTP + 1 ? KTP : nqt) ? 2 : (wave < nqt ? 1 : 0));
+        if constexpr (XKEY) {
+            if (x_ntq >= 1) xq_request(qx[0], xq_off[0]);
+            if (x_ntq == 2) xq_request(qx[1], xq_off[1]);
+        } else {
+            q_request(wave < nqt ? wave : 0);
+        }
         __syncthreads();
-        {
-            const int nxt = pair + (int)gridDim.x < total_pairs ? pair + (int)gridDim.x : pair;
-            if (!(dbg & 1)) {
-                ATS_PREFETCH(nxt)
-                x_request(nxt);
-            }
+        const int nxt = pair + (int)gridDim.x < total_pairs ? pair + (int)gridDim.x : pair;
+        // XKEY: the next pair's K / V are requested after the softmax of the wave's tiles (xkey_tiles), when the score
+        // registers are dead; a wave without a tile (q_tiles > 0) requests them here
+        if (!(dbg & 1) && (!XKEY || x_ntq == 0 || (dbg & 2))) {
+            ATS_PREFETCH(nxt)
+            x_request(nxt);
         }
         // XKEY, all query tiles wanted: the tiles 0 .. KTP-1 are full, tile KTP holds ONE query (token L-1).  Handed to one
         // wave as a tile of its own (round 3) that wave did three tiles per pair where the others did two, and everybody
@@ -610,6 +669,211 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8 || XKEY) ? 2 : 1) void attention_
         // (max, sum, O) leave through LDS and wave 0 merges them -- a quarter tile per wave instead of a whole one for one.
         const bool tail = XKEY && nqt == KTP + 1;
         const int nmain = tail ? KTP : nqt;
+        // XKEY: the wave's NTQ main tiles (wave, wave + NW) in ONE pass over K / V.  Every K fragment and every transposed V
+        // fragment is read from LDS once and multiplied into both tiles' accumulators: half the LDS read bytes and address
+        // arithmetic of a pass per tile, and twice as many independent accumulation chains to put between a fragment's
+        // read and its use.  Each accumulator sees the products of the single-tile form in the same order (key tile, then
+        // ks, then hi.hi' + lo.hi' + hi.lo'; PV step, then dt), the softmax is per tile as before: the bits are the same.
+        // The next pair's K (32 registers) is requested after the softmax and its V (32) after the second of the four PV
+        // steps, when half of P is consumed, instead of both before the tiles: two tiles' scores fit where one tile's did.
+        // The rest of the PV phase, the write-out, the tail query and the barrier cover their round trip.  (Requested
+        // earlier -- K at the barrier or before the softmax, V right after the softmax -- 18 to 21 registers spill.)
+        auto xkey_tiles = [&](auto ntq_) {
+            constexpr int NTQ = decltype(ntq_)::value;
+            f16x8 qh[NTQ][2], ql[NTQ][2];
+            float sx[NTQ];   // q . k of the extra key (token L-1), fp32, for this lane's query column
+#pragma unroll
+            for (int t = 0; t < NTQ; ++t) {
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    const float4 a0 = qx[t][2 * ks], a1 = qx[t][2 * ks + 1];
+                    const float qv[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+                    split_pairs<8>(qv, qh[t][ks], ql[t][ks]);
+                }
+                sx[t] = 0.f;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {   // this lane's 16 d values: ks * 32 + fq * 8 + (c & 1) * 4 .. + 3
+                    const float4 kx = *reinterpret_cast<const float4 *>(Xk + (c >> 1) * 32 + fq * 8 + (c & 1) * 4);
+                    sx[t] = fmaf(qx[t][c].x, kx.x, sx[t]);
+                    sx[t] = fmaf(qx[t][c].y, kx.y, sx[t]);
+                    sx[t] = fmaf(qx[t][c].z, kx.z, sx[t]);
+                    sx[t] = fmaf(qx[t][c].w, kx.w, sx[t]);
+                }
+                sx[t] = xor16_32_sum(sx[t]);
+            }
+            // the K fragments of step i + 1 (i = 2 kt + ks) are requested before the products of step i are issued, and the
+            // scheduler is held to that order (a group of two LDS reads, then the step's 3 NTQ matrix instructions)
+            f32x4 s[NTQ][KTP];
+            f16x8 kh[2], kl[2];
+            auto k_read = [&](int i) {
+                const int ko = ((i >> 1) * 16 + fr) * 128 + ((((i & 1) * 4 + fq) ^ (lane & 7)) << 4);
+                kh[i & 1] = *reinterpret_cast<const f16x8 *>(Kh + ko);
+                kl[i & 1] = *reinterpret_cast<const f16x8 *>(Kl + ko);
+            };
+            __builtin_amdgcn_sched_barrier(0);   // (the reads of the extra key's row above are no part of the groups below)
+            if (!(dbg & 32)) {
+                k_read(0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+            }
+#pragma unroll
+            for (int i = 0; i < 2 * KTP; ++i) {
+                const int kt = i >> 1, ks = i & 1;
+                if (ks == 0) {
+#pragma unroll
+                    for (int t = 0; t < NTQ; ++t) s[t][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+                if (!(dbg & 32)) {
+                    if (i + 1 < 2 * KTP) {
+                        k_read(i + 1);
+                        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+                    }
+#pragma unroll
+                    for (int t = 0; t < NTQ; ++t) {
+                        s[t][kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh[i & 1], qh[t][ks], s[t][kt], 0, 0, 0);
+                        s[t][kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl[i & 1], qh[t][ks], s[t][kt], 0, 0, 0);
+                        s[t][kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh[i & 1], ql[t][ks], s[t][kt], 0, 0, 0);
+                    }
+                    __builtin_amdgcn_sched_group_barrier(0x8, 3 * NTQ, 0);
+                }
+            }
+            float sum[NTQ], px[NTQ];
+#pragma unroll
+            for (int t = 0; t < NTQ; ++t) {
+                float mx = -3.0e38f;
+#pragma unroll
+                for (int kt = 0; kt < KTP; ++kt)
+                    mx = fmaxf(mx, fmaxf(fmaxf(s[t][kt][0], s[t][kt][1]), fmaxf(s[t][kt][2], s[t][kt][3])));
+                mx = xor16_32_max(mx);
+                mx = fmaxf(mx, sx[t]);
+                // p * 2^10 = exp2(s*c - mx*c + 10)
+                const float nmx = fmaf(-mx, scale_log2e, 10.0f);
+                sum[t] = 0.f;
+#pragma unroll
+                for (int kt = 0; kt < KTP; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float p = __builtin_amdgcn_exp2f(fmaf(s[t][kt][r], scale_log2e, nmx));
+                        s[t][kt][r] = p;
+                        sum[t] += p;
+                    }
+                sum[t] = xor16_32_sum(sum[t]);
+                px[t] = __builtin_amdgcn_exp2f(fmaf(sx[t], scale_log2e, nmx));
+                sum[t] += px[t];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (!(dbg & 1)) {
+                ATS_PREFETCH_PART(nxt, ATS_LOAD_K)
+                x_request(nxt);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            f32x4 o[NTQ][4];
+#pragma unroll
+            for (int t = 0; t < NTQ; ++t)
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) o[t][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            // the transposed V fragments of step j + 1 (j = 4 s2 + dt) are requested before the products of step j, like K
+            f16x8 vh[2], vl[2];
+            auto v_read = [&](int j) {
+                const int trq = fr >> 2, trp = fr & 3;
+                const int row0 = (j >> 2) * 32 + fq * 4 + trq, row1 = row0 + 16;
+                const int chunk = (j & 3) * 2 + (trp >> 1);
+                const int o0 = row0 * 128 + ((chunk ^ (((row0 >> 1) & 3) << 1)) << 4) + (trp & 1) * 8;
+                const int o1 = row1 * 128 + ((chunk ^ (((row1 >> 1) & 3) << 1)) << 4) + (trp & 1) * 8;
+                typedef short s8_t __attribute__((ext_vector_type(8)));
+                const att_s4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((att_lds_s4 *)(Vh + o0));
+                const att_s4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((att_lds_s4 *)(Vh + o1));
+                const att_s4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((att_lds_s4 *)(Vl + o0));
+                const att_s4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((att_lds_s4 *)(Vl + o1));
+                const s8_t vh8 = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+                const s8_t vl8 = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+                vh[j & 1] = __builtin_bit_cast(f16x8, vh8);
+                vl[j & 1] = __builtin_bit_cast(f16x8, vl8);
+            };
+            if (!(dbg & 8)) {
+                v_read(0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 4, 1);
+            }
+#pragma unroll
+            for (int s2 = 0; s2 < ((dbg & 8) ? 0 : KTP / 2); ++s2) {
+                f16x8 ph[NTQ], pl[NTQ];
+#pragma unroll
+                for (int t = 0; t < NTQ; ++t) {
+                    const float pv[8] = {s[t][2 * s2][0], s[t][2 * s2][1], s[t][2 * s2][2], s[t][2 * s2][3],
+                                         s[t][2 * s2 + 1][0], s[t][2 * s2 + 1][1], s[t][2 * s2 + 1][2], s[t][2 * s2 + 1][3]};
+                    split_pairs<8>(pv, ph[t], pl[t]);
+                }
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) {
+                    const int j = s2 * 4 + dt;
+                    // (the read ahead stays on this side of the V request in the middle of the PV steps: full fences there)
+                    if (j + 1 < 2 * KTP && !(dt == 3 && s2 == KTP / 4 - 1)) {
+                        v_read(j + 1);
+                        __builtin_amdgcn_sched_group_barrier(0x100, 4, 1);
+                    }
+#pragma unroll
+                    for (int t = 0; t < NTQ; ++t) {
+                        o[t][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh[j & 1], ph[t], o[t][dt], 0, 0, 0);
+                        o[t][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl[j & 1], ph[t], o[t][dt], 0, 0, 0);
+                        o[t][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh[j & 1], pl[t], o[t][dt], 0, 0, 0);
+                    }
+                    __builtin_amdgcn_sched_group_barrier(0x8, 3 * NTQ, 1);
+                }
+                if (s2 == KTP / 4 - 1) {   // half of P is consumed: its registers take the next pair's V
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (!(dbg & 1)) ATS_PREFETCH_PART(nxt, ATS_LOAD_V)
+                    __builtin_amdgcn_sched_barrier(0);
+                    v_read(4 * (s2 + 1));
+                    __builtin_amdgcn_sched_group_barrier(0x100, 4, 1);
+                }
+            }
+            if ((dbg & 8) && !(dbg & 1)) ATS_PREFETCH_PART(nxt, ATS_LOAD_V)
+#pragma unroll
+            for (int t = 0; t < NTQ; ++t) {
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) {   // + p_x * v_x: lane (query fr) owns d = dt * 16 + fq * 4 .. + 3
+                    const float4 vx = *reinterpret_cast<const float4 *>(Xk + 64 + dt * 16 + fq * 4);
+                    o[t][dt][0] = fmaf(px[t], vx.x, o[t][dt][0]);
+                    o[t][dt][1] = fmaf(px[t], vx.y, o[t][dt][1]);
+                    o[t][dt][2] = fmaf(px[t], vx.z, o[t][dt][2]);
+                    o[t][dt][3] = fmaf(px[t], vx.w, o[t][dt][3]);
+                }
+                if (!(dbg & 16)) {   // O^T -> fp16 pair, through the wave's LDS patch as whole 128-byte rows: hi part, then lo part
+                    const float inv = 1.0f / sum[t];
+                    _Float16 *ot = Ot + wave * (16 * OS);
+                    h4_t ohi[4], olo[4];
+#pragma unroll
+                    for (int dt = 0; dt < 4; ++dt) {
+                        const float ovf[4] = {o[t][dt][0] * inv, o[t][dt][1] * inv, o[t][dt][2] * inv, o[t][dt][3] * inv};
+                        split_pairs<4>(ovf, ohi[dt], olo[dt]);
+                    }
+#pragma unroll
+                    for (int part = 0; part < 2; ++part) {
+#pragma unroll
+                        for (int dt = 0; dt < 4; ++dt)
+                            *reinterpret_cast<h4_t *>(ot + fr * OS + dt * 16 + fq * 4) = part == 0 ? ohi[dt] : olo[dt];
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+                        for (int it = 0; it < 2; ++it) {
+                            const int row = it * 8 + (lane >> 3), ch = lane & 7;
+                            const uint4 v = *reinterpret_cast<const uint4 *>(ot + row * OS + ch * 8);
+                            // (rows (wave + t * NW) * 16 + it * 8 + (lane >> 3) < 16 * KTP = L - 1: every main-tile row exists)
+                            if (!(dbg & 4))
+                                buffer_store_nt16(xo_rs, xo_off, ((t * NW * 16 + it * 8) * 2 * W + part * W + h * 64) * 2, v);
+                        }
+                        __builtin_amdgcn_wave_barrier();
+                    }
+                }
+            }
+        };
+        if constexpr (XKEY) {
+            if (!(dbg & 2)) {
+                if (x_ntq == 2) xkey_tiles(std::integral_constant<int, 2>{});
+                else if (x_ntq == 1) xkey_tiles(std::integral_constant<int, 1>{});
+            }
+        }
+        if constexpr (!XKEY)
         for (int qt = wave; qt < ((dbg & 2) ? 0 : nmain); qt += NW) {
             f16x8 qh[2], ql[2];
 #pragma unroll
@@ -618,23 +882,10 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8 || XKEY) ? 2 : 1) void attention_
                 const float qv[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
                 split_pairs<8>(qv, qh[ks], ql[ks]);
             }
-            float sx = 0.f;   // XKEY: q . k of the extra key (token L-1), fp32, for this lane's query column
-            if constexpr (XKEY) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {   // this lane's 16 d values: ks * 32 + fq * 8 + (c & 1) * 4 .. + 3
-                    const float4 kx = *reinterpret_cast<const float4 *>(Xk + (c >> 1) * 32 + fq * 8 + (c & 1) * 4);
-                    sx = fmaf(qraw[c].x, kx.x, sx);
-                    sx = fmaf(qraw[c].y, kx.y, sx);
-                    sx = fmaf(qraw[c].z, kx.z, sx);
-                    sx = fmaf(qraw[c].w, kx.w, sx);
-                }
-                sx = xor16_32_sum(sx);
-            }
             if (qt + NW < nmain) q_request(qt + NW);
-            else if (tail) q_request(KTP);   // (every column of that tile clamps to token L-1: sixteen copies of the one query)
             f32x4 s[KTP];
             float mx = -3.0e38f;
-            const int nkt = XKEY ? KTP : (L + 15) >> 4;   // key tiles that hold a valid key
+            const int nkt = (L + 15) >> 4;   // key tiles that hold a valid key
 #pragma unroll
             for (int kt = 0; kt < KTP; ++kt) {
                 s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -653,15 +904,12 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8 || XKEY) ? 2 : 1) void attention_
             }
 #pragma unroll
             for (int kt = 0; kt < KTP; ++kt) {
-                if constexpr (!XKEY) {   // (XKEY: every key of the tiles is valid)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (kt * 16 + fq * 4 + r >= L) s[kt][r] = -3.0e38f;
-                }
+                for (int r = 0; r < 4; ++r)
+                    if (kt * 16 + fq * 4 + r >= L) s[kt][r] = -3.0e38f;
                 mx = fmaxf(mx, fmaxf(fmaxf(s[kt][0], s[kt][1]), fmaxf(s[kt][2], s[kt][3])));
             }
             mx = xor16_32_max(mx);
-            if constexpr (XKEY) mx = fmaxf(mx, sx);
             // p * 2^10 = exp2(s*c - mx*c + 10); masked entries give exp2(-huge) = 0
             const float nmx = fmaf(-mx, scale_log2e, 10.0f);
             float sum = 0.f;
@@ -674,11 +922,6 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8 || XKEY) ? 2 : 1) void attention_
                     sum += p;
                 }
             sum = xor16_32_sum(sum);
-            float px = 0.f;
-            if constexpr (XKEY) {
-                px = __builtin_amdgcn_exp2f(fmaf(sx, scale_log2e, nmx));
-                sum += px;
-            }
             f32x4 o[4];
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -711,16 +954,6 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8 || XKEY) ? 2 : 1) void attention_
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if constexpr (XKEY) {   // + p_x * v_x: lane (query fr) owns d = dt * 16 + fq * 4 .. + 3
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) {
-                    const float4 vx = *reinterpret_cast<const float4 *>(Xk + 64 + dt * 16 + fq * 4);
-                    o[dt][0] = fmaf(px, vx.x, o[dt][0]);
-                    o[dt][1] = fmaf(px, vx.y, o[dt][1]);
-                    o[dt][2] = fmaf(px, vx.z, o[dt][2]);
-                    o[dt][3] = fmaf(px, vx.w, o[dt][3]);
-                }
-            }
             if (!(dbg & 16)) {   // O^T -> fp16 pair, through the wave's LDS patch as whole 128-byte rows: hi part, then lo part
                 const float inv = 1.0f / sum;
                 _Float16 *ot = Ot + wave * (16 * OS);
@@ -752,6 +985,11 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8 || XKEY) ? 2 : 1) void attention_
         if constexpr (XKEY) {
             if (tail && !(dbg & 2)) {
                 static_assert(!XKEY || KTP == 2 * NW, "the tail query is shared by keys: two key tiles (one PV step) per wave");
+                // Q of token L-1 was staged into LDS beside the extra key's K / V rows: this lane's 16 d values, as a main
+                // tile's lane holds them (every column of this tile is the one query)
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    qraw[c] = *reinterpret_cast<const float4 *>(Xk + 128 + (c >> 1) * 32 + fq * 8 + (c & 1) * 4);
                 f16x8 qh[2], ql[2];
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
@@ -1342,7 +1580,7 @@ template <int KTP, int NW, bool XKEY = false>
 static int launch_attention_split(const float *qkv, int B, int L, int W, int heads, _Float16 *out, int q_tiles,
                                   hipStream_t stream) {
     constexpr int KEYS = KTP * 16;
-    const size_t lds = (size_t)4 * KEYS * 128 + (size_t)NW * 16 * 72 * 2 + (XKEY ? 512 : 0);
+    const size_t lds = (size_t)4 * KEYS * 128 + (size_t)NW * 16 * 72 * 2 + (XKEY ? 768 : 0);
     static PerDeviceOnce attr_once;
     const int rc = attr_once.run([&]() -> int {
         if (lds > 48 * 1024)
@@ -1435,6 +1673,27 @@ static int attention_dispatch(const _Float16 *qkv, int B, int L, int W, int head
         return kt >= 13 ? launch_attention<14, 8, true>(qkv, B, L, W, heads, out, q_tiles, stream)
                         : launch_attention<14, 8, false>(qkv, B, L, W, heads, out, q_tiles, stream);
     return launch_attention<16, 8, true>(qkv, B, L, W, heads, out, q_tiles, stream);   // kt is 15 or 16: always EXACT
+}
+
+extern "C" int mpreid_vit_attention(const void *qkv, int precision, int B, int L, int W, int heads, int q_tiles, void *out,
+                                    mpreid_stream_t stream) {
+    ARG_CHECK(qkv && out && B > 0 && heads > 0 && q_tiles >= 0);
+    ARG_CHECK(precision == MPREID_VIT_F16 || precision == MPREID_VIT_SPLIT);
+    ARG_CHECK(W == 64 * heads && L >= 2 && L <= MPREID_VIT_MAX_TOKENS);
+    ARG_CHECK(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 15) == 0);
+    if (16 * (int64_t)q_tiles >= L) q_tiles = 0;   // every tile: the kernels' own form of "all rows"
+    hipStream_t s = (hipStream_t)stream;
+    const int pr = precision == MPREID_VIT_SPLIT ? 2 : 1;
+    const int64_t M = (int64_t)B * L;
+    const int64_t qrows = q_tiles > 0 ? (int64_t)B * (16 * q_tiles < L ? 16 * q_tiles : L) : M;
+    void *ptok = mpreid_prof_begin(s);   // the class of the forward's launches: (MPREID_PROF_ATTENTION, M, q_tiles != 0, pr)
+    const int rc = precision == MPREID_VIT_SPLIT
+                       ? attention_split_dispatch(reinterpret_cast<const float *>(qkv), B, L, W, heads,
+                                                  reinterpret_cast<_Float16 *>(out), q_tiles, s)
+                       : attention_dispatch(reinterpret_cast<const _Float16 *>(qkv), B, L, W, heads,
+                                            reinterpret_cast<_Float16 *>(out), q_tiles, s);
+    mpreid_prof_end(ptok, s, MPREID_PROF_ATTENTION, M, q_tiles ? 1 : 0, pr, ((double)M * 2.0 * W + (double)qrows * 2.0 * W) * 2.0 * pr);
+    return rc;
 }
 
 extern "C" int mpreid_vit_forward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_image_in *img, int B,

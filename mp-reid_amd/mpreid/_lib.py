@@ -173,6 +173,7 @@ PROTOTYPES = {
     # the encoders: (cfg, weights, image batch, B, [cv_emb,] out, workspace, workspace bytes, stream)
     "mpreid_vit_workspace_bytes": (sz, [P(VitCfg), i32]),
     "mpreid_vit_forward": (i32, [P(VitCfg), P(VitWeights), P(ImageIn), i32, vp, vp, vp, sz, vp]),
+    "mpreid_vit_attention": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "mpreid_vit_workspace_bytes_f32": (sz, [P(VitCfg), i32]),
     "mpreid_vit_forward_f32": (i32, [P(VitCfg), P(VitWeights), P(ImageIn), i32, vp, vp, vp, sz, vp]),
     "mpreid_tta_mean_f32": (i32, [vp, i32, i64, i32, i32, vp, vp]),

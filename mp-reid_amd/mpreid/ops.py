@@ -956,6 +956,27 @@ def conv_split_layer(conv, B: int, H: int, W: int, x: Optional[torch.Tensor] = N
     return out, pair_out
 
 
+def vit_attention(qkv: torch.Tensor, batch: int, tokens: int, heads: int, q_tiles: int = 0,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the encoder's attention step alone (mpreid_vit_attention, include/mpreid.h).  qkv: [batch * tokens, 3 * 64 * heads],
+    fp32 (split precision) or fp16.  out: fp16 [batch * tokens, 2 * width] = [hi | lo] for fp32 input, [batch * tokens, width]
+    for fp16 input; allocated (uninitialised) when not passed.  q_tiles > 0 writes only the first 16 * q_tiles rows of every
+    image.  `out` may be a view into a larger buffer (the tests put guard rows around it)."""
+    _lib.require_gpu()
+    width = 64 * heads
+    assert qkv.is_cuda and qkv.is_contiguous() and tuple(qkv.shape) == (batch * tokens, 3 * width)
+    assert qkv.dtype in (torch.float32, torch.float16)
+    split = qkv.dtype == torch.float32
+    cols = 2 * width if split else width
+    if out is None:
+        out = torch.empty((batch * tokens, cols), dtype=torch.float16, device=qkv.device)
+    assert out.dtype == torch.float16 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (batch * tokens, cols)
+    _lib.check(_lib.load().mpreid_vit_attention(_ptr(qkv), _lib.VIT_SPLIT if split else _lib.VIT_F16, int(batch), int(tokens),
+                                                width, int(heads), int(q_tiles), _ptr(out), _lib.stream_ptr()),
+               "mpreid_vit_attention")
+    return out
+
+
 def _np_getter(state_dict):
     """name -> numpy array of a ModifiedResNet state dict (keys optionally prefixed 'image_encoder.', numpy or torch)"""
     def get(name):
