@@ -2,6 +2,7 @@
 #include "common.h"
 
 #include <cstring>
+#include <map>
 #include <string>
 #include <utility>
 #include <vector>
@@ -49,6 +50,25 @@ int mpreid_tune(const char *key, int dflt) {
     for (const auto &p : t.kv)
         if (p.first == key) return p.second;
     return dflt;
+}
+
+// dynamic LDS of a launch: see common.h.  The mark is raised only after the runtime accepted the value.
+int mpreid_dyn_lds(const void *kernel, size_t bytes) {
+    if (bytes > 160 * 1024) {
+        mpreid_set_error("kernel needs %zu bytes of LDS (> 160 KiB)", bytes);
+        return MPREID_ERR_UNSUPPORTED;
+    }
+    if (bytes <= 48 * 1024) return MPREID_OK;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, size_t> mark;   // (device, kernel) -> bytes granted so far
+    std::lock_guard<std::mutex> lk(mu);
+    size_t *m = dev >= 0 && dev < 64 ? &mark[{dev, kernel}] : nullptr;
+    if (m && bytes <= *m) return MPREID_OK;
+    HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (m) *m = bytes;
+    return MPREID_OK;
 }
 
 extern "C" int mpreid_version(void) { return 101; } /* 0.1.1: mpreid/_lib.py (VERSION) loads exactly this one */

@@ -152,8 +152,21 @@ void *mpreid_prof_begin(hipStream_t stream);
 bool mpreid_prof_active(); // mpreid_profile_enable(1) is in force: a launcher whose work figure costs something computes it only then
 void mpreid_prof_end(void *token, hipStream_t stream, int cls, int64_t m, int n, int k, double work);
 
-// Run `f` (returns an mpreid/hip status) once per HIP device for the call site that owns this object: function
-// attributes (dynamic LDS size) and occupancy queries are per device, and one process may drive several GPUs.
+// The ONE way a launcher asks for `bytes` of dynamic LDS for `kernel`, called before every launch that passes them:
+// MPREID_ERR_UNSUPPORTED above 160 KiB (one workgroup's LDS on gfx950), nothing to do up to 48 KiB (what a launch may pass
+// without the attribute), and in between hipFuncAttributeMaxDynamicSharedMemorySize is raised when `bytes` exceeds what
+// this kernel was last given on the CURRENT HIP device -- the attribute is per device and one process may drive several
+// GPUs.  Grow-only, one table and one mutex (api.cpp); devices numbered 64 or higher are not cached, as in PerDeviceOnce.
+// Returns MPREID_OK, or an mpreid / hip status with the error text set.
+int mpreid_dyn_lds(const void *kernel, size_t bytes);
+template <typename F>
+static inline int mpreid_dyn_lds(F *kernel, size_t bytes) {
+    return mpreid_dyn_lds(reinterpret_cast<const void *>(kernel), bytes);
+}
+
+// Run `f` (returns an mpreid/hip status) once per HIP device for the call site that owns this object: whatever else is
+// per device (occupancy queries, a verbose line) -- one process may drive several GPUs.  The dynamic-LDS attribute has
+// its own rule: mpreid_dyn_lds above.
 struct PerDeviceOnce {
     std::mutex mu;
     bool done[64] = {};

@@ -269,15 +269,8 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(ConvArgs g, int tiles
 template <int TAPS, bool RELU, int BN, bool SPLIT = false>
 static int launch_conv_variant(const ConvArgs &a, hipStream_t stream) {
     const int tiles_m = (a.M + CBM - 1) / CBM, tiles_n = (a.N + BN - 1) / BN;
-    static PerDeviceOnce attr_once;
-    {
-        const int rc = attr_once.run([]() -> int {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_gemm_kernel<TAPS, RELU, BN, SPLIT>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, conv_lds_bytes(BN)));
-            return MPREID_OK;
-        });
-        if (rc) return rc;
-    }
+    const int rc = mpreid_dyn_lds(conv_gemm_kernel<TAPS, RELU, BN, SPLIT>, conv_lds_bytes(BN));
+    if (rc) return rc;
     hipLaunchKernelGGL((conv_gemm_kernel<TAPS, RELU, BN, SPLIT>), dim3((unsigned)(tiles_m * tiles_n)), dim3(256), conv_lds_bytes(BN),
                        stream, a, tiles_m, tiles_n);
     LAUNCH_CHECK();

@@ -217,31 +217,35 @@ static inline size_t ev_geometry(int rcap, int *cap_out, int *hw_out) {
     return (size_t)cap * 8 + (size_t)hw * 4;
 }
 
+// The one launch of every instantiation: geometry, dynamic LDS, profiler bracket (filed under (nq, prof_n, prof_k) with
+// `work` algorithmic bytes), launch.  ng: the gallery size, 0 with SPLITS (the lists g_off / g_idx give it per pair).
+template <bool CAM, bool SPLITS>
+static int launch_eval_rank(const float *dist, int64_t ld, int nq, int ng, const int64_t *q_pids, const int64_t *g_pids,
+                            const int64_t *q_camids, const int64_t *g_camids, int rcap, int32_t *pos_out, int32_t *cnt_out,
+                            const int32_t *q_row, const int32_t *q_split, const int64_t *g_off, const int32_t *g_idx,
+                            int prof_n, int prof_k, double work, hipStream_t stream) {
+    int cap, hw;
+    const size_t lds = ev_geometry(rcap, &cap, &hw);
+    const int rc = mpreid_dyn_lds(eval_rank_kernel<CAM, SPLITS>, lds);
+    if (rc != MPREID_OK) return rc;
+    void *ptok = mpreid_prof_begin(stream);
+    hipLaunchKernelGGL((eval_rank_kernel<CAM, SPLITS>), dim3((unsigned)nq), dim3(256), lds, stream, dist, ld, nq, ng,
+                       (const long long *)q_pids, (const long long *)g_pids, (const long long *)q_camids,
+                       (const long long *)g_camids, rcap, cap, hw, pos_out, cnt_out, (const int *)q_row, (const int *)q_split,
+                       (const long long *)g_off, (const int *)g_idx);
+    mpreid_prof_end(ptok, stream, MPREID_PROF_EVALRANK, nq, prof_n, prof_k, work);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
 extern "C" int mpreid_eval_rank_positions(const float *dist_dev, int64_t ld, int nq, int ng, const int64_t *q_pids_dev,
                                           const int64_t *g_pids_dev, int rcap, int32_t *pos_out_dev,
                                           int32_t *cnt_out_dev, mpreid_stream_t stream) {
     ARG_CHECK(dist_dev && q_pids_dev && g_pids_dev && pos_out_dev && cnt_out_dev && nq > 0 && ng > 0 && ld >= ng &&
               rcap > 0);
-    int cap, hw;
-    const size_t lds = ev_geometry(rcap, &cap, &hw);
-    static PerDeviceOnce attr_once;
-    {
-        const int rc = attr_once.run([]() -> int {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel<false, false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        EV_CAP_MAX * 8 + (EV_CAP_MAX + 1) * 4));
-            return MPREID_OK;
-        });
-        if (rc != MPREID_OK) return rc;
-    }
-    void *ptok = mpreid_prof_begin((hipStream_t)stream);
-    hipLaunchKernelGGL((eval_rank_kernel<false, false>), dim3((unsigned)nq), dim3(256), lds, (hipStream_t)stream, dist_dev,
-                       ld, nq, ng, (const long long *)q_pids_dev, (const long long *)g_pids_dev,
-                       (const long long *)nullptr, (const long long *)nullptr, rcap, cap, hw, pos_out_dev, cnt_out_dev,
-                       (const int *)nullptr, (const int *)nullptr, (const long long *)nullptr, (const int *)nullptr);
-    mpreid_prof_end(ptok, (hipStream_t)stream, MPREID_PROF_EVALRANK, nq, ng, 0, 4.0 * (double)nq * (double)ng);
-    LAUNCH_CHECK();
-    return MPREID_OK;
+    return launch_eval_rank<false, false>(dist_dev, ld, nq, ng, q_pids_dev, g_pids_dev, nullptr, nullptr, rcap, pos_out_dev,
+                                          cnt_out_dev, nullptr, nullptr, nullptr, nullptr, ng, 0,
+                                          4.0 * (double)nq * (double)ng, (hipStream_t)stream);
 }
 
 extern "C" int mpreid_eval_rank_positions_cam(const float *dist_dev, int64_t ld, int nq, int ng,
@@ -250,27 +254,9 @@ extern "C" int mpreid_eval_rank_positions_cam(const float *dist_dev, int64_t ld,
                                               int32_t *pos_out_dev, int32_t *cnt_out_dev, mpreid_stream_t stream) {
     ARG_CHECK(dist_dev && q_pids_dev && g_pids_dev && q_camids_dev && g_camids_dev && pos_out_dev && cnt_out_dev &&
               nq > 0 && ng > 0 && ld >= ng && rcap > 0);
-    int cap, hw;
-    const size_t lds = ev_geometry(rcap, &cap, &hw);
-    static PerDeviceOnce attr_once; // its own: the attribute belongs to the function, not to the file
-    {
-        const int rc = attr_once.run([]() -> int {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel<true, false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        EV_CAP_MAX * 8 + (EV_CAP_MAX + 1) * 4));
-            return MPREID_OK;
-        });
-        if (rc != MPREID_OK) return rc;
-    }
-    void *ptok = mpreid_prof_begin((hipStream_t)stream);
-    hipLaunchKernelGGL((eval_rank_kernel<true, false>), dim3((unsigned)nq), dim3(256), lds, (hipStream_t)stream, dist_dev,
-                       ld, nq, ng, (const long long *)q_pids_dev, (const long long *)g_pids_dev,
-                       (const long long *)q_camids_dev, (const long long *)g_camids_dev, rcap, cap, hw, pos_out_dev,
-                       cnt_out_dev, (const int *)nullptr, (const int *)nullptr, (const long long *)nullptr,
-                       (const int *)nullptr);
-    mpreid_prof_end(ptok, (hipStream_t)stream, MPREID_PROF_EVALRANK, nq, ng, 0, 4.0 * (double)nq * (double)ng);
-    LAUNCH_CHECK();
-    return MPREID_OK;
+    return launch_eval_rank<true, false>(dist_dev, ld, nq, ng, q_pids_dev, g_pids_dev, q_camids_dev, g_camids_dev, rcap,
+                                         pos_out_dev, cnt_out_dev, nullptr, nullptr, nullptr, nullptr, ng, 0,
+                                         4.0 * (double)nq * (double)ng, (hipStream_t)stream);
 }
 
 // A batch of (split, query) pairs over one resident matrix: include/mpreid.h.  One launch, one block per pair.
@@ -285,22 +271,6 @@ extern "C" int mpreid_eval_rank_positions_splits(const float *dist_dev, int64_t 
     ARG_CHECK((q_camids_dev == nullptr) == (g_camids_dev == nullptr));
     ARG_CHECK(n_rows > 0 && n_rows <= INT32_MAX && n_cols > 0 && n_cols <= INT32_MAX && ld >= n_cols && nqt > 0 &&
               n_splits > 0 && rcap > 0);
-    const bool cam = q_camids_dev != nullptr;
-    int cap, hw;
-    const size_t lds = ev_geometry(rcap, &cap, &hw);
-    static PerDeviceOnce attr_once; // one per launcher, as above; it sets both instantiations this launcher starts
-    {
-        const int rc = attr_once.run([]() -> int {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel<false, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        EV_CAP_MAX * 8 + (EV_CAP_MAX + 1) * 4));
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel<true, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        EV_CAP_MAX * 8 + (EV_CAP_MAX + 1) * 4));
-            return MPREID_OK;
-        });
-        if (rc != MPREID_OK) return rc;
-    }
     // profiling runs only: the work figure (4 bytes per gathered distance, summed over the pairs) needs the split of
     // every pair and the list lengths, which live on the device -- two small blocking copies BEFORE the timed interval
     double work = 0.0;
@@ -313,20 +283,7 @@ extern "C" int mpreid_eval_rank_positions_splits(const float *dist_dev, int64_t 
         for (int b = 0; b < nqt; ++b)
             if (qs[b] >= 0 && qs[b] < n_splits) work += 4.0 * (double)(off[qs[b] + 1] - off[qs[b]]);
     }
-    void *ptok = mpreid_prof_begin((hipStream_t)stream);
-    if (cam)
-        hipLaunchKernelGGL((eval_rank_kernel<true, true>), dim3((unsigned)nqt), dim3(256), lds, (hipStream_t)stream,
-                           dist_dev, ld, nqt, 0, (const long long *)q_pids_dev, (const long long *)g_pids_dev,
-                           (const long long *)q_camids_dev, (const long long *)g_camids_dev, rcap, cap, hw, pos_out_dev,
-                           cnt_out_dev, (const int *)q_row_dev, (const int *)q_split_dev, (const long long *)g_off_dev,
-                           (const int *)g_idx_dev);
-    else
-        hipLaunchKernelGGL((eval_rank_kernel<false, true>), dim3((unsigned)nqt), dim3(256), lds, (hipStream_t)stream,
-                           dist_dev, ld, nqt, 0, (const long long *)q_pids_dev, (const long long *)g_pids_dev,
-                           (const long long *)nullptr, (const long long *)nullptr, rcap, cap, hw, pos_out_dev,
-                           cnt_out_dev, (const int *)q_row_dev, (const int *)q_split_dev, (const long long *)g_off_dev,
-                           (const int *)g_idx_dev);
-    mpreid_prof_end(ptok, (hipStream_t)stream, MPREID_PROF_EVALRANK, nqt, (int)n_cols, n_splits, work);
-    LAUNCH_CHECK();
-    return MPREID_OK;
+    const auto launch = q_camids_dev ? launch_eval_rank<true, true> : launch_eval_rank<false, true>;
+    return launch(dist_dev, ld, nqt, 0, q_pids_dev, g_pids_dev, q_camids_dev, g_camids_dev, rcap, pos_out_dev, cnt_out_dev,
+                  q_row_dev, q_split_dev, g_off_dev, g_idx_dev, (int)n_cols, n_splits, work, (hipStream_t)stream);
 }

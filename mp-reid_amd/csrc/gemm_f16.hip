@@ -2241,15 +2241,7 @@ static int current_device_cus(int *cus) {
 template <int EPI>
 static int launch_one(const GemmArgs &a_in, hipStream_t stream) {
     const GemmArgs &a = a_in;
-    static PerDeviceOnce attr_once;
-    {
-        const int rc = attr_once.run([]() -> int {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16_kernel<EPI>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS_BYTES));
-            return MPREID_OK;
-        });
-        if (rc) return rc;
-    }
+    if (const int rc = mpreid_dyn_lds(gemm_f16_kernel<EPI>, G_LDS_BYTES)) return rc;
     constexpr bool HAS_BIG = (EPI == GE_F32 || EPI == GE_BIAS_F16 || EPI == GE_BIAS_RES || EPI == GE_BIAS_GELU ||
                               EPI == GE_EUCLID || EPI == GE_PATCH || EPI == GE_BIAS_RELU || EPI == GE_BIAS_ADD_RELU ||
                               EPI == GE_CAND || gemm_epi_is_split(EPI));
@@ -2270,13 +2262,7 @@ static int launch_one(const GemmArgs &a_in, hipStream_t stream) {
     const bool use_big = HAS_BIG && (EPI == GE_CAND || (bm > 0 && (a.M % BBM == 0) && (a.N % BBN == 0) &&
                                                         (bm >= 2 || (int64_t)(a.M / BBM) * (a.N / BBN) >= 128)));
     if constexpr (HAS_BIG) {
-        static PerDeviceOnce big_attr_once;
-        const int rc = big_attr_once.run([]() -> int {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16_big_kernel<EPI>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_TOTAL));
-            return MPREID_OK;
-        });
-        if (rc) return rc;
+        if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI>, B_LDS_TOTAL)) return rc;
     }
     const int tiles_m = use_big ? a.M / BBM : a.M / GBM, tiles_n = use_big ? a.N / BBN : a.N / GBN;
     static const int verbose = mpreid_tune("verbose", 0);
@@ -2304,13 +2290,7 @@ static int launch_one(const GemmArgs &a_in, hipStream_t stream) {
     }
     if (use_p2) {
         if constexpr (EPI == GE_EUCLID) {
-            static PerDeviceOnce p2_once;
-            const int rc = p2_once.run([]() -> int {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(dist_sym_p2_kernel<0>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS_BYTES));
-                return MPREID_OK;
-            });
-            if (rc) return rc;
+            if (const int rc = mpreid_dyn_lds(dist_sym_p2_kernel<0>, P_LDS_BYTES)) return rc;
             int cus = 0;
             if (const int rcc = current_device_cus(&cus)) return rcc;
             const int grid = std::max(8, (2 * cus) & ~7);
@@ -2330,13 +2310,11 @@ static int launch_one(const GemmArgs &a_in, hipStream_t stream) {
             if (const char *sp = getenv("MPREID_GEMM_STAMPS")) a.stamps = reinterpret_cast<unsigned long long *>(strtoull(sp, nullptr, 16));
 #define MPREID_P2_CASE(V)                                                                                      \
     case V:                                                                                                    \
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(dist_sym_p2_kernel<V>),                     \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS_BYTES));                 \
+        if (const int rc = mpreid_dyn_lds(dist_sym_p2_kernel<V>, P_LDS_BYTES)) return rc;                      \
         hipLaunchKernelGGL(dist_sym_p2_kernel<V>, gdim, dim3(256), P_LDS_BYTES, stream, a, a.M / PBM, a.N / PBN, naps, strip); \
         break;
             if (p2_full) {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(dist_sym_p2_kernel<0, true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS_BYTES));
+                if (const int rc = mpreid_dyn_lds(dist_sym_p2_kernel<0, true>, P_LDS_BYTES)) return rc;
                 hipLaunchKernelGGL((dist_sym_p2_kernel<0, true>), gdim, dim3(256), P_LDS_BYTES, stream, a, a.M / PBM, a.N / PBN, naps, strip);
             } else
             switch (abl) {
@@ -2348,13 +2326,7 @@ static int launch_one(const GemmArgs &a_in, hipStream_t stream) {
 #undef MPREID_P2_CASE
 #else
             if (p2_full) {
-                static PerDeviceOnce p2f_once;
-                const int rcf = p2f_once.run([]() -> int {
-                    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(dist_sym_p2_kernel<0, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS_BYTES));
-                    return MPREID_OK;
-                });
-                if (rcf) return rcf;
+                if (const int rc = mpreid_dyn_lds(dist_sym_p2_kernel<0, true>, P_LDS_BYTES)) return rc;
                 hipLaunchKernelGGL((dist_sym_p2_kernel<0, true>), gdim, dim3(256), P_LDS_BYTES, stream, a, a.M / PBM, a.N / PBN, naps, strip);
             } else {
                 hipLaunchKernelGGL(dist_sym_p2_kernel<0>, gdim, dim3(256), P_LDS_BYTES, stream, a, a.M / PBM, a.N / PBN, naps, strip);
@@ -2409,23 +2381,20 @@ static int launch_one(const GemmArgs &a_in, hipStream_t stream) {
             }
 #ifdef MPREID_ABLATION
             if (dbg == 64 && gemm_epi_is_split(EPI)) {   // operand panels aliased onto two (L2-resident): see set_tile
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16_big_kernel<EPI, 64>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_TOTAL));
+                if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, 64>, B_LDS_TOTAL)) return rc;
                 hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, 64>), grid, dim3(512), B_LDS_TOTAL, stream, a, tiles_m, tiles_n);
             } else if (dbg == 32 && EPI != GE_EUCLID && EPI != GE_BIAS_GELU) {   // per-tile phase stamps for any epilogue (tools/gemm_tile_stamps.py)
                 GemmArgs as = a;
                 const char *sp = getenv("MPREID_GEMM_STAMPS");
                 as.stamps = sp ? reinterpret_cast<unsigned long long *>(strtoull(sp, nullptr, 16)) : nullptr;
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16_big_kernel<EPI, 32>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_TOTAL));
+                if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, 32>, B_LDS_TOTAL)) return rc;
                 hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, 32>), grid, dim3(512), B_LDS_TOTAL, stream, as, tiles_m, tiles_n);
             } else
 #endif
             if constexpr (EPI == GE_BIAS_F16) {
 #define MPREID_DBG_CASE(D)                                                                                  \
     case D: {                                                                                               \
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16_big_kernel<EPI, D>),            \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_TOTAL));              \
+        if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, D>, B_LDS_TOTAL)) return rc;                 \
         hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, D>), grid, dim3(512), B_LDS_TOTAL, stream, a, tiles_m, tiles_n); \
         break;                                                                                              \
     }
@@ -2442,38 +2411,28 @@ static int launch_one(const GemmArgs &a_in, hipStream_t stream) {
                     GemmArgs as = a;
                     const char *sp = getenv("MPREID_GEMM_STAMPS");
                     as.stamps = sp ? reinterpret_cast<unsigned long long *>(strtoull(sp, nullptr, 16)) : nullptr;
-                    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16_big_kernel<EPI, 800>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_TOTAL));
+                    if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, 800>, B_LDS_TOTAL)) return rc;
                     hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, 800>), grid, dim3(512), B_LDS_TOTAL, stream, as, tiles_m, tiles_n);
                 } else if (dbg == 32) {   // (ablation builds) per-tile phase stamps; MPREID_GEMM_STAMPS = device pointer (hex)
                     GemmArgs as = a;
                     const char *sp = getenv("MPREID_GEMM_STAMPS");
                     as.stamps = sp ? reinterpret_cast<unsigned long long *>(strtoull(sp, nullptr, 16)) : nullptr;
-                    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16_big_kernel<EPI, 32>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_TOTAL));
+                    if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, 32>, B_LDS_TOTAL)) return rc;
                     hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, 32>), grid, dim3(512), B_LDS_TOTAL, stream, as, tiles_m, tiles_n);
                 } else if (dbg >= 128 && dbg <= 6 * 128 && dbg % 128 == 0) {   // (ablation builds) store cache policies
 #define MPREID_FLAV_CASE(F)                                                                                         \
     case F * 128:                                                                                                    \
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16_big_kernel<EPI, F * 128>),               \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_TOTAL));                       \
+        if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, F * 128>, B_LDS_TOTAL)) return rc;                    \
         hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, F * 128>), grid, dim3(512), B_LDS_TOTAL, stream, a, tiles_m, tiles_n); \
         break;
                     switch (dbg) { MPREID_FLAV_CASE(1) MPREID_FLAV_CASE(2) MPREID_FLAV_CASE(3) MPREID_FLAV_CASE(4) MPREID_FLAV_CASE(5) MPREID_FLAV_CASE(6) }
 #undef MPREID_FLAV_CASE
                 } else if (dbg == 16) {   // (ablation builds) the unpaired DMA schedule
-                    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16_big_kernel<EPI, 16>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_TOTAL));
+                    if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, 16>, B_LDS_TOTAL)) return rc;
                     hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, 16>), grid, dim3(512), B_LDS_TOTAL, stream, a, tiles_m, tiles_n);
                 } else if (EPI == GE_EUCLID && a.sym) {   // symmetric problem: the instance with the mirrored stores
                     if constexpr (EPI == GE_EUCLID) {
-                        static PerDeviceOnce sym_once;
-                        const int rc = sym_once.run([]() -> int {
-                            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16_big_kernel<EPI, 0, true>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_TOTAL));
-                            return MPREID_OK;
-                        });
-                        if (rc) return rc;
+                        if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, 0, true>, B_LDS_TOTAL)) return rc;
                         hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, 0, true>), grid, dim3(512), B_LDS_TOTAL, stream, a, tiles_m, tiles_n);
                     }
                 } else {

@@ -2086,18 +2086,6 @@ static bool dense_lds_ok(const RerankLayout &L) {
     return krecip_lds_bytes(false, (int)((L.N + 31) >> 5), L.K, L.vcap, 0) <= LDS_WG_MAX;
 }
 
-template <typename F>
-static int set_dyn_lds(F kernel, size_t bytes) {
-    if (bytes > LDS_WG_MAX) {
-        mpreid_set_error("kernel needs %zu bytes of LDS (> 160 KiB)", bytes);
-        return MPREID_ERR_UNSUPPORTED;
-    }
-    if (bytes > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)bytes));
-    return MPREID_OK;
-}
-
 // the k-reciprocal kernel's LDS request, with an error that names the limit in the caller's terms (include/mpreid.h "Limits")
 template <typename F>
 static int set_krecip_lds(F kernel, size_t bytes, int K, int64_t N) {
@@ -2108,7 +2096,51 @@ static int set_krecip_lds(F kernel, size_t bytes, int K, int64_t N) {
                          K - 1, (long long)N, bytes);
         return MPREID_ERR_UNSUPPORTED;
     }
-    return set_dyn_lds(kernel, bytes);
+    return mpreid_dyn_lds(kernel, bytes);
+}
+
+// (4)-(6) V rows of the rows [row0, row0 + rows) of the N x N problem: the reciprocity bits of ALL rows into rk
+// (mpreid_rr_krecip_scratch_bytes; the candidates of a row live anywhere), then the k-reciprocal kernel.  Dense: MT /
+// rowmax / vcnt.. are indexed by the local row, feat = norms = rankd = NULL, d = 0.  SPARSE: distances on the fly from
+// feat / norms, rankd indexed by the GLOBAL row.  r_count: |R| per row, or NULL.
+template <bool SPARSE>
+static int launch_krecip(const float *MT, int64_t ld, int64_t N, const float *rowmax, const int *rank, int K, int KR, int h,
+                         int vcap, int *vcnt, int *vidx, uint16_t *vval, int64_t row0, int64_t rows, int *r_count,
+                         const float *feat, const float *norms, int d, const float *rankd, unsigned *rk, hipStream_t stream) {
+    const size_t lds = krecip_lds_bytes(SPARSE, (int)((N + 31) >> 5), K, vcap, d);
+    int rc = set_krecip_lds(krecip_kernel<SPARSE>, lds, K, N);
+    if (rc) return rc;
+    unsigned *rh = rk + (size_t)N * RB_WORDS;
+    hipLaunchKernelGGL(recip_bits_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, rank, N, K, KR, h, rk, rh);
+    hipLaunchKernelGGL(krecip_kernel<SPARSE>, dim3((unsigned)rows), dim3(256), lds, stream, MT, ld, N, rowmax, rank, K, KR, h,
+                       vcap, vcnt, vidx, vval, (int)row0, r_count, feat, norms, d, rankd, rk, rh);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
+// (7) query expansion of the rows [row0, row0 + rows) from the V rows of all N: union sizes, then the fill with row
+// stride qcap >= the largest union
+static int launch_qe_count(int64_t N, const int *rank, int KR, int k2, int64_t row0, int64_t rows, const int *vcnt,
+                           const int *vidx, int vcap, int *ucnt, hipStream_t stream) {
+    const size_t lds = (size_t)((N + 31) >> 5) * 4;
+    int rc = mpreid_dyn_lds(qe_count_kernel, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(qe_count_kernel, dim3((unsigned)rows), dim3(64), lds, stream, N, rank, KR, k2, vcnt, vidx, vcap, ucnt,
+                       (int)row0);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
+static int launch_qe_fill(int64_t N, const int *rank, int KR, int k2, int64_t row0, int64_t rows, const int *vcnt,
+                          const int *vidx, const uint16_t *vval, int vcap, int qcap, int *qcnt, int *qidx, uint16_t *qval,
+                          hipStream_t stream) {
+    const size_t lds = (size_t)((N + 31) >> 5) * 8 + (size_t)qcap * 8;
+    int rc = mpreid_dyn_lds(qe_fill_kernel, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(qe_fill_kernel, dim3((unsigned)rows), dim3(64), lds, stream, N, rank, KR, k2, vcnt, vidx, vval, vcap, qcap,
+                       qcnt, qidx, qval, (int)row0);
+    LAUNCH_CHECK();
+    return MPREID_OK;
 }
 
 // max of x[0..n) -> out[0] (one workgroup)
@@ -2142,9 +2174,9 @@ static int launch_csc(int64_t N, int64_t nq, const int *fcnt, const int *fidx, c
         const JaccardPlan jp = jaccard_plan(M);
         const int nranges = (int)((N + CSC_CR - 1) / CSC_CR);
         const size_t lds = (size_t)std::min<int64_t>(N, CSC_CR) * 4;
-        int rc = set_dyn_lds(csc2_hist_kernel, lds);
+        int rc = mpreid_dyn_lds(csc2_hist_kernel, lds);
         if (rc) return rc;
-        rc = set_dyn_lds(csc2_fill_kernel, lds);
+        rc = mpreid_dyn_lds(csc2_fill_kernel, lds);
         if (rc) return rc;
         hipLaunchKernelGGL(csc2_hist_kernel, dim3(CSC_B, nranges), dim3(1024), lds, stream, N, fcnt, fidx, qcap, jp.rpb, chist,
                            nq, (int64_t)0, N);
@@ -2198,7 +2230,7 @@ static int launch_jaccard(int64_t N, int64_t nq, int q0, int64_t qrows, const fl
     const size_t lds = align_up((size_t)rch * 2 + 16, 16) + (size_t)qcap * (8 + 4 + 2) + 16;
 #define MPREID_JACCARD_LAUNCH(JT_, NPF_, PD_, PK_)                                                                       \
     {                                                                                                                    \
-        int rc = set_dyn_lds(jaccard_kernel<JT_, NPF_, PD_, PK_>, lds);                                                  \
+        int rc = mpreid_dyn_lds(jaccard_kernel<JT_, NPF_, PD_, PK_>, lds);                                                  \
         if (rc) return rc;                                                                                               \
         hipLaunchKernelGGL((jaccard_kernel<JT_, NPF_, PD_, PK_>), dim3((unsigned)qrows, (unsigned)nchunks), dim3(JT_),   \
                            lds, stream, N, nq, MT, ld, rowmax, fcnt, fidx, fval, qcap, cptr, crow, cval, rch, oml, lam32, \
@@ -2210,14 +2242,14 @@ static int launch_jaccard(int64_t N, int64_t nq, int q0, int64_t qrows, const fl
     static const int jtab = mpreid_tune("jaccard_table", 0);   // A/B: LDS table form
     const size_t wl = align_up((size_t)rch * 2 + 16, 16);   // table-free kernels: the accumulators only
     if (threads == 64 && !jtab) {
-        int rc = set_dyn_lds(jaccard_wave_kernel<64, 2, 8>, wl);
+        int rc = mpreid_dyn_lds(jaccard_wave_kernel<64, 2, 8>, wl);
         if (rc) return rc;
         hipLaunchKernelGGL((jaccard_wave_kernel<64, 2, 8>), dim3((unsigned)qrows, (unsigned)nchunks), dim3(64), wl, stream, N, nq,
                            MT, ld, rowmax, fcnt, fidx, fval, qcap, cptr, (const unsigned *)crow, rch, oml, lam32, out, ldo,
                            pair_counter, q0, Hp, rpb, bpc);
     } else if (threads == 64) MPREID_JACCARD_LAUNCH(64, 2, 8, true)
     else if (blocked && !jtab) {
-        int rc = set_dyn_lds(jaccard_wave_kernel<JT, 3, 4>, wl);
+        int rc = mpreid_dyn_lds(jaccard_wave_kernel<JT, 3, 4>, wl);
         if (rc) return rc;
         hipLaunchKernelGGL((jaccard_wave_kernel<JT, 3, 4>), dim3((unsigned)qrows, (unsigned)nchunks), dim3(JT), wl, stream, N, nq,
                            MT, ld, rowmax, fcnt, fidx, fval, qcap, cptr, (const unsigned *)crow, rch, oml, lam32, out, ldo,
@@ -2267,7 +2299,6 @@ struct TailArgs {
 
 static int rerank_tail(const TailArgs &a, hipStream_t stream, StageTimer &tm, mpreid_rerank_stats *stats, int marks_so_far) {
     const int64_t N = a.N;
-    const int nw = (int)((N + 31) >> 5);
     const int k2e = (int)std::min<int64_t>(a.k2, N); // rows the query expansion really averages (numpy clamps the slice)
     int qcap = a.vcap;
     const int *fcnt = a.vcnt, *fidx = a.vidx;
@@ -2277,11 +2308,8 @@ static int rerank_tail(const TailArgs &a, hipStream_t stream, StageTimer &tm, mp
     hipLaunchKernelGGL(sum_i32_kernel, dim3(1), dim3(1024), 0, stream, a.vcnt, N, a.counters + 2);
     if (a.k2 != 1) {
         {
-            const size_t lds = (size_t)nw * 4;
-            int rc = set_dyn_lds(qe_count_kernel, lds);
+            int rc = launch_qe_count(N, a.rank, a.KR, k2e, 0, N, a.vcnt, a.vidx, a.vcap, a.ucnt, stream);
             if (rc) return rc;
-            hipLaunchKernelGGL(qe_count_kernel, dim3((unsigned)N), dim3(64), lds, stream, N, a.rank, a.KR, k2e, a.vcnt, a.vidx,
-                               a.vcap, a.ucnt, 0);
             hipLaunchKernelGGL(max_i32_kernel, dim3(1), dim3(1024), 0, stream, a.ucnt, N, (int *)(a.counters + 3));
             LAUNCH_CHECK();
         }
@@ -2311,12 +2339,9 @@ static int rerank_tail(const TailArgs &a, hipStream_t stream, StageTimer &tm, mp
             }
         }
         {
-            const size_t lds = (size_t)nw * 8 + (size_t)qcap * 8;
-            int rc = set_dyn_lds(qe_fill_kernel, lds);
+            int rc = launch_qe_fill(N, a.rank, a.KR, k2e, 0, N, a.vcnt, a.vidx, a.vval, a.vcap, qcap, a.qcnt, a.qidx, a.qval,
+                                    stream);
             if (rc) return rc;
-            hipLaunchKernelGGL(qe_fill_kernel, dim3((unsigned)N), dim3(64), lds, stream, N, a.rank, a.KR, k2e, a.vcnt, a.vidx,
-                               a.vval, a.vcap, qcap, a.qcnt, a.qidx, a.qval, 0);
-            LAUNCH_CHECK();
         }
         fcnt = a.qcnt;
         fidx = a.qidx;
@@ -2415,7 +2440,6 @@ static int rerank_dense(const float *q, const float *g, int64_t nq, int64_t ng, 
     int *crow = (int *)(base + L.crow);
     uint16_t *cval = (uint16_t *)(base + L.cval);
     unsigned long long *counters = (unsigned long long *)(base + L.counters);
-    const int nw = (int)((N + 31) >> 5);
 
     StageTimer tm(timing != 0, stream);
     HIP_TRY(hipMemsetAsync(counters, 0, 64, stream));
@@ -2444,15 +2468,9 @@ static int rerank_dense(const float *q, const float *g, int64_t nq, int64_t ng, 
     tm.mark(); // 2
     // (4)-(6) V rows
     {
-        const size_t lds = krecip_lds_bytes(false, nw, L.K, L.vcap, 0);
-        int rc = set_krecip_lds(krecip_kernel<false>, lds, L.K, N);
+        int rc = launch_krecip<false>(MT, L.ld, N, rowmax, rank, L.K, L.KR, L.h, L.vcap, vcnt, vidx, vval, 0, N, ucnt, nullptr,
+                                      nullptr, 0, nullptr, (unsigned *)(base + L.rbits), stream);
         if (rc) return rc;
-        unsigned *rk = (unsigned *)(base + L.rbits);
-        hipLaunchKernelGGL(recip_bits_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, rank, N, L.K, L.KR, L.h, rk,
-                           rk + (size_t)N * RB_WORDS);
-        hipLaunchKernelGGL(krecip_kernel<false>, dim3((unsigned)N), dim3(256), lds, stream, MT, L.ld, N, rowmax, rank, L.K,
-                           L.KR, L.h, L.vcap, vcnt, vidx, vval, 0, ucnt, (const float *)nullptr,
-                           (const float *)nullptr, 0, (const float *)nullptr, rk, rk + (size_t)N * RB_WORDS);
         hipLaunchKernelGGL(sum_i32_kernel, dim3(1), dim3(1024), 0, stream, ucnt, N, counters + 1);
         LAUNCH_CHECK();
     }
@@ -2651,8 +2669,7 @@ static int rerank_sparse(const float *q, const float *g, int64_t nq, int64_t ng,
     int *ucnt = (int *)(base + L.ucnt);
     float *dq = (float *)(base + L.dq);
     unsigned long long *counters = (unsigned long long *)(base + L.counters);
-    const int nw = (int)((N + 31) >> 5);
-    const int ns = (int)((N + RR2_SAMPLE_STRIDE - 1) / RR2_SAMPLE_STRIDE);
+    const int ns =(int)((N + RR2_SAMPLE_STRIDE - 1) / RR2_SAMPLE_STRIDE);
 
     StageTimer tm(timing != 0, stream);
     HIP_TRY(hipMemsetAsync(counters, 0, 64, stream));
@@ -2738,7 +2755,7 @@ static int rerank_sparse(const float *q, const float *g, int64_t nq, int64_t ng,
     }
     {   // refinement + fallback rows
         const size_t lds = 512 * 8 + RR2_MAXE * 8 + RR2_MAXH * 8 + (size_t)((d + 3) & ~3) * 4 + 2 * 64 * WXD_STRIDE * 4;
-        rc = set_dyn_lds(rr2_refine_kernel<RR2_CAP_LO, RR2_CAP_HI>, lds);
+        rc = mpreid_dyn_lds(rr2_refine_kernel<RR2_CAP_LO, RR2_CAP_HI>, lds);
         if (rc) return rc;
         hipLaunchKernelGGL((rr2_refine_kernel<RR2_CAP_LO, RR2_CAP_HI>), dim3((unsigned)N), dim3(256), lds, stream, feat, sqn, N,
                            d, L.KR, cnt_lo, list_lo, cnt_hi, list_hi, tlo, eps, rowmax, rank, rankd, fb_count, fb_rows,
@@ -2758,15 +2775,9 @@ static int rerank_sparse(const float *q, const float *g, int64_t nq, int64_t ng,
     }
     tm.mark(); // 2
     {   // V rows, distances on the fly
-        const size_t lds = krecip_lds_bytes(true, nw, L.K, L.vcap, d);
-        rc = set_krecip_lds(krecip_kernel<true>, lds, L.K, N);
+        rc = launch_krecip<true>(nullptr, L.ld, N, rowmax, rank, L.K, L.KR, L.h, L.vcap, vcnt, vidx, vval, 0, N, ucnt, feat, sqn,
+                                 d, rankd, (unsigned *)(base + L.rbits), stream);
         if (rc) return rc;
-        unsigned *rk = (unsigned *)(base + L.rbits);
-        hipLaunchKernelGGL(recip_bits_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, rank, N, L.K, L.KR, L.h, rk,
-                           rk + (size_t)N * RB_WORDS);
-        hipLaunchKernelGGL(krecip_kernel<true>, dim3((unsigned)N), dim3(256), lds, stream, (const float *)nullptr, L.ld, N,
-                           rowmax, rank, L.K, L.KR, L.h, L.vcap, vcnt, vidx, vval, 0, ucnt, feat, sqn, d, rankd, rk,
-                           rk + (size_t)N * RB_WORDS);
         hipLaunchKernelGGL(sum_i32_kernel, dim3(1), dim3(1024), 0, stream, ucnt, N, counters + 1);
         LAUNCH_CHECK();
     }
@@ -3328,7 +3339,7 @@ static int rerank_wide(const float *q, const float *g, int64_t nq, int64_t ng, i
     // (2)+(3) row max, neighbour table, its index-sorted copy, reciprocity positions
     {
         const size_t lds = L.sort_in_lds ? (size_t)L.P * 8 : 0;
-        int rc = set_dyn_lds(wide_topk_kernel, lds);
+        int rc = mpreid_dyn_lds(wide_topk_kernel, lds);
         if (rc) return rc;
         hipLaunchKernelGGL(wide_topk_kernel, dim3((unsigned)L.nwg), dim3(256), lds, stream, MT, L.ld, N, L.K, L.KR, L.P, rowmax,
                            rank, rsort, sortscr);
@@ -3339,7 +3350,7 @@ static int rerank_wide(const float *q, const float *g, int64_t nq, int64_t ng, i
     // (4)-(6) V rows
     {
         const size_t lds = (size_t)nw * 8;
-        int rc = set_dyn_lds(wide_krecip_kernel, lds);
+        int rc = mpreid_dyn_lds(wide_krecip_kernel, lds);
         if (rc) return rc;
         hipLaunchKernelGGL(wide_krecip_kernel, dim3((unsigned)L.nwg), dim3(256), lds, stream, MT, L.ld, N, rowmax, rank, rpos, L.K,
                            L.KR, L.h, L.vcap, vcnt, vidx, vval, wscr, rcount);
@@ -3374,7 +3385,7 @@ static int rerank_wide(const float *q, const float *g, int64_t nq, int64_t ng, i
     // (8)-(11) Jaccard + blend
     {
         const size_t lds = align_up((size_t)L.rch * 2, 16);
-        int rc = set_dyn_lds(wide_jaccard_kernel, lds);
+        int rc = mpreid_dyn_lds(wide_jaccard_kernel, lds);
         if (rc) return rc;
         const unsigned nchunks = (unsigned)((ng + L.rch - 1) / L.rch);
         hipLaunchKernelGGL(wide_jaccard_kernel, dim3((unsigned)nq, nchunks), dim3(256), lds, stream, N, nq, MT, L.ld, rowmax, fcnt,
@@ -3581,21 +3592,10 @@ extern "C" int mpreid_rr_krecip(const float *d_local, int64_t ld, int64_t n, con
     const int K = (int)std::min<int64_t>(k1 + 1, n), h = (int)std::min<int64_t>(mpreid_half_k1(k1), n);
     const int vcap = mpreid_rr_vcap(n, k1);
     ARG_CHECK(d_local && rowmax_local && rank_all && vcnt && vidx && vval && scratch && rows > 0 && kr >= K);
-    const int nw = (int)((n + 31) >> 5);
-    const size_t lds = krecip_lds_bytes(false, nw, K, vcap, 0);
-    int rc = set_krecip_lds(krecip_kernel<false>, lds, K, n);
-    if (rc) return rc;
     // reciprocity bits of ALL rows (candidates of a local row live anywhere): recomputed by every rank from the
     // all-gathered table -- N x K membership tests, cheaper than another exchange
-    unsigned *rk = (unsigned *)scratch;
-    hipLaunchKernelGGL(recip_bits_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream_, rank_all, n, K, kr,
-                       h, rk, rk + (size_t)n * RB_WORDS);
-    hipLaunchKernelGGL(krecip_kernel<false>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream_, d_local, ld, n,
-                       rowmax_local, rank_all, K, kr, h, vcap, vcnt, vidx, vval, (int)r_lo,
-                       (int *)nullptr, (const float *)nullptr, (const float *)nullptr, 0, (const float *)nullptr, rk,
-                       rk + (size_t)n * RB_WORDS);
-    LAUNCH_CHECK();
-    return MPREID_OK;
+    return launch_krecip<false>(d_local, ld, n, rowmax_local, rank_all, K, kr, h, vcap, vcnt, vidx, vval, r_lo, rows, nullptr,
+                                nullptr, nullptr, 0, nullptr, (unsigned *)scratch, (hipStream_t)stream_);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3717,7 +3717,7 @@ extern "C" int mpreid_rr_neighbours_sparse(const float *feat_all, const float *n
     }
     {
         const size_t lds = 512 * 8 + RR2_MAXE * 8 + RR2_MAXH * 8 + (size_t)((d + 3) & ~3) * 4 + 2 * 64 * WXD_STRIDE * 4;
-        if ((rc = set_dyn_lds(rr2_refine_kernel<RR2_CAP_LO, RR2_CAP_HI>, lds))) return rc;
+        if ((rc = mpreid_dyn_lds(rr2_refine_kernel<RR2_CAP_LO, RR2_CAP_HI>, lds))) return rc;
         hipLaunchKernelGGL((rr2_refine_kernel<RR2_CAP_LO, RR2_CAP_HI>), dim3((unsigned)rows), dim3(256), lds, stream, feat_all, sqn,
                            n, d, kr, cnt_lo, list_lo, cnt_hi, list_hi, tlo, eps, rowmax_local, rank_local, rankd_local, fb_count,
                            fb_rows, (unsigned)L.fb_max, r_lo);
@@ -3751,19 +3751,10 @@ extern "C" int mpreid_rr_krecip_sparse(const float *feat_all, const float *norms
     const int vcap = mpreid_rr_vcap(n, k1);
     ARG_CHECK(feat_all && norms_all && rowmax_local && rank_all && rankd_local && vcnt && vidx && vval && scratch && rows > 0 &&
               kr >= K);
-    const int nw = (int)((n + 31) >> 5);
-    const size_t lds = krecip_lds_bytes(true, nw, K, vcap, d);
-    int rc = set_krecip_lds(krecip_kernel<true>, lds, K, n);
-    if (rc) return rc;
-    unsigned *rk = (unsigned *)scratch;
-    hipLaunchKernelGGL(recip_bits_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream_, rank_all, n, K, kr,
-                       h, rk, rk + (size_t)n * RB_WORDS);
     // rankd is indexed by the global row inside the kernel: shift the local table's base accordingly
-    hipLaunchKernelGGL(krecip_kernel<true>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream_, (const float *)nullptr,
-                       (int64_t)0, n, rowmax_local, rank_all, K, kr, h, vcap, vcnt, vidx, vval, (int)r_lo, (int *)nullptr, feat_all,
-                       norms_all, d, rankd_local - (int64_t)r_lo * kr, rk, rk + (size_t)n * RB_WORDS);
-    LAUNCH_CHECK();
-    return MPREID_OK;
+    return launch_krecip<true>(nullptr, 0, n, rowmax_local, rank_all, K, kr, h, vcap, vcnt, vidx, vval, r_lo, rows, nullptr,
+                               feat_all, norms_all, d, rankd_local - (int64_t)r_lo * kr, (unsigned *)scratch,
+                               (hipStream_t)stream_);
 }
 
 extern "C" int mpreid_rr_pack_rows(const int32_t *cnt, const int32_t *idx, const uint16_t *val, int64_t rows,
@@ -3858,13 +3849,7 @@ extern "C" int mpreid_rr_qe_count(int64_t n, const int32_t *rank_all, int kr, in
                                   const int32_t *vcnt_all, const int32_t *vidx_all, int vstride, int32_t *ucnt_local,
                                   mpreid_stream_t stream_) {
     ARG_CHECK(rank_all && vcnt_all && vidx_all && ucnt_local && rows > 0 && k2 >= 1 && kr >= k2);
-    const size_t lds = (size_t)((n + 31) >> 5) * 4;
-    int rc = set_dyn_lds(qe_count_kernel, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(qe_count_kernel, dim3((unsigned)rows), dim3(64), lds, (hipStream_t)stream_, n, rank_all, kr, k2,
-                       vcnt_all, vidx_all, vstride, ucnt_local, (int)r_lo);
-    LAUNCH_CHECK();
-    return MPREID_OK;
+    return launch_qe_count(n, rank_all, kr, k2, r_lo, rows, vcnt_all, vidx_all, vstride, ucnt_local, (hipStream_t)stream_);
 }
 
 extern "C" int mpreid_rr_qe_fill(int64_t n, const int32_t *rank_all, int kr, int k2, int64_t r_lo, int64_t rows,
@@ -3873,13 +3858,8 @@ extern "C" int mpreid_rr_qe_fill(int64_t n, const int32_t *rank_all, int kr, int
                                  mpreid_stream_t stream_) {
     ARG_CHECK(rank_all && vcnt_all && vidx_all && vval_all && qcnt_local && qidx_local && qval_local && rows > 0 &&
               qcap > 0);
-    const size_t lds = (size_t)((n + 31) >> 5) * 8 + (size_t)qcap * 8;
-    int rc = set_dyn_lds(qe_fill_kernel, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(qe_fill_kernel, dim3((unsigned)rows), dim3(64), lds, (hipStream_t)stream_, n, rank_all, kr, k2,
-                       vcnt_all, vidx_all, vval_all, vstride, qcap, qcnt_local, qidx_local, qval_local, (int)r_lo);
-    LAUNCH_CHECK();
-    return MPREID_OK;
+    return launch_qe_fill(n, rank_all, kr, k2, r_lo, rows, vcnt_all, vidx_all, vval_all, vstride, qcap, qcnt_local, qidx_local,
+                          qval_local, (hipStream_t)stream_);
 }
 
 // phase 4: inverted index of the GLOBAL V_qe (row stride qstride) + Jaccard / blend for the query rows
@@ -3933,7 +3913,7 @@ extern "C" int mpreid_rr_csc_count(int64_t n, int64_t nq, const int32_t *qcnt_al
     const int64_t cols = c_hi - c_lo;
     const int nranges = (int)((cols + CSC_CR - 1) / CSC_CR);
     const size_t lds = (size_t)std::min<int64_t>(cols, CSC_CR) * 4;
-    int rc = set_dyn_lds(csc2_hist_kernel, lds);
+    int rc = mpreid_dyn_lds(csc2_hist_kernel, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(csc2_hist_kernel, dim3(CSC_B, nranges), dim3(1024), lds, stream, n, qcnt_all, qidx_all, qstride, jp.rpb,
                        chist, nq, c_lo, c_hi);
@@ -3967,7 +3947,7 @@ extern "C" int mpreid_rr_csc_fill(int64_t n, int64_t nq, const int32_t *qcnt_all
         const int64_t cols = c_hi - c_lo;
         const int nranges = (int)((cols + CSC_CR - 1) / CSC_CR);
         const size_t lds = (size_t)std::min<int64_t>(cols, CSC_CR) * 4;
-        int rc = set_dyn_lds(csc2_fill_kernel, lds);
+        int rc = mpreid_dyn_lds(csc2_fill_kernel, lds);
         if (rc) return rc;
         hipLaunchKernelGGL(csc2_fill_kernel, dim3(CSC_B, nranges), dim3(1024), lds, stream, n, qcnt_all, qidx_all, qval_all, qstride,
                            jp.rpb, chist, cptr, cpk, nq, jp.bpc, c_lo, c_hi);

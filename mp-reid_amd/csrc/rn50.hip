@@ -593,24 +593,14 @@ extern "C" int mpreid_rn50_forward(const mpreid_rn50_cfg *cfg, const mpreid_rn50
         if (!v.pool_scg) {
             const size_t lds = pool_lds_resident(v.T, v.E, Hh);
             ARG_CHECK(lds <= 160 * 1024 && v.E % 32 == 0 && H16 % 4 == 0);
-            static size_t lds_set = 0;
-            if (lds > 48 * 1024 && lds > lds_set) {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(rn50_pool_core_kernel<false>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                lds_set = lds;
-            }
+            if ((rc = mpreid_dyn_lds(rn50_pool_core_kernel<false>, lds))) return rc;
             hipLaunchKernelGGL(rn50_pool_core_kernel<false>, dim3(B), dim3(512), lds, stream, uvec, tok, v.T, v.E, Hh, zvec,
                                nullptr);
         } else {
             const size_t lu = (size_t)H16 * (v.E + 8) * 2, ls = (size_t)H16 * v.T * 4;
             const size_t lds = lu > ls ? lu : ls;
             ARG_CHECK(lds <= 160 * 1024 && v.E % 32 == 0 && H16 % 4 == 0);
-            static size_t lds_set = 0;
-            if (lds > 48 * 1024 && lds > lds_set) {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(rn50_pool_core_kernel<true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                lds_set = lds;
-            }
+            if ((rc = mpreid_dyn_lds(rn50_pool_core_kernel<true>, lds))) return rc;
             hipLaunchKernelGGL(rn50_pool_core_kernel<true>, dim3(B), dim3(512), lds, stream, uvec, tok, v.T, v.E, Hh, zvec,
                                (float *)(base + v.scg));
         }

@@ -1538,34 +1538,30 @@ static int launch_attention(const _Float16 *qkv, int B, int L, int W, int heads,
                             hipStream_t stream) {
     constexpr int KEYS = KTP * 16;
     const size_t lds = (size_t)2 * KEYS * 128 + (size_t)NW * 16 * 72 * 2;
-    // per-device state (a process may drive several GPUs: the reference's do_inference is multi-device in one
-    // process, processor/processor.py:178-182): the dynamic-LDS attribute and the occupancy are set / queried once
-    // per HIP device, under a mutex
-    constexpr int MAX_DEV = 64;
-    static std::mutex mu;
-    static int blocks_per_cu_dev[MAX_DEV] = {0};
+    // a process may drive several GPUs (the reference's do_inference is multi-device in one process,
+    // processor/processor.py:178-182): the occupancy is queried once per HIP device, after the LDS attribute it depends on
     int dev = 0, cus = 256;
     HIP_TRY(hipGetDevice(&dev));
-    int blocks_per_cu;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        const int slot = dev < MAX_DEV ? dev : MAX_DEV - 1;
-        if (blocks_per_cu_dev[slot] == 0 || dev >= MAX_DEV) {
-            if (lds > 48 * 1024)
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(attention_kernel<KTP, NW, EXACT>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            // persistent grid: as many workgroups as fit the chip at once (LDS and the 4-waves/SIMD register
-            // bound), each walking pairs with stride gridDim
-            int occ = 0;
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                &occ, reinterpret_cast<const void *>(attention_kernel<KTP, NW, EXACT>), 64 * NW, lds));
-            blocks_per_cu_dev[slot] = occ > 0 ? occ : 1;
-            if (mpreid_tune("verbose", 0))
-                fprintf(stderr, "[mpreid] attention<%d,%d,%s> on device %d: %d workgroups/CU by the occupancy API (lds %zu B, %d threads)\n",
-                        KTP, NW, EXACT ? "EXACT" : "MASKALL", dev, occ, lds, 64 * NW);
-        }
-        blocks_per_cu = blocks_per_cu_dev[slot];
-    }
+    int rc = mpreid_dyn_lds(attention_kernel<KTP, NW, EXACT>, lds);
+    if (rc) return rc;
+    static PerDeviceOnce occ_once;
+    static int occ_dev[64] = {};
+    int blocks_per_cu = 0;
+    rc = occ_once.run([&]() -> int {
+        // persistent grid: as many workgroups as fit the chip at once (LDS and the 4-waves/SIMD register
+        // bound), each walking pairs with stride gridDim
+        int occ = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &occ, reinterpret_cast<const void *>(attention_kernel<KTP, NW, EXACT>), 64 * NW, lds));
+        blocks_per_cu = occ > 0 ? occ : 1;
+        if (dev < 64) occ_dev[dev] = blocks_per_cu;
+        if (mpreid_tune("verbose", 0))
+            fprintf(stderr, "[mpreid] attention<%d,%d,%s> on device %d: %d workgroups/CU by the occupancy API (lds %zu B, %d threads)\n",
+                    KTP, NW, EXACT ? "EXACT" : "MASKALL", dev, occ, lds, 64 * NW);
+        return MPREID_OK;
+    });
+    if (rc) return rc;
+    if (!blocks_per_cu) blocks_per_cu = occ_dev[dev];   // queried by an earlier call on this device
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     const int total = B * heads;
     int grid = cus * blocks_per_cu;
@@ -1581,22 +1577,18 @@ static int launch_attention_split(const float *qkv, int B, int L, int W, int hea
                                   hipStream_t stream) {
     constexpr int KEYS = KTP * 16;
     const size_t lds = (size_t)4 * KEYS * 128 + (size_t)NW * 16 * 72 * 2 + (XKEY ? 768 : 0);
-    static PerDeviceOnce attr_once;
-    const int rc = attr_once.run([&]() -> int {
-        if (lds > 48 * 1024)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(attention_split_kernel<KTP, NW, XKEY>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (mpreid_tune("verbose", 0)) {   // once per instantiation and device, like launch_attention's line
-            int dev = 0;
-            HIP_TRY(hipGetDevice(&dev));
+    int dev = 0, cus = 256;
+    HIP_TRY(hipGetDevice(&dev));
+    int rc = mpreid_dyn_lds(attention_split_kernel<KTP, NW, XKEY>, lds);
+    if (rc) return rc;
+    static PerDeviceOnce verbose_once;   // once per instantiation and device, like launch_attention's line
+    rc = verbose_once.run([&]() -> int {
+        if (mpreid_tune("verbose", 0))
             fprintf(stderr, "[mpreid] attention_split<%d,%d%s> on device %d: lds %zu B, %d threads\n", KTP, NW, XKEY ? ",XKEY" : "",
                     dev, lds, 64 * NW);
-        }
         return MPREID_OK;
     });
     if (rc) return rc;
-    int dev = 0, cus = 256;
-    HIP_TRY(hipGetDevice(&dev));
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     const int total = B * heads;
     // persistent: as many workgroups as the LDS lets a CU hold (one for L = 129; the small test shapes fit several)
@@ -1617,11 +1609,10 @@ template <bool SPLIT>
 static int launch_attention_long(const void *qkv, int B, int L, int W, int heads, _Float16 *out, int q_tiles,
                                  hipStream_t stream) {
     const size_t lds = (size_t)2 * (SPLIT ? 4 : 2) * ATL_KB * 128;
-    static PerDeviceOnce attr_once;
-    const int rc = attr_once.run([&]() -> int {
-        if (lds > 48 * 1024)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(attention_long_kernel<SPLIT>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int rc = mpreid_dyn_lds(attention_long_kernel<SPLIT>, lds);
+    if (rc) return rc;
+    static PerDeviceOnce verbose_once;
+    rc = verbose_once.run([&]() -> int {
         if (mpreid_tune("verbose", 0)) {
             int dev = 0;
             HIP_TRY(hipGetDevice(&dev));
@@ -2055,10 +2046,8 @@ extern "C" int mpreid_vit_forward_f32(const mpreid_vit_cfg *cfg, const mpreid_vi
     // K / V of a head resident in LDS where they fit (L <= 320), streamed in chunks above that
     const bool att_chunked = (size_t)L * 64 * 4 * 2 > 160 * 1024;
     const size_t att_lds = att_chunked ? (size_t)ATF_CHUNK * 64 * 4 * 2 : (size_t)L * 64 * 4 * 2;
-    if (att_lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(att_chunked ? reinterpret_cast<const void *>(attention_f32_chunked_kernel)
-                                                : reinterpret_cast<const void *>(attention_f32_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)att_lds));
+    if ((rc = att_chunked ? mpreid_dyn_lds(attention_f32_chunked_kernel, att_lds) : mpreid_dyn_lds(attention_f32_kernel, att_lds)))
+        return rc;
     for (int l = 0; l < cfg->layers; ++l) {
         const mpreid_vit_layer &ly = w->layers[l];
         hipLaunchKernelGGL(layernorm_kernel<0>, dim3((unsigned)((v.M + 3) / 4)), dim3(256), 0, stream, x, (int64_t)v.M, W,

@@ -118,6 +118,26 @@ def test_rn50_other_resolution_vs_oracle():
     _check(got, want, 5e-3)
 
 
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two HIP devices in one process")
+def test_rn50_forward_on_a_second_device():
+    """one process, two devices: the dynamic-LDS attribute of the attention pool is per HIP device (csrc/common.h:
+    mpreid_dyn_lds), so a forward on cuda:1 after one on cuda:0 must set it again.  384x352 pixels = 24 x 22 + 1 = 529
+    pool tokens at width 16 (E = 512), 8 heads: 16 640 + 64 * 529 = 50 496 B of LDS, above the 49 152 B a launch may pass
+    without the attribute (smaller grids stay below and test nothing).  cuda:0, cuda:1, cuda:0 again: same bits."""
+    from mpreid import ops, synth
+    cfg = dict(layers=(1, 1, 1, 1), width=16, heads=8, out_dim=64, h_res=24, w_res=22)
+    sd = synth.rn50_state_dict(cfg, seed=23)
+    imgs = torch.from_numpy(synth.synthetic_images(2, 384, 352, seed=43))
+    feats = []
+    for dev in (0, 1, 0):
+        with torch.cuda.device(dev):
+            enc = ops.Rn50Encoder(cfg, sd, (384, 352), precision="fp16")
+            feats.append(enc(imgs).cpu())
+    assert feats[0].shape == (2, 576) and bool(torch.isfinite(feats[0]).all())
+    assert torch.equal(feats[1], feats[0])
+    assert torch.equal(feats[2], feats[0])
+
+
 # ---- fp32 mode (MODEL.ENCODER_PRECISION fp32): the parity mode of the RN50 tower ----
 def test_rn50_fp32_mode_vs_reference(golden):
     """every activation fp32, every convolution a GEMM on the exact fp32 matrix instruction: the reference class's own
