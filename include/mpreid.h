@@ -528,6 +528,41 @@ size_t mpreid_vit_workspace_bytes_f32(const mpreid_vit_cfg *cfg, int batch);
 int mpreid_vit_forward_f32(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w_f32, const mpreid_image_in *img, int batch,
                            const float *cv_emb_dev, float *out_dev, void *ws_dev, size_t ws_bytes,
                            mpreid_stream_t stream);
+/* ---- CLIP text tower, model/clip/model.py:609-619 after the embedding lookup (= model/make_model_uniprompt.py:58-68) ----
+ * x = prompts + pos_emb; cfg.layers residual blocks with CAUSAL attention (key j takes part in query row i iff j <= i,
+ * model/clip/model.py:582-588); ln_final; row eot[b] of prompt b; @ text_projection.  No BatchNorm neck.
+ * Precision: the SPLIT mode of the image encoder (above) and nothing else -- fp16 pair operands, hi.hi' + lo.hi' + hi.lo' on
+ * the matrix cores, fp32 accumulation, fp32 residual stream / LayerNorm / softmax.  The text side is never the throughput
+ * path, so there is NO fp16 and NO all-fp32 text mode and the config has no precision field: a caller that asks for one
+ * (mpreid.ops.TextEncoder / text_attention) gets MPREID_ERR_UNSUPPORTED.  The layers are mpreid_vit_layer entries in their
+ * SPLIT-mode layouts (pair matrices from mpreid_split_pack_f32 and the matching *_s).
+ * Limits: width == 64 * heads, width % 128 == 0, width <= 1024, 2 <= tokens <= MPREID_TEXT_MAX_TOKENS (K / V of one head stay
+ * in LDS, one workgroup per (prompt, head)); anything else is MPREID_ERR_UNSUPPORTED.  NULL pointers, batch <= 0, buffers that
+ * are not 16-byte aligned (the workspace: 256): MPREID_ERR_ARG; a short or NULL workspace: MPREID_ERR_WORKSPACE -- all of
+ * them before anything is launched.  A row of the output does not depend on the batch it is computed in, and not on the
+ * prompt rows behind its eot row.
+ * LIMIT: the CONTENTS of eot_dev (0 <= eot[b] < tokens) are device data and are NOT checked here: the caller validates them
+ * (mpreid.ops.TextEncoder.forward does, on the host).  A value outside the range reads the nearest row of its own prompt. */
+#define MPREID_TEXT_MAX_TOKENS 128
+typedef struct { int32_t tokens, width, layers, heads, out_dim; } mpreid_text_cfg;      /* 77, 512, 12, 8, 512 */
+typedef struct {                       /* device pointers; SPLIT-mode layouts of mpreid_vit_layer */
+    const float *pos_emb;              /* [tokens][width] */
+    const float *ln_final_g, *ln_final_b;
+    const float *proj;                 /* text_projection, fp32 [width][out_dim] */
+    const mpreid_vit_layer *layers;    /* HOST array of cfg.layers entries */
+} mpreid_text_weights;
+size_t mpreid_text_workspace_bytes(const mpreid_text_cfg *cfg, int batch);   /* needs no device; 0 for a NULL / empty request */
+int mpreid_text_forward(const mpreid_text_cfg *cfg, const mpreid_text_weights *w,
+                        const float *prompts_dev,   /* [B][tokens][width] fp32: the embedded prompts, positional embedding NOT added */
+                        const int32_t *eot_dev,     /* [B]: the row each prompt is read out at */
+                        int batch, float *out_dev,  /* [B][out_dim] fp32 */
+                        void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
+/* The causal attention kernel alone, for unit tests and tools.  qkv_dev fp32 [batch * tokens][3 * width] in the column
+ * layout of mpreid_vit_attention; out_dev fp16 [batch * tokens][2 * width] = [hi(width) | lo(width)]; both 16-byte aligned.
+ * Every row of every prompt is written and no other byte.  Limits and errors as above. */
+int mpreid_text_attention(const void *qkv_dev, int batch, int tokens, int width, int heads, void *out_dev,
+                          mpreid_stream_t stream);
+
 /* processor/processor_uniprompt_stage2.py:636-640: out[rows][dim] = mean over the views of
  * feats[n_views][rows][dim] (sequential sum in view order, true division), then F.normalize(p=2, dim=1,
  * eps=1e-12) when normalize != 0. */

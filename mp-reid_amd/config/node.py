@@ -72,7 +72,13 @@ def make_defaults():
     return CfgNode({
         "MODEL": {"NAME": "ViT-B-16", "DEVICE": "cuda", "DEVICE_ID": "0", "STRIDE_SIZE": [16, 16],
                   "SIE_CAMERA": False, "SIE_VIEW": False, "SIE_COE": 3.0, "NECK": "bnneck", "COS_LAYER": False,
-                  "DIST_TRAIN": False, "INIT_SEED": 7, "ENCODER_PRECISION": "split"},
+                  "DIST_TRAIN": False, "INIT_SEED": 7, "ENCODER_PRECISION": "split",
+                  # not a reference key: the row of the Uni-Prompt prompt that get_text reads out.  The reference takes it
+                  # from tokenized_prompts.argmax(-1), a tensor that is in no checkpoint.  19 = the end-of-text position of
+                  # its template "X X ... X person." (16 X): start token, 16 context tokens, `person`, `.`, end token.
+                  # DERIVED from the template, NOT checked against the BPE tokenizer (which this build does not ship);
+                  # model.prompt_learner.tokenized_prompts, when a caller sets it, takes precedence
+                  "PROMPT_EOT_INDEX": 19},
         "INPUT": {"SIZE_TRAIN": [256, 128], "SIZE_TEST": [256, 128], "PIXEL_MEAN": [0.5, 0.5, 0.5],
                   "PIXEL_STD": [0.5, 0.5, 0.5]},
         "DATASETS": {"NAMES": "synthetic", "ROOT_DIR": "", "EXP_SETTING": "", "SYNTH_QUERY": 3368,

@@ -2081,3 +2081,453 @@ extern "C" int mpreid_vit_forward_f32(const mpreid_vit_cfg *cfg, const mpreid_vi
     LAUNCH_CHECK();
     return MPREID_OK;
 }
+
+// =============================================================================================
+// CLIP text tower (model/clip/model.py:609-619 after the embedding lookup, model/make_model_uniprompt.py:58-68): the
+// residual blocks of the split mode above with a CAUSAL attention, ln_final on the end-of-text row, text_projection.
+// Split precision only: the text side is never the throughput path.
+// =============================================================================================
+// ---------------------------------------------------------------------------------------------
+// causal attention, split precision: softmax(q k^T / 8 + mask) v per (prompt, head), key j takes part in query row i iff
+// j <= i (model/clip/model.py:582-588).  Operands and product terms are attention_split_kernel's: q | k | v fp32 [M][3W],
+// K / V split into fp16 pairs while staged into LDS (the layouts of that kernel), Q in registers, every product
+// hi.hi' + lo.hi' + hi.lo' into one fp32 accumulator, P carrying 2^10, O leaving as the pair [hi(W) | lo(W)].
+// One workgroup per (prompt, head), K / V of the head resident in LDS (L <= 16 * KTP <= MPREID_TEXT_MAX_TOKENS), one
+// wave per 16-query tile (wave w owns tile w; KTP waves).  What the mask means here:
+//   * masked keys are excluded by SELECTION: their score is replaced by -3e38 before the row maximum, so exp2 gives an
+//     exact 0.  No infinity is added anywhere: this file is compiled with -ffinite-math-only (mpreid/build.py).
+//   * keys >= L of the last 16-key tile lie above every diagonal of a valid query (j >= L > i): causality alone
+//     excludes their scores, there is no separate length mask.
+//   * their K / V rows are nevertheless ZERO in LDS (selected while staging; the load address is clamped to row L - 1):
+//     a probability of 0 times stale LDS content could be NaN, and the P V steps are 32 keys wide.
+//   * key tiles wholly above a query tile's diagonal (kt > qt) are SKIPPED: no Q K products, no exponentials, and no
+//     P V step that holds only such tiles (tile qt needs the steps 0 .. qt / 2).  Only the diagonal tile is masked.
+//   * a row's bits depend on its own prompt's rows 0 .. i and on nothing else: the workgroup of a (prompt, head) pair
+//     reads that pair alone, a tile's arithmetic and its order are fixed by (qt, L), and there is no loop over pairs --
+//     the batch, the grid and the scheduling cannot reach a result.
+// ---------------------------------------------------------------------------------------------
+// The `lo` halves of split_pairs are written by inline assembly (common.h: v_fma_mixlo / mixhi_f16), and a matrix
+// instruction that reads a register as an operand needs two wait states after a vector-ALU write of it.  hipcc pads that
+// distance for its own instructions and not for a write inside an assembly string, so an MFMA scheduled one instruction
+// behind the last v_fma_mixhi_f16 read a stale upper half (seen at KTP = 8: the first P V product of every query tile used
+// the old bits in the `lo` of one probability per lane -- 3e-3 slab-relative in the output dimensions 0..15, every other
+// dimension exact).  This statement carries the two states and is tied by "+v" behind the split and ahead of the product.
+__device__ __forceinline__ void split_lo_settle(f16x8 &lo) { asm volatile("s_nop 1" : "+v"(lo)); }
+
+template <int KTP>
+__global__ __launch_bounds__(64 * KTP) void attention_causal_kernel(const float *__restrict__ qkv, int L, int W, int heads,
+                                                                    _Float16 *__restrict__ out) {
+    static_assert(KTP % 2 == 0 && KTP * 16 <= MPREID_TEXT_MAX_TOKENS, "whole 32-key P V steps, at most the token limit");
+    constexpr int NW = KTP, KEYS = KTP * 16, NT = 64 * NW;
+    constexpr int K_ITERS = KEYS * 16 / NT;   // 16-byte chunks of a [KEYS][64] fp32 array per thread: 4
+    static_assert(K_ITERS * NT == KEYS * 16, "whole staging iterations");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char *Kh = smem, *Kl = smem + KEYS * 128, *Vh = smem + 2 * KEYS * 128, *Vl = smem + 3 * KEYS * 128;
+    constexpr int OS = 72;
+    _Float16 *Ot = reinterpret_cast<_Float16 *>(smem + 4 * KEYS * 128);   // [NW][16][OS]
+    // (the wave index through readfirstlane: the compiler then knows that every `kt <= qt` below is wave-uniform and branches
+    // on scalars instead of masking lanes)
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fr = lane & 15, fq = lane >> 4;
+    const int64_t ld = 3 * (int64_t)W;
+    const int pair = blockIdx.x, b = pair / heads, h = pair - b * heads;
+    const float *base = qkv + (int64_t)b * L * ld + h * 64;
+    const float scale_log2e = 0.125f * 1.44269504088896340736f;
+
+    // ---- K / V of the head -> fp16 pairs in LDS; rows >= L are zero (loaded from the clamped row L - 1, then replaced) ----
+    float4 kr[K_ITERS], vr[K_ITERS];
+#pragma unroll
+    for (int i = 0; i < K_ITERS; ++i) {
+        const int idx = tid + i * NT, row = idx >> 4, c = idx & 15;
+        const int rc = row < L ? row : L - 1;
+        kr[i] = load_nt_f4(base + (int64_t)rc * ld + W + c * 4);
+        vr[i] = load_nt_f4(base + (int64_t)rc * ld + 2 * W + c * 4);
+    }
+    // Q of the wave's tile (B operand: B[k = d][col = query]); rows >= L are clamped and feed only columns that are not stored
+    const int qt = wave;
+    const int q = qt * 16 + fr;
+    float4 qraw[4];
+    {
+        const int qc = q < L ? q : L - 1;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const float *qp = base + (int64_t)qc * ld + ks * 32 + fq * 8;
+            qraw[2 * ks] = *reinterpret_cast<const float4 *>(qp);
+            qraw[2 * ks + 1] = *reinterpret_cast<const float4 *>(qp + 4);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < K_ITERS; ++i) {
+        const int idx = tid + i * NT, row = idx >> 4, c = idx & 15;
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 kv = row < L ? kr[i] : zero, vv = row < L ? vr[i] : zero;
+        h4_t hi, lo;
+        const int ko = row * 128 + (((c >> 1) ^ (row & 7)) << 4) + (c & 1) * 8;
+        split4(kv, hi, lo);
+        *reinterpret_cast<h4_t *>(Kh + ko) = hi;
+        *reinterpret_cast<h4_t *>(Kl + ko) = lo;
+        const int vo = row * 128 + (((c >> 1) ^ (((row >> 1) & 3) << 1)) << 4) + (c & 1) * 8;
+        split4(vv, hi, lo);
+        *reinterpret_cast<h4_t *>(Vh + vo) = hi;
+        *reinterpret_cast<h4_t *>(Vl + vo) = lo;
+    }
+    __syncthreads();   // the only workgroup barrier: a wave without a valid query row leaves after it
+    if (qt * 16 >= L) return;
+
+    f16x8 qh[2], ql[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+        const float4 a0 = qraw[2 * ks], a1 = qraw[2 * ks + 1];
+        const float qv[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+        split_pairs<8>(qv, qh[ks], ql[ks]);
+        split_lo_settle(ql[ks]);
+    }
+    // S^T = K Q^T for the key tiles 0 .. qt (wave-uniform bound); C: row = key kt * 16 + fq * 4 + r, column = query q
+    f32x4 s[KTP];
+#pragma unroll
+    for (int kt = 0; kt < KTP; ++kt) {
+        s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (kt <= qt) {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const int ko = (kt * 16 + fr) * 128 + (((ks * 4 + fq) ^ (lane & 7)) << 4);
+                const f16x8 kh = *reinterpret_cast<const f16x8 *>(Kh + ko);
+                const f16x8 kl = *reinterpret_cast<const f16x8 *>(Kl + ko);
+                s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, qh[ks], s[kt], 0, 0, 0);
+                s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl, qh[ks], s[kt], 0, 0, 0);
+                s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, ql[ks], s[kt], 0, 0, 0);
+            }
+        }
+    }
+    // the mask, by selection: key > query.  Below the diagonal tile nothing is masked (key < 16 qt <= q); key 0 <= q is
+    // never masked, so the maximum is a real score
+    float mx = -3.0e38f;
+#pragma unroll
+    for (int kt = 0; kt < KTP; ++kt) {
+        if (kt <= qt) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (kt * 16 + fq * 4 + r > q) s[kt][r] = -3.0e38f;
+            mx = fmaxf(mx, fmaxf(fmaxf(s[kt][0], s[kt][1]), fmaxf(s[kt][2], s[kt][3])));
+        }
+    }
+    mx = xor16_32_max(mx);
+    // p * 2^10 = exp2(s*c - mx*c + 10); masked entries give exp2(-huge) = 0, skipped tiles are 0 without an exponential
+    const float nmx = fmaf(-mx, scale_log2e, 10.0f);
+    float sum = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < KTP; ++kt) {
+        if (kt <= qt) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float p = __builtin_amdgcn_exp2f(fmaf(s[kt][r], scale_log2e, nmx));
+                s[kt][r] = p;
+                sum += p;
+            }
+        }
+    }
+    sum = xor16_32_sum(sum);
+    // O^T = V^T P^T over the 32-key steps that hold a computed tile; the upper half of step qt / 2 is tile qt + 1 when qt is
+    // even: P = 0 there and its V rows are the prompt's own finite rows or the zero rows >= L
+    f32x4 o[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s2 = 0; s2 < KTP / 2; ++s2) {
+        if (2 * s2 <= qt) {
+            f16x8 ph, pl;
+            {
+                const float pv[8] = {s[2 * s2][0], s[2 * s2][1], s[2 * s2][2], s[2 * s2][3],
+                                     s[2 * s2 + 1][0], s[2 * s2 + 1][1], s[2 * s2 + 1][2], s[2 * s2 + 1][3]};
+                split_pairs<8>(pv, ph, pl);
+                split_lo_settle(pl);
+            }
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                const int trq = fr >> 2, trp = fr & 3;
+                const int row0 = s2 * 32 + fq * 4 + trq, row1 = row0 + 16;
+                const int chunk = dt * 2 + (trp >> 1);
+                const int o0 = row0 * 128 + ((chunk ^ (((row0 >> 1) & 3) << 1)) << 4) + (trp & 1) * 8;
+                const int o1 = row1 * 128 + ((chunk ^ (((row1 >> 1) & 3) << 1)) << 4) + (trp & 1) * 8;
+                typedef short s8_t __attribute__((ext_vector_type(8)));
+                const att_s4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((att_lds_s4 *)(Vh + o0));
+                const att_s4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((att_lds_s4 *)(Vh + o1));
+                const att_s4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((att_lds_s4 *)(Vl + o0));
+                const att_s4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((att_lds_s4 *)(Vl + o1));
+                const s8_t vh8 = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+                const s8_t vl8 = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+                const f16x8 vh = __builtin_bit_cast(f16x8, vh8), vl = __builtin_bit_cast(f16x8, vl8);
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, ph, o[dt], 0, 0, 0);
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl, ph, o[dt], 0, 0, 0);
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, pl, o[dt], 0, 0, 0);
+            }
+        }
+    }
+    // O^T -> fp16 pair, through the wave's LDS patch as whole 128-byte rows: hi part, then lo part (attention_split_kernel)
+    const float inv = 1.0f / sum;
+    _Float16 *ot = Ot + wave * (16 * OS);
+    h4_t ohi[4], olo[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+        const float ovf[4] = {o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv};
+        split_pairs<4>(ovf, ohi[dt], olo[dt]);
+    }
+#pragma unroll
+    for (int part = 0; part < 2; ++part) {
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+            *reinterpret_cast<h4_t *>(ot + fr * OS + dt * 16 + fq * 4) = part == 0 ? ohi[dt] : olo[dt];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int row = it * 8 + (lane >> 3), ch = lane & 7;
+            const uint4 v = *reinterpret_cast<const uint4 *>(ot + row * OS + ch * 8);
+            const int qrow = qt * 16 + row;
+            if (qrow < L) store_nt16(out + ((int64_t)b * L + qrow) * 2 * W + part * W + h * 64 + ch * 8, v);
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+template <int KTP>
+static int launch_attention_causal(const float *qkv, int B, int L, int W, int heads, _Float16 *out, hipStream_t stream) {
+    constexpr int KEYS = KTP * 16;
+    const size_t lds = (size_t)4 * KEYS * 128 + (size_t)KTP * 16 * 72 * 2;
+    int rc = mpreid_dyn_lds(attention_causal_kernel<KTP>, lds);
+    if (rc) return rc;
+    static PerDeviceOnce verbose_once;
+    rc = verbose_once.run([&]() -> int {
+        if (mpreid_tune("verbose", 0)) {
+            int dev = 0;
+            HIP_TRY(hipGetDevice(&dev));
+            fprintf(stderr, "[mpreid] attention_causal<%d> on device %d: lds %zu B, %d threads\n", KTP, dev, lds, 64 * KTP);
+        }
+        return MPREID_OK;
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL((attention_causal_kernel<KTP>), dim3((unsigned)(B * heads)), dim3(64 * KTP), lds, stream, qkv, L, W, heads,
+                       out);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
+// one wave per 16-query tile and K / V for the even round-up of the key tiles (the P V steps are 32 keys wide)
+static int attention_causal_dispatch(const float *qkv, int B, int L, int W, int heads, _Float16 *out, hipStream_t stream) {
+    const int kt = (L + 15) / 16;
+    if (kt <= 2) return launch_attention_causal<2>(qkv, B, L, W, heads, out, stream);
+    if (kt <= 4) return launch_attention_causal<4>(qkv, B, L, W, heads, out, stream);
+    if (kt <= 6) return launch_attention_causal<6>(qkv, B, L, W, heads, out, stream);   // CLIP's 77 tokens
+    return launch_attention_causal<8>(qkv, B, L, W, heads, out, stream);
+}
+
+static int text_check_shape(int tokens, int width, int heads) {
+    if (heads <= 0 || width != 64 * heads || width % 128 != 0 || width > 1024) {
+        mpreid_set_error("text tower: head dim must be 64 and the width a multiple of 128 up to 1024 (width %d, heads %d)", width, heads);
+        return MPREID_ERR_UNSUPPORTED;
+    }
+    if (tokens < 2 || tokens > MPREID_TEXT_MAX_TOKENS) {
+        mpreid_set_error("text tower: %d tokens outside 2 .. %d (MPREID_TEXT_MAX_TOKENS: K / V of a head stay in LDS)", tokens,
+                         MPREID_TEXT_MAX_TOKENS);
+        return MPREID_ERR_UNSUPPORTED;
+    }
+    return MPREID_OK;
+}
+
+static int text_attention_profiled(const float *qkv, int B, int L, int W, int heads, _Float16 *out, hipStream_t s) {
+    const int64_t M = (int64_t)B * L;
+    void *ptok = mpreid_prof_begin(s);   // filed like the encoder's launches: (MPREID_PROF_ATTENTION, M, every row, pairs)
+    const int rc = attention_causal_dispatch(qkv, B, L, W, heads, out, s);
+    mpreid_prof_end(ptok, s, MPREID_PROF_ATTENTION, M, 0, 2, (double)M * 4.0 * W * 2.0 * 2);
+    return rc;
+}
+
+extern "C" int mpreid_text_attention(const void *qkv, int B, int L, int W, int heads, void *out, mpreid_stream_t stream) {
+    ARG_CHECK(qkv && out && B > 0);
+    ARG_CHECK(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 15) == 0);
+    const int rc = text_check_shape(L, W, heads);
+    if (rc) return rc;
+    ARG_CHECK((int64_t)B * heads < (int64_t)1 << 31 && (int64_t)B * L * 3 * W < (int64_t)1 << 40);
+    return text_attention_profiled(reinterpret_cast<const float *>(qkv), B, L, W, heads, reinterpret_cast<_Float16 *>(out),
+                                   (hipStream_t)stream);
+}
+
+// x[m][:] = prompts[m][:] + pos[m % L][:]   (model/make_model_uniprompt.py:59)
+__global__ __launch_bounds__(256) void text_add_pos_kernel(const float *__restrict__ prompts, const float *__restrict__ pos,
+                                                           int64_t M, int L, int W, float *__restrict__ x) {
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;   // one float4 each
+    const int w4 = W / 4;
+    if (gid >= M * w4) return;
+    const int64_t m = gid / w4;
+    const int k = (int)(gid - m * w4) * 4;
+    const float4 a = *reinterpret_cast<const float4 *>(prompts + m * W + k);
+    const float4 p = *reinterpret_cast<const float4 *>(pos + (int64_t)(m % L) * W + k);
+    *reinterpret_cast<float4 *>(x + m * W + k) = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
+}
+
+// ln_final of row eot[b] of prompt b (one wave per prompt; the arithmetic of cls_ln_kernel) -> y[b][:] fp32.  eot is device
+// data and is not validated (include/mpreid.h): the row index is clamped into the prompt so that the read stays inside x
+__global__ __launch_bounds__(256) void text_eot_ln_kernel(const float *__restrict__ x, const int32_t *__restrict__ eot, int B,
+                                                          int L, int W, const float *__restrict__ g,
+                                                          const float *__restrict__ bta, float *__restrict__ y) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    int e = eot[b];
+    e = e < 0 ? 0 : (e > L - 1 ? L - 1 : e);
+    const float *xr = x + ((int64_t)b * L + e) * W;
+    float s = 0.f;
+    for (int k = lane; k < W; k += 64) s += xr[k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    const float mean = s / (float)W;
+    float q = 0.f;
+    for (int k = lane; k < W; k += 64) {
+        const float d = xr[k] - mean;
+        q += d * d;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) q += __shfl_xor(q, off, 64);
+    const float rstd = 1.0f / sqrtf(q / (float)W + 1e-5f);
+    for (int k = lane; k < W; k += 64) y[(int64_t)b * W + k] = (xr[k] - mean) * rstd * g[k] + bta[k];
+}
+
+// out[b][o] = sum_k y[b][k] * proj[k][o]  (fp32, k ascending: cls_proj_kernel with an output row of out_dim alone)
+__global__ __launch_bounds__(256) void text_proj_kernel(const float *__restrict__ y, int B, int W, int out_dim,
+                                                        const float *__restrict__ proj, float *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float *ys = reinterpret_cast<float *>(smem);   // [HEAD_IMGS][W]
+    const int tid = threadIdx.x;
+    const int b0 = blockIdx.x * HEAD_IMGS;
+    for (int idx = tid; idx < HEAD_IMGS * W; idx += 256) {
+        const int i = idx / W, k = idx - i * W;
+        ys[idx] = (b0 + i < B) ? y[(int64_t)(b0 + i) * W + k] : 0.f;
+    }
+    __syncthreads();
+    const int o = blockIdx.y * 256 + tid;
+    if (o >= out_dim) return;
+    float acc[HEAD_IMGS];
+#pragma unroll
+    for (int i = 0; i < HEAD_IMGS; ++i) acc[i] = 0.f;
+#pragma unroll 8
+    for (int k = 0; k < W; ++k) {
+        const float pw = proj[(int64_t)k * out_dim + o];
+#pragma unroll
+        for (int i = 0; i < HEAD_IMGS; ++i) acc[i] = fmaf(ys[i * W + k], pw, acc[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < HEAD_IMGS; ++i)
+        if (b0 + i < B) out[(int64_t)(b0 + i) * out_dim + o] = acc[i];
+}
+
+struct TextLayout {
+    int64_t M, Mpad;
+    size_t x, a, qkv, hbuf, y, total;
+};
+
+static TextLayout text_layout(const mpreid_text_cfg *c, int B) {
+    TextLayout v{};
+    v.M = (int64_t)B * c->tokens;
+    v.Mpad = (int64_t)align_up((size_t)v.M, 256);   // 256-row tiles of the big GEMM kernel
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        size_t o = off;
+        off += align_up(bytes, 256);
+        return o;
+    };
+    const size_t W = (size_t)c->width;
+    v.x = take((size_t)v.Mpad * W * 4);          // residual stream, fp32
+    v.a = take((size_t)v.Mpad * 2 * W * 2);      // LN output, then attention output: fp16 pairs
+    v.qkv = take((size_t)v.Mpad * 3 * W * 4);    // q | k | v, fp32
+    v.hbuf = take((size_t)v.Mpad * 8 * W * 2);   // MLP hidden, fp16 pairs
+    v.y = take((size_t)B * W * 4);               // ln_final of the end-of-text rows
+    v.total = off;
+    return v;
+}
+
+static int text_check_cfg(const mpreid_text_cfg *c) {
+    ARG_CHECK(c != nullptr);
+    ARG_CHECK(c->layers >= 0 && c->out_dim > 0);
+    return text_check_shape(c->tokens, c->width, c->heads);
+}
+
+extern "C" size_t mpreid_text_workspace_bytes(const mpreid_text_cfg *cfg, int batch) {
+    if (!cfg || batch <= 0 || cfg->tokens <= 0 || cfg->width <= 0) return 0;
+    return text_layout(cfg, batch).total;
+}
+
+extern "C" int mpreid_text_forward(const mpreid_text_cfg *cfg, const mpreid_text_weights *w, const float *prompts,
+                                   const int32_t *eot, int B, float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
+    int rc = text_check_cfg(cfg);
+    if (rc) return rc;
+    ARG_CHECK(w && prompts && eot && out && B > 0);
+    ARG_CHECK(w->pos_emb && w->ln_final_g && w->ln_final_b && w->proj && (w->layers || cfg->layers == 0));
+    ARG_CHECK(((uintptr_t)prompts & 15) == 0 && ((uintptr_t)w->pos_emb & 15) == 0 && ((uintptr_t)eot & 3) == 0 &&
+              ((uintptr_t)out & 3) == 0);
+    ARG_CHECK((int64_t)B * cfg->tokens <= ((int64_t)1 << 31) - 256);   // GemmArgs::M is an int
+    const TextLayout v = text_layout(cfg, B);
+    if (!ws || ws_bytes < v.total) {
+        mpreid_set_error("text workspace too small: %zu < %zu", ws_bytes, v.total);
+        return MPREID_ERR_WORKSPACE;
+    }
+    ARG_CHECK(((uintptr_t)ws & 255) == 0);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int W = cfg->width, L = cfg->tokens;
+    const int M = (int)v.M, Mpad = (int)v.Mpad;
+    char *base = (char *)ws;
+    float *x = (float *)(base + v.x);
+    _Float16 *a = (_Float16 *)(base + v.a);
+    float *qkv = (float *)(base + v.qkv);
+    _Float16 *hbuf = (_Float16 *)(base + v.hbuf);
+    float *y = (float *)(base + v.y);
+    auto linear = [&](GemmArgs &g, int kdim, float wscale, int epi) -> int {   // a split-mode linear layer (mpreid_vit_forward)
+        g.K = 2 * kdim;
+        g.kseg = kdim;
+        g.oscale = wscale;
+        return launch_gemm_f16(g, epi, stream);
+    };
+    {
+        const int64_t n4 = v.M * (W / 4);
+        hipLaunchKernelGGL(text_add_pos_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, prompts, w->pos_emb, v.M, L,
+                           W, x);
+        LAUNCH_CHECK();
+    }
+    for (int l = 0; l < cfg->layers; ++l) {
+        const mpreid_vit_layer &ly = w->layers[l];
+        GemmArgs g{};
+        // x = x + out_proj(causal_attn(ln_1(x)))
+        void *ptok = mpreid_prof_begin(stream);
+        hipLaunchKernelGGL(layernorm_kernel<2>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, x, (int64_t)M, W, ly.ln1_g,
+                           ly.ln1_b, (void *)a, (int64_t)W);
+        mpreid_prof_end(ptok, stream, MPREID_PROF_LAYERNORM, M, W, 2, (double)M * W * 8.0);
+        LAUNCH_CHECK();
+        g.A = a; g.W = (const _Float16 *)ly.in_proj_w; g.M = Mpad; g.N = 3 * W;
+        g.out = qkv; g.ldo = 3 * W; g.bias = ly.in_proj_b;
+        if ((rc = linear(g, W, ly.in_proj_s, GE_S_BIAS_F32))) return rc;
+        if ((rc = text_attention_profiled(qkv, B, L, W, cfg->heads, a, stream))) return rc;
+        g = GemmArgs{};
+        g.A = a; g.W = (const _Float16 *)ly.out_proj_w; g.M = Mpad; g.N = W;
+        g.out = x; g.ldo = W; g.bias = ly.out_proj_b;
+        if ((rc = linear(g, W, ly.out_proj_s, GE_S_BIAS_RES))) return rc;
+        // x = x + c_proj(quickgelu(c_fc(ln_2(x))))
+        hipLaunchKernelGGL(layernorm_kernel<2>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, x, (int64_t)M, W, ly.ln2_g,
+                           ly.ln2_b, (void *)a, (int64_t)W);
+        LAUNCH_CHECK();
+        g = GemmArgs{};
+        g.A = a; g.W = (const _Float16 *)ly.fc_w; g.M = Mpad; g.N = 4 * W;
+        g.out = hbuf; g.ldo = 2 * 4 * W; g.bias = ly.fc_b;
+        if ((rc = linear(g, W, ly.fc_s, GE_S_BIAS_GELU))) return rc;
+        g = GemmArgs{};
+        g.A = hbuf; g.W = (const _Float16 *)ly.proj_w; g.M = Mpad; g.N = W;
+        g.out = x; g.ldo = W; g.bias = ly.proj_b;
+        if ((rc = linear(g, 4 * W, ly.proj_s, GE_S_BIAS_RES))) return rc;
+    }
+    // ln_final on the end-of-text row alone (LayerNorm is per row: the same values as normalising every row first), @ proj
+    hipLaunchKernelGGL(text_eot_ln_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, stream, x, eot, B, L, W, w->ln_final_g,
+                       w->ln_final_b, y);
+    hipLaunchKernelGGL(text_proj_kernel, dim3((unsigned)((B + HEAD_IMGS - 1) / HEAD_IMGS), (unsigned)((cfg->out_dim + 255) / 256)),
+                       dim3(256), (size_t)HEAD_IMGS * W * 4, stream, y, B, W, cfg->out_dim, w->proj, out);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}

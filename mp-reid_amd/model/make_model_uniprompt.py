@@ -6,38 +6,194 @@ projection, eval BatchNorm, concat per ``TEST.NECK_FEAT``), so the HIP encoder o
 Kept from the reference signature (:159): ``forward(x=None, label=None, get_image=False, get_text=False,
 cam_label=None, view_label=None, ..., get_image_vp=False)``:
 
-  default          -> Tensor[B, 1280]           (:203-238, what do_inference / the TTA evaluation call)
-  get_image=True   -> projected CLS [B, 512]    (:172-177)
-  get_image_vp     -> projected CLS + visual_prompt (:178-186)
+  default                      -> Tensor[B, 1280]           (:203-238, what do_inference / the TTA evaluation call)
+  get_image=True               -> projected CLS [B, 512]    (:172-177)
+  get_image_vp                 -> projected CLS + visual_prompt (:178-186)
+  label=..., get_text=True     -> text features of the identity prompts, Tensor[b, 512] (:160-170; get_raw_text is
+                                  the same branch there and returns the same thing here)
 
-The text tower (``get_text`` / ``get_raw_text``: PromptLearner + CLIP text transformer), the MLP feature fusion
-(``get_image_update``) and the multi-token variant (``get_more_image``) belong to training / TTPT and are out of
-scope: they raise NotImplementedError.  ``load_param`` accepts Uni-Prompt checkpoints and skips the keys of those
-modules (the reference would copy them into modules this build does not have).
+The text branch: ``prompt_learner`` assembles ``token_prefix | ctx_generic[label] | modality ctx | platform ctx |
+token_suffix`` (PromptLearner.forward, :334-377; torch indexing on the device) and the CLIP text transformer
+(mpreid.ops.TextEncoder: causal attention, ln_final on the end-of-text row, text_projection -- :49-68) encodes it.  The
+end-of-text row is ``prompt_learner.tokenized_prompts.argmax(-1)`` when a caller sets that tensor (the reference's
+source; it is in no checkpoint) and ``MODEL.PROMPT_EOT_INDEX`` otherwise (config/node.py).  The text-tower tensors are
+NOT registered parameters (``state_dict()`` keeps the evaluation model's keys, construction costs what it did): they
+live in a holder that is built at the first ``get_text`` call -- from the checkpoint when ``load_param`` found a
+complete set (``text_encoder.*`` and ``prompt_learner.{ctx_generic, ctx_modality, ctx_platform, token_prefix,
+token_suffix}``), else from the seeded initialisation (``MODEL.INIT_SEED``), as the image tower does with an empty
+``TEST.WEIGHT``.  ``get_text`` / ``get_raw_text`` without ``label``, the MLP feature fusion (``get_image_update``), the
+multi-token variant (``get_more_image``) and training mode raise NotImplementedError; test-time prompt tuning (a
+backward pass through the text tower) is out of scope.  ``load_param`` skips the checkpoint keys of modules this build
+does not have (``prompt_learner.visual_enhanced_net.*``, ``image_fusion_net.*``, unknown keys under those prefixes), and
+an INCOMPLETE set of text-tower tensors as a whole.
 
 ``tta_view`` (not in the reference) selects a test-time-augmentation view computed inside the patch gather; the
 reference materialises the view tensors instead (processor/processor_uniprompt_stage2.py:605-633) — passing such a
 tensor as ``x`` works as well and gives the same bits.
 """
+import numpy as np
 import torch
 import torch.nn as nn
+
+from mpreid import ops as _ops
+from mpreid import synth as _synth
 
 from . import make_model as _base
 
 _SKIPPED_PREFIXES = ("prompt_learner.", "text_encoder.", "image_fusion_net.")
+TEXT_CFG = dict(_synth.CLIP_TEXT)
+#: reference PromptLearner.__init__ (:279-296): 8 generic + 4 modality + 4 platform context tokens of width 512
+N_GENERIC_CTX, N_MODAL_CTX, N_PLAT_CTX, CTX_DIM = 8, 4, 4, 512
+PROMPT_KEYS = ("ctx_generic", "ctx_modality", "ctx_platform", "token_prefix", "token_suffix")
+
+
+def prompt_shapes(num_class, tokens=TEXT_CFG["tokens"]):
+    n_ctx = N_GENERIC_CTX + N_MODAL_CTX + N_PLAT_CTX
+    return {"ctx_generic": (num_class, N_GENERIC_CTX, CTX_DIM), "ctx_modality": (2, N_MODAL_CTX, CTX_DIM),
+            "ctx_platform": (2, N_PLAT_CTX, CTX_DIM), "token_prefix": (1, 1, CTX_DIM),
+            "token_suffix": (1, tokens - 1 - n_ctx, CTX_DIM)}
+
+
+def text_shapes(cfg=TEXT_CFG):
+    """name -> shape of every text_encoder.* tensor the tower needs (CLIP's own key names)"""
+    w = cfg["width"]
+    s = {"positional_embedding": (cfg["tokens"], w), "ln_final.weight": (w,), "ln_final.bias": (w,),
+         "text_projection": (w, cfg["out_dim"])}
+    for i in range(cfg["layers"]):
+        b = f"transformer.resblocks.{i}."
+        s.update({b + "attn.in_proj_weight": (3 * w, w), b + "attn.in_proj_bias": (3 * w,), b + "attn.out_proj.weight": (w, w),
+                  b + "attn.out_proj.bias": (w,), b + "ln_1.weight": (w,), b + "ln_1.bias": (w,), b + "ln_2.weight": (w,),
+                  b + "ln_2.bias": (w,), b + "mlp.c_fc.weight": (4 * w, w), b + "mlp.c_fc.bias": (4 * w,),
+                  b + "mlp.c_proj.weight": (w, 4 * w), b + "mlp.c_proj.bias": (w,)})
+    return s
+
+
+class PromptLearner:
+    """The prompt tensors and PromptLearner.forward (:334-377).  A plain holder, not a module: its tensors stay out of
+    the model's state_dict.  ``tokenized_prompts`` is None unless a caller sets it (see the module docstring)."""
+
+    def __init__(self):
+        self.training_stage = '1a'
+        self.tokenized_prompts = None
+        for k in PROMPT_KEYS:
+            setattr(self, k, None)
+
+    def set_training_stage(self, stage):
+        self.training_stage = stage
+
+    def set_tensors(self, tensors, device=None):
+        for k in PROMPT_KEYS:
+            setattr(self, k, tensors[k].detach().to(device=device, dtype=torch.float32).contiguous())
+
+    def forward(self, label, view=None):
+        dev = self.ctx_generic.device
+        label = torch.as_tensor(label).to(dev).long()
+        b = label.shape[0]
+        if b and (int(label.min()) < 0 or int(label.max()) >= self.ctx_generic.shape[0]):
+            raise ValueError(f"label outside 0 .. {self.ctx_generic.shape[0] - 1}")
+        generic_ctx = self.ctx_generic[label]
+        if self.training_stage == '1a':
+            modal_ctx = torch.zeros(b, N_MODAL_CTX, CTX_DIM, device=dev, dtype=generic_ctx.dtype)
+            plat_ctx = torch.zeros(b, N_PLAT_CTX, CTX_DIM, device=dev, dtype=generic_ctx.dtype)
+        elif view is not None:
+            # 0-5 cctv_rgb, 6-11 cctv_ir, 12 uav_rgb, 13 uav_ir: platform 1 iff view >= 12, modality 1 iff 6 <= view < 12 or 13
+            view = torch.as_tensor(view).to(dev).long()
+            if view.shape != label.shape:
+                raise ValueError(f"view: expected shape {tuple(label.shape)}, got {tuple(view.shape)}")
+            plat_ctx = self.ctx_platform[(view >= 12).long()]
+            modal_ctx = self.ctx_modality[(((view >= 6) & (view < 12)) | (view == 13)).long()]
+        else:
+            modal_ctx = self.ctx_modality.mean(dim=0, keepdim=True).expand(b, -1, -1)
+            plat_ctx = self.ctx_platform.mean(dim=0, keepdim=True).expand(b, -1, -1)
+        return torch.cat([self.token_prefix.expand(b, -1, -1), generic_ctx, modal_ctx, plat_ctx,
+                          self.token_suffix.expand(b, -1, -1)], dim=1)
+
+    __call__ = forward
+
+
+def seeded_text_tensors(num_class, seed):
+    """(text state dict, prompt tensors) of a model without a text checkpoint: synth.text_state_dict and N(0, 0.02) prompt
+    tensors (the reference's init of the ctx_* parameters, :287-296; prefix / suffix stand in for token embeddings)"""
+    g = torch.Generator().manual_seed(seed + 3)
+    prompt = {k: torch.randn(*s, generator=g) * 0.02 for k, s in prompt_shapes(num_class).items()}
+    return _synth.text_state_dict(TEXT_CFG, seed=seed + 2), prompt
+
+
+def split_text_checkpoint(param_dict, num_class):
+    """The text-tower part of a Uni-Prompt checkpoint -> (text state dict, prompt tensors, keys used), or None when the
+    set is incomplete or a shape does not fit the tower (the caller then skips those keys).  A complete set whose
+    ctx_generic is not [num_class, 8, 512] is a checkpoint of another label space: ValueError."""
+    text, prompt, used = {}, {}, []
+    for name, v in param_dict.items():
+        key = name.replace('module.', '')
+        if key.startswith("text_encoder."):
+            text[key[len("text_encoder."):]] = v
+            used.append(name)
+        elif key.startswith("prompt_learner.") and key[len("prompt_learner."):] in PROMPT_KEYS:
+            prompt[key[len("prompt_learner."):]] = v
+            used.append(name)
+    want_t, want_p = text_shapes(), prompt_shapes(num_class)
+    if any(k not in text or tuple(text[k].shape) != s for k, s in want_t.items()):
+        return None
+    if any(k not in prompt for k in want_p):
+        return None
+    if any(tuple(prompt[k].shape) != s for k, s in want_p.items() if k != "ctx_generic"):
+        return None
+    cg = tuple(prompt["ctx_generic"].shape)
+    if cg[1:] != want_p["ctx_generic"][1:]:
+        return None
+    if cg[0] != num_class:
+        raise ValueError(f"prompt_learner.ctx_generic holds {cg[0]} identities, the model was built for {num_class}")
+    return {k: text[k] for k in want_t}, prompt, used
 
 
 class build_transformer(_base.build_transformer):
     def __init__(self, num_classes, camera_num, view_num, cfg):
+        eot = int(getattr(cfg.MODEL, "PROMPT_EOT_INDEX", 19))
+        if not 0 <= eot < TEXT_CFG["tokens"]:
+            raise ValueError(f"MODEL.PROMPT_EOT_INDEX {eot} outside 0 .. {TEXT_CFG['tokens'] - 1}")
         super().__init__(num_classes, camera_num, view_num, cfg)
+        self.prompt_eot_index = eot
         self.prompt_dim = 512   # hard-coded in the reference (:89), whatever the backbone
-        g = torch.Generator().manual_seed(int(getattr(cfg.MODEL, "INIT_SEED", 7)) + 1)
+        self._init_seed = int(getattr(cfg.MODEL, "INIT_SEED", 7))
+        g = torch.Generator().manual_seed(self._init_seed + 1)
         self.visual_prompt = nn.Parameter(torch.randn(1, 1, self.prompt_dim, generator=g) * 0.02, requires_grad=False)
         self._proj_encoder = None
+        # the text tower: nothing is generated, copied or packed before the first get_text call
+        self.prompt_learner = PromptLearner()
+        self._text_source = None    # (text state dict, prompt tensors) of the last checkpoint that carried a complete set
+        self._text_encoder = None
 
     def _invalidate(self):
         super()._invalidate()
         self._proj_encoder = None
+
+    def text_tower(self):
+        """the device text encoder (mpreid.ops.TextEncoder), built on first use together with the prompt tensors"""
+        if self._text_encoder is None:
+            if self._text_source is None:
+                print('text tower: no checkpoint tensors, seeded initialisation (MODEL.INIT_SEED {})'.format(self._init_seed))
+                sd, prompt = seeded_text_tensors(self.num_classes, self._init_seed)
+            else:
+                sd, prompt = self._text_source
+            enc = _ops.TextEncoder(TEXT_CFG, sd, ws_tag="text")
+            self.prompt_learner.set_tensors(prompt, enc.device)
+            self._text_encoder = enc
+        return self._text_encoder
+
+    def _eot_rows(self, b):
+        tok = self.prompt_learner.tokenized_prompts
+        if tok is None:
+            return np.full(b, self.prompt_eot_index, dtype=np.int64)
+        rows = torch.as_tensor(tok).reshape(-1, TEXT_CFG["tokens"]).argmax(dim=-1).cpu().numpy()
+        if rows.shape[0] not in (1, b):
+            raise ValueError(f"prompt_learner.tokenized_prompts: {rows.shape[0]} rows for {b} prompts")
+        return np.broadcast_to(rows, (b,)).astype(np.int64)
+
+    def _text_features(self, label, view):
+        enc = self.text_tower()
+        prompts = self.prompt_learner(label, view=view)
+        return enc.forward(prompts, self._eot_rows(prompts.shape[0]))
 
     def _raw_features(self, x, view):
         """cat(x12[:,0], xproj[:,0]) before any BatchNorm, whatever TEST.NECK_FEAT says"""
@@ -56,9 +212,15 @@ class build_transformer(_base.build_transformer):
                 get_more_image=False, exp_setting=None, get_image_vp=False, tta_view=0):
         if self.training:
             raise NotImplementedError("training-mode forward is out of scope; call .eval()")
-        if get_text or get_raw_text or get_image_update or get_more_image:
-            raise NotImplementedError("text tower / feature fusion / multi-token outputs belong to Uni-Prompt "
-                                      "training and TTPT, outside the accelerated evaluation path (SURVEY.md §8f)")
+        if get_image_update or get_more_image:
+            raise NotImplementedError("feature fusion / multi-token outputs belong to Uni-Prompt training and TTPT, outside "
+                                      "the accelerated evaluation path (SURVEY.md §8f)")
+        if get_text or get_raw_text:
+            if label is None:
+                raise NotImplementedError("get_text / get_raw_text encode the identity prompts of `label` (reference "
+                                          ":168-170): pass label=...; there is no text output without it")
+            # (the reference also runs the image encoder when x is given, :161-166, and does not use the result)
+            return self._text_features(label, view)
         if get_image or get_image_vp:
             proj = self._raw_features(x, tta_view)[:, self.in_planes:]
             return proj + self.visual_prompt[0].to(proj.device) if get_image_vp else proj
@@ -67,15 +229,25 @@ class build_transformer(_base.build_transformer):
     def load_param(self, trained_path):
         param_dict = torch.load(trained_path, map_location="cpu")
         own = self.state_dict()
+        text = split_text_checkpoint(param_dict, self.num_classes)
+        used = set(text[2]) if text is not None else set()
         skipped = 0
         for name in param_dict:
             key = name.replace('module.', '')
+            if name in used:
+                continue
             if key.startswith(_SKIPPED_PREFIXES):
                 skipped += 1
                 continue
             own[key].copy_(param_dict[name])
         self._invalidate()
+        if text is not None:
+            self._text_source = ({k: v.detach().float() for k, v in text[0].items()},
+                                 {k: v.detach().float() for k, v in text[1].items()})
+            self._text_encoder = None
         print('Loading pretrained model from {}'.format(trained_path))
+        if text is not None:
+            print('  (text tower: {} tensors loaded)'.format(len(used)))
         if skipped:
             print('  ({} text-tower / fusion tensors are not used at evaluation and were skipped)'.format(skipped))
 

@@ -17,7 +17,7 @@ GEMM_F16_FAST = 1
 GEMM_F16_SPLIT3 = 2
 RERANK_AUTO, RERANK_DENSE, RERANK_SPARSE, RERANK_SPARSE_SPLIT3, RERANK_WIDE = 0, 1, 2, 3, 4
 ERR_RETRY_DENSE = -5
-ERR_ARG, ERR_UNSUPPORTED = -1, -3
+ERR_ARG, ERR_WORKSPACE, ERR_UNSUPPORTED = -1, -2, -3
 RANK_TOPK_MAX = 1024   # MPREID_RANK_TOPK_MAX
 PAIR_BOUNDS_MAX = 4096   # MPREID_PAIR_BOUNDS_MAX
 
@@ -49,6 +49,18 @@ class VitWeights(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("conv_w", "class_emb", "pos_emb", "ln_pre_g", "ln_pre_b", "ln_post_g",
                                           "ln_post_b", "proj", "bn_scale", "bn_shift", "bn_proj_scale",
                                           "bn_proj_shift")] + [("layers", C.POINTER(VitLayer)), ("conv_s", C.c_float)]
+
+
+TEXT_MAX_TOKENS = 128   # MPREID_TEXT_MAX_TOKENS
+
+
+class TextCfg(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("tokens", "width", "layers", "heads", "out_dim")]
+
+
+class TextWeights(C.Structure):
+    """mpreid_text_weights: the layers are VitLayer entries in their split-mode layouts"""
+    _fields_ = [(k, C.c_void_p) for k in ("pos_emb", "ln_final_g", "ln_final_b", "proj")] + [("layers", C.POINTER(VitLayer))]
 
 
 class ImageIn(C.Structure):
@@ -176,6 +188,10 @@ PROTOTYPES = {
     "mpreid_vit_attention": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "mpreid_vit_workspace_bytes_f32": (sz, [P(VitCfg), i32]),
     "mpreid_vit_forward_f32": (i32, [P(VitCfg), P(VitWeights), P(ImageIn), i32, vp, vp, vp, sz, vp]),
+    # the text tower: (cfg, weights, prompts, eot rows, B, out, workspace, workspace bytes, stream)
+    "mpreid_text_workspace_bytes": (sz, [P(TextCfg), i32]),
+    "mpreid_text_forward": (i32, [P(TextCfg), P(TextWeights), vp, vp, i32, vp, vp, sz, vp]),
+    "mpreid_text_attention": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "mpreid_tta_mean_f32": (i32, [vp, i32, i64, i32, i32, vp, vp]),
     "mpreid_resize_workspace_bytes": (sz, [i32, i32, i32]),
     "mpreid_resize_bilinear_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),

@@ -977,6 +977,163 @@ def vit_attention(qkv: torch.Tensor, batch: int, tokens: int, heads: int, q_tile
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# CLIP text tower (include/mpreid.h: mpreid_text_forward)
+# ----------------------------------------------------------------------------------------------
+def _text_unsupported(what: str):
+    """the text tower is built in the split precision only (include/mpreid.h): any other request is MPREID_ERR_UNSUPPORTED"""
+    raise RuntimeError(f"{what} failed (code {_lib.ERR_UNSUPPORTED}): the text tower runs in the split precision only; there is "
+                       "no fp16 and no all-fp32 text mode")
+
+
+def text_attention(qkv: torch.Tensor, batch: int, tokens: int, heads: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the text tower's causal attention step alone (mpreid_text_attention).  qkv: fp32 [batch * tokens, 3 * 64 * heads] in
+    the column layout of vit_attention; out: fp16 [batch * tokens, 2 * width] = [hi | lo], allocated (uninitialised) when
+    not passed; it may be a view into a larger buffer (the tests put guard rows around it)."""
+    _lib.require_gpu()
+    width = 64 * heads
+    assert qkv.is_cuda and qkv.is_contiguous() and tuple(qkv.shape) == (batch * tokens, 3 * width)
+    if qkv.dtype != torch.float32:
+        _text_unsupported("mpreid_text_attention")
+    if out is None:
+        out = torch.empty((batch * tokens, 2 * width), dtype=torch.float16, device=qkv.device)
+    assert out.dtype == torch.float16 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (batch * tokens, 2 * width)
+    _lib.check(_lib.load().mpreid_text_attention(_ptr(qkv), int(batch), int(tokens), width, int(heads), _ptr(out),
+                                                 _lib.stream_ptr()), "mpreid_text_attention")
+    return out
+
+
+def check_eot(eot, batch: int, tokens: int) -> np.ndarray:
+    """the read-out rows of a prompt batch as int32 [batch], validated on the host (the library does not look at them):
+    integers with 0 <= eot < tokens, else ValueError"""
+    e = eot.detach().cpu().numpy() if torch.is_tensor(eot) else np.asarray(eot)
+    if e.shape != (batch,):
+        raise ValueError(f"eot: expected shape ({batch},), got {e.shape}")
+    if e.dtype == np.bool_ or not np.issubdtype(e.dtype, np.integer):
+        raise ValueError(f"eot: expected an integer type, got {e.dtype}")
+    if batch and (int(e.min()) < 0 or int(e.max()) >= tokens):
+        raise ValueError(f"eot: rows must lie in 0 .. {tokens - 1}, got {int(e.min())} .. {int(e.max())}")
+    return np.ascontiguousarray(e, dtype=np.int32)
+
+
+class TextEncoder:
+    """Device-resident CLIP text transformer: prompts + positional embedding, causal residual blocks, ln_final on the
+    end-of-text row, text_projection (model/make_model_uniprompt.py:49-68).  Split precision.
+
+    cfg keys: tokens, width, layers, heads, out_dim (mpreid.synth.CLIP_TEXT layout); an optional 'precision' other than
+    'split' is refused.  state_dict: CLIP's own key names, optionally prefixed 'text_encoder.', numpy or torch:
+    transformer.resblocks.{l}.*, positional_embedding, ln_final.*, text_projection and, optionally, token_embedding.weight."""
+
+    CHUNK = 512   # prompts per library call: one workspace of ~0.6 GB at CLIP's size serves any batch
+
+    def __init__(self, cfg: dict, state_dict: dict, ws_tag: str = "text", device=None):
+        if cfg.get("precision", "split") != "split":
+            _text_unsupported("TextEncoder")
+        self.device = dev = device or _lib.require_gpu()
+        self.ws_tag = ws_tag
+        self.cfg = {k: int(cfg[k]) for k in ("tokens", "width", "layers", "heads", "out_dim")}
+        L = _lib.load()
+
+        def find(name):
+            for k in (name, "text_encoder." + name):
+                if k in state_dict:
+                    v = state_dict[k]
+                    return torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach()
+            return None
+
+        def get(name):
+            v = find(name)
+            if v is None:
+                raise KeyError(name)
+            return v
+
+        def f32(name, shape):
+            t = get(name).to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+            return t
+
+        scales, pack_src = {}, []
+
+        def pair(name, shape):   # a GEMM weight as VitEncoder packs it for the split precision
+            t = f32(name, shape)
+            amax = float(t.abs().max())
+            e = 9 - int(np.floor(np.log2(amax))) if amax > 0 and np.isfinite(amax) else 0
+            p = torch.empty((t.shape[0], 2 * t.shape[1]), dtype=torch.float16, device=dev)
+            _lib.check(L.mpreid_split_pack_f32(_ptr(t), t.shape[0], t.shape[1], float(2.0 ** e), _ptr(p), _lib.stream_ptr()),
+                       "mpreid_split_pack_f32")
+            pack_src.append(t)   # read by the pack kernel: alive until the synchronize below
+            scales[name] = float(2.0 ** -e)
+            return p
+
+        w, nl = self.cfg["width"], self.cfg["layers"]
+        self._keep = []   # owns every device tensor referenced by the C structs
+        self.c_cfg = _lib.TextCfg(self.cfg["tokens"], w, nl, self.cfg["heads"], self.cfg["out_dim"])
+        layers = (_lib.VitLayer * max(nl, 1))()
+        for i in range(nl):
+            b = f"transformer.resblocks.{i}"
+            t = dict(in_proj_w=pair(b + ".attn.in_proj_weight", (3 * w, w)), in_proj_b=f32(b + ".attn.in_proj_bias", (3 * w,)),
+                     out_proj_w=pair(b + ".attn.out_proj.weight", (w, w)), out_proj_b=f32(b + ".attn.out_proj.bias", (w,)),
+                     ln1_g=f32(b + ".ln_1.weight", (w,)), ln1_b=f32(b + ".ln_1.bias", (w,)),
+                     ln2_g=f32(b + ".ln_2.weight", (w,)), ln2_b=f32(b + ".ln_2.bias", (w,)),
+                     fc_w=pair(b + ".mlp.c_fc.weight", (4 * w, w)), fc_b=f32(b + ".mlp.c_fc.bias", (4 * w,)),
+                     proj_w=pair(b + ".mlp.c_proj.weight", (w, 4 * w)), proj_b=f32(b + ".mlp.c_proj.bias", (w,)))
+            for k, v in t.items():
+                self._keep.append(v)
+                setattr(layers[i], k, v.data_ptr())
+            layers[i].in_proj_s = scales[b + ".attn.in_proj_weight"]
+            layers[i].out_proj_s = scales[b + ".attn.out_proj.weight"]
+            layers[i].fc_s = scales[b + ".mlp.c_fc.weight"]
+            layers[i].proj_s = scales[b + ".mlp.c_proj.weight"]
+        self._layers = layers
+        top = dict(pos_emb=f32("positional_embedding", (self.cfg["tokens"], w)), ln_final_g=f32("ln_final.weight", (w,)),
+                   ln_final_b=f32("ln_final.bias", (w,)), proj=f32("text_projection", (w, self.cfg["out_dim"])))
+        self.c_w = _lib.TextWeights()
+        for k, v in top.items():
+            self._keep.append(v)
+            setattr(self.c_w, k, v.data_ptr())
+        self.c_w.layers = C.cast(layers, C.POINTER(_lib.VitLayer))
+        emb = find("token_embedding.weight")
+        self.token_embedding = None if emb is None else emb.to(device=dev, dtype=torch.float32).contiguous()
+        torch.cuda.current_stream().synchronize()   # the pack kernels are done with their fp32 sources
+        del pack_src[:]
+
+    @torch.no_grad()
+    def forward(self, prompts: torch.Tensor, eot, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """prompts [B, tokens, width] (the embedded prompts, positional embedding NOT added), eot [B] integer rows ->
+        fp32 [B, out_dim] on the device; at most CHUNK prompts per library call, through one workspace"""
+        L = _lib.load()
+        n_tok, w, od = self.cfg["tokens"], self.cfg["width"], self.cfg["out_dim"]
+        if prompts.dim() != 3 or tuple(prompts.shape[1:]) != (n_tok, w):
+            raise ValueError(f"prompts: expected [B, {n_tok}, {w}], got {tuple(prompts.shape)}")
+        B = prompts.shape[0]
+        e = torch.from_numpy(check_eot(eot, B, n_tok)).to(self.device)
+        x = _dev_f32(prompts, self.device)
+        if out is None:
+            out = torch.empty((B, od), dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, od)
+        for s in range(0, B, self.CHUNK):
+            n = min(B, s + self.CHUNK) - s
+            ws = _workspace(self.ws_tag, L.mpreid_text_workspace_bytes(C.byref(self.c_cfg), n), self.device)
+            _lib.check(L.mpreid_text_forward(C.byref(self.c_cfg), C.byref(self.c_w), _ptr(x[s:]), _ptr(e[s:]), n, _ptr(out[s:]),
+                                             _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_text_forward")
+        return out
+
+    __call__ = forward
+
+    def encode_tokens(self, token_ids: torch.Tensor) -> torch.Tensor:
+        """model/clip/model.py:609-619: forward(token_embedding[token_ids], token_ids.argmax(-1)); the embedding gather is
+        torch indexing on the device"""
+        if self.token_embedding is None:
+            raise ValueError("encode_tokens: the state dict had no token_embedding.weight")
+        ids = torch.as_tensor(token_ids).to(self.device).long()
+        if ids.dim() != 2 or ids.shape[1] != self.cfg["tokens"]:
+            raise ValueError(f"token_ids: expected [B, {self.cfg['tokens']}], got {tuple(ids.shape)}")
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.token_embedding.shape[0]):
+            raise ValueError(f"token_ids outside the embedding table of {self.token_embedding.shape[0]} rows")
+        return self.forward(self.token_embedding[ids], ids.argmax(dim=-1))
+
+
 def _np_getter(state_dict):
     """name -> numpy array of a ModifiedResNet state dict (keys optionally prefixed 'image_encoder.', numpy or torch)"""
     def get(name):

@@ -9,7 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 __all__ = ["clustered_features", "labels_for", "vit_state_dict", "synthetic_images", "identity_images", "VIT_B16", "rn50_state_dict",
-           "RN50"]
+           "RN50", "text_state_dict", "CLIP_TEXT"]
 
 
 def clustered_features(n: int, dim: int, sigma: float, seed: int = 1234, per_id: int = 20,
@@ -74,6 +74,49 @@ def vit_state_dict(cfg: dict, seed: int = 7, std: float = 0.02, ln_jitter: float
         ln(b + ".ln_2", sd)
     ln("ln_post", sd)
     sd["proj"] = nrm(w, od, s=scale)
+    return sd
+
+
+# CLIP's text tower (model/clip/model.py:535-547: context length 77, width 512, 8 heads, 12 layers, embed_dim 512)
+CLIP_TEXT = dict(tokens=77, width=512, layers=12, heads=8, out_dim=512)
+
+
+def text_state_dict(cfg: dict, seed: int = 21, ln_jitter: float = 0.05, bias_std: float = 0.01, vocab: int = 0):
+    """Deterministic random weights of the CLIP text tower in its own state-dict layout, the sibling of ``vit_state_dict``.
+
+    Standard deviations of model/clip/model.py:552-580: positional_embedding 0.01, in_proj width**-0.5, out_proj and
+    mlp.c_proj width**-0.5 * (2 * layers)**-0.5, mlp.c_fc (2 * width)**-0.5, text_projection width**-0.5 (token_embedding
+    0.02, only with vocab > 0).  Biases ~ N(0, bias_std) and jittered LayerNorm gamma / beta, so that their handling is
+    exercised (the reference initialises them to 0 / 1).  float32 numpy arrays."""
+    rng = np.random.default_rng(seed)
+    w, nl, od, ntok = cfg["width"], cfg["layers"], cfg["out_dim"], cfg["tokens"]
+    attn_std, fc_std = w ** -0.5, (2 * w) ** -0.5
+    proj_std = (w ** -0.5) * ((2 * max(nl, 1)) ** -0.5)
+
+    def nrm(*shape, s):
+        return (rng.standard_normal(shape) * s).astype(np.float32)
+
+    def ln(prefix, sd):
+        sd[prefix + ".weight"] = (1.0 + ln_jitter * rng.standard_normal(w)).astype(np.float32)
+        sd[prefix + ".bias"] = (ln_jitter * rng.standard_normal(w)).astype(np.float32)
+
+    sd = {"positional_embedding": nrm(ntok, w, s=0.01)}
+    for i in range(nl):
+        b = f"transformer.resblocks.{i}"
+        sd[b + ".attn.in_proj_weight"] = nrm(3 * w, w, s=attn_std)
+        sd[b + ".attn.in_proj_bias"] = nrm(3 * w, s=bias_std)
+        sd[b + ".attn.out_proj.weight"] = nrm(w, w, s=proj_std)
+        sd[b + ".attn.out_proj.bias"] = nrm(w, s=bias_std)
+        ln(b + ".ln_1", sd)
+        sd[b + ".mlp.c_fc.weight"] = nrm(4 * w, w, s=fc_std)
+        sd[b + ".mlp.c_fc.bias"] = nrm(4 * w, s=bias_std)
+        sd[b + ".mlp.c_proj.weight"] = nrm(w, 4 * w, s=proj_std)
+        sd[b + ".mlp.c_proj.bias"] = nrm(w, s=bias_std)
+        ln(b + ".ln_2", sd)
+    ln("ln_final", sd)
+    sd["text_projection"] = nrm(w, od, s=w ** -0.5)
+    if vocab > 0:
+        sd["token_embedding.weight"] = nrm(vocab, w, s=0.02)
     return sd
 
 

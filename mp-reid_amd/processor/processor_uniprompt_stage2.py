@@ -63,8 +63,9 @@ def do_inference(cfg, model, val_loader, num_query):
 
 
 def do_inference_ttpt_clipstyle(cfg, model, val_loader, num_query):
-    raise NotImplementedError("TTA + TTPT with CLIP-style image-text matching (option B) needs the text tower; "
-                              "only option A (image features) is on the accelerated path")
+    raise NotImplementedError("TTA + TTPT with CLIP-style image-text matching (option B) tunes cls_ctx by backpropagation through "
+                              "the text tower: its forward pass exists (model(label=..., get_text=True)), the prompt-tuning "
+                              "backward pass does not; only option A (image features) is on the accelerated path")
 
 
 def do_inference_ttpt_option_a(cfg, model, val_loader, num_query):
