@@ -528,6 +528,67 @@ size_t mpreid_vit_workspace_bytes_f32(const mpreid_vit_cfg *cfg, int batch);
 int mpreid_vit_forward_f32(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w_f32, const mpreid_image_in *img, int batch,
                            const float *cv_emb_dev, float *out_dev, void *ws_dev, size_t ws_bytes,
                            mpreid_stream_t stream);
+/* ---- MoE image encoder: model/clip/model.py:163-258 (MoEResidualAttentionBlock), 283-330 (MoETransformer) -------------
+ * With MODEL.MOE.ENABLED the first moe_layers blocks of the image tower replace their MLP by num_experts expert MLPs behind a
+ * softmax gate, every token goes to its top_k experts, and the routing is decided ONCE, in block 0, and reused by every
+ * later MoE block (their own gate.weight is never read).  Eval semantics (dropout is the identity):
+ *   x1 = x + attn(ln_1(x)); h = ln_2(x1)
+ *   block 0 only: logits = h @ gate^T (fp32, no bias); p = softmax(logits); (p_sel, sel) = topk(p, top_k), equal
+ *                 probabilities: the lower expert index first; w = p_sel / sum(p_sel)
+ *   out = x1 + sum over e in sel(token), ASCENDING e, of w_e * (c_proj_e(QuickGELU(c_fc_e(h))) + b_proj_e)
+ * A token's result depends on no other token or image of the batch, and not on the launch geometry.
+ * Precision: the SPLIT mode (above) and nothing else -- MPREID_VIT_F16 in cfg->precision gives MPREID_ERR_UNSUPPORTED and there
+ * is no all-fp32 MoE forward (the text tower's precedent).  Why: the router takes a discrete decision, so it runs in fp32 end
+ * to end (LayerNorm as the tower's, fmaf dot products in a fixed order, no fp16 operand anywhere), and the expert GEMMs must
+ * stay within the 2e-5 parity bound of the split mode, which fp16 operands miss by a factor of twenty.
+ * cls_only_last: honoured when the last block is a dense block, exactly as in mpreid_vit_forward.  When the last block is an
+ * MoE block (moe_layers == layers) that block runs on ALL token rows; the features are the same either way.
+ * Limits: 1 <= top_k <= min(num_experts, MPREID_MOE_MAX_TOPK), num_experts <= MPREID_MOE_MAX_EXPERTS, 0 <= moe_layers <=
+ * layers (the Python side resolves -1 and values above layers), width % 128 == 0, width == 64 * heads, batch * tokens <= MPREID_MOE_MAX_ROWS, tokens as for the dense
+ * forward: MPREID_ERR_UNSUPPORTED otherwise.  NULL or misaligned pointers (16 bytes; the workspace: 256) and batch <= 0:
+ * MPREID_ERR_ARG; a short or NULL workspace: MPREID_ERR_WORKSPACE -- all of them before anything is launched.  Stream-ordered,
+ * no host synchronisation inside: the per-expert token counts never leave the device. */
+#define MPREID_MOE_MAX_EXPERTS 64
+#define MPREID_MOE_MAX_TOPK 8
+/* token rows (batch * tokens) of one call, forward or unit seam: MPREID_ERR_UNSUPPORTED above that.  The dispatch scans its
+ * per-workgroup counts in ONE workgroup, serially over ceil(rows / 1024) entries: microseconds at the 65 536 rows of an
+ * encoder call (508 images of 129 tokens), of the order of 0.1 ms at this limit (8128 such images; estimated, not measured). */
+#define MPREID_MOE_MAX_ROWS (1 << 20)
+typedef struct {                 /* device pointers; one MoE block */
+    const float *gate_w;         /* fp32 [E][width]; read in block 0 only (may be NULL elsewhere) */
+    const void *fc_w;            /* fp16 pairs [E][4*width][2*width] = per expert the layout of mpreid_split_pack_f32 */
+    const float *fc_b;           /* [E][4*width] */
+    const void *proj_w;          /* fp16 pairs [E][width][2*4*width] */
+    const float *proj_b;         /* [E][width] */
+    const float *fc_s, *proj_s;  /* DEVICE arrays [E]: 2^-e of each expert's matrix */
+} mpreid_moe_layer;
+typedef struct {
+    int32_t num_experts, top_k, moe_layers;
+    const mpreid_moe_layer *layers;   /* HOST array of moe_layers entries */
+} mpreid_vit_moe;
+/* w->layers[l] of an MoE block (l < moe_layers): fc_w / fc_b / proj_w / proj_b / fc_s / proj_s are not read and may be NULL. */
+size_t mpreid_vit_workspace_bytes_moe(const mpreid_vit_cfg *cfg, const mpreid_vit_moe *moe, int batch);   /* 0: a bad request */
+int mpreid_vit_forward_moe(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_moe *moe,
+                           const mpreid_image_in *img, int batch, const float *cv_emb_dev, float *out_dev, void *ws_dev,
+                           size_t ws_bytes, mpreid_stream_t stream);
+/* The unit seams, for tests and tools.
+ * mpreid_moe_route: x_dev fp32 [rows][width]; ln_g / ln_b the LayerNorm in front of the gate, or BOTH NULL when x already
+ * holds h; gate_dev fp32 [E][width]; sel_out int32 [rows][K] in descending probability (ties: lower index first); w_out fp32
+ * [rows][K] renormalised (K == 1: exactly 1.0f); logits_out fp32 [rows][E] or NULL.  Rows are b * L + l (the reference's flat
+ * order is l * B + b).
+ * mpreid_moe_mlp_split: x[row] += sum over the row's experts (ascending) of w * (expert MLP of a[row]), a_pairs_dev the fp16
+ * pair rows [rows][hi(width) | lo(width)] that layernorm produces in split mode; the workspace (mpreid_moe_workspace_bytes,
+ * 256-byte aligned) holds the dispatch tables and the per-slot intermediates; nothing else is written.
+ * LIMIT: the CONTENTS of sel_dev (0 <= sel < E, distinct within a row) are device data and are NOT checked here: the caller
+ * validates them (mpreid_moe_route produces valid ones).  An entry outside the range, or a repeated one, contributes nothing. */
+size_t mpreid_moe_workspace_bytes(int64_t rows, int width, int num_experts, int top_k);   /* 0: outside the limits */
+int mpreid_moe_route(const float *x_dev, int64_t rows, int width, const float *ln_g_dev, const float *ln_b_dev,
+                     const float *gate_dev, int num_experts, int top_k, int32_t *sel_out, float *w_out, float *logits_out,
+                     mpreid_stream_t stream);
+int mpreid_moe_mlp_split(const void *a_pairs_dev, int64_t rows, int width, const int32_t *sel_dev, const float *w_dev,
+                         int num_experts, int top_k, const mpreid_moe_layer *layer, float *x_inout_dev, void *ws_dev,
+                         size_t ws_bytes, mpreid_stream_t stream);
+
 /* ---- CLIP text tower, model/clip/model.py:609-619 after the embedding lookup (= model/make_model_uniprompt.py:58-68) ----
  * x = prompts + pos_emb; cfg.layers residual blocks with CAUSAL attention (key j takes part in query row i iff j <= i,
  * model/clip/model.py:582-588); ln_final; row eot[b] of prompt b; @ text_projection.  No BatchNorm neck.
@@ -740,6 +801,13 @@ int mpreid_cast_f32_to_f16(const float *x_dev, void *y_dev, int64_t n, mpreid_st
 #define MPREID_PROF_EVALRANK 102   /* eval_rank_kernel: m = nq, n = ng; work = 4*nq*ng bytes (the matrix read once).  The splits
                                     * entry point files m = pairs, n = n_cols, k = n_splits; work = 4 * sum over the pairs of the
                                     * pair's gallery list length (the gathered distances) */
+/* the MoE kernels (csrc/moe.hip): m = token rows, n = num_experts, k = top_k (the grouped GEMMs: n = N, k = 2 * kseg).  The
+ * work figure is 0: the slot count is device data -- tools/moe_bench.py computes 2 * slots * N * 3 * kseg from the routing. */
+#define MPREID_PROF_MOE_ROUTER 110
+#define MPREID_PROF_MOE_DISPATCH 111   /* the three dispatch launches together */
+#define MPREID_PROF_MOE_FC1 112
+#define MPREID_PROF_MOE_FC2 113
+#define MPREID_PROF_MOE_COMBINE 114
 typedef struct {
     int32_t epilogue;        /* GemmEpi id of the fp16 GEMM class, or MPREID_PROF_* */
     int32_t n, k;            /* GEMM N and K (split epilogues: K = 2 * kseg halfs per operand row; 3 * kseg is executed) */

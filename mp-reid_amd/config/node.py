@@ -78,7 +78,11 @@ def make_defaults():
                   # its template "X X ... X person." (16 X): start token, 16 context tokens, `person`, `.`, end token.
                   # DERIVED from the template, NOT checked against the BPE tokenizer (which this build does not ship);
                   # model.prompt_learner.tokenized_prompts, when a caller sets it, takes precedence
-                  "PROMPT_EOT_INDEX": 19},
+                  "PROMPT_EOT_INDEX": 19,
+                  # the reference's keys (config/defaults.py:65-73): the first MOE_LAYERS blocks (-1: all) of the ViT image
+                  # tower carry NUM_EXPERTS expert MLPs behind a softmax gate, TOP_K of them per token.  DROPOUT is accepted
+                  # and unused at eval
+                  "MOE": {"ENABLED": False, "NUM_EXPERTS": 0, "TOP_K": 0, "MOE_LAYERS": 0, "DROPOUT": 0.0}},
         "INPUT": {"SIZE_TRAIN": [256, 128], "SIZE_TEST": [256, 128], "PIXEL_MEAN": [0.5, 0.5, 0.5],
                   "PIXEL_STD": [0.5, 0.5, 0.5]},
         "DATASETS": {"NAMES": "synthetic", "ROOT_DIR": "", "EXP_SETTING": "", "SYNTH_QUERY": 3368,

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "gemm_f16.h"
+#include "moe.h"
 
 // ---------------------------------------------------------------------------------------------
 // im2col: img [B][3][H][W] fp32 -> patches [MPpad][3*p*p] fp16; rows >= B*P are zero
@@ -1687,16 +1688,44 @@ extern "C" int mpreid_vit_attention(const void *qkv, int precision, int B, int L
     return rc;
 }
 
-extern "C" int mpreid_vit_forward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_image_in *img, int B,
-                                  const float *cv_emb, float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
+// The MoE forward's share of the workspace, behind the dense layout: the routing of block 0 and the routed-MLP workspace
+struct VitMoeLayout {
+    MoeLayout m;
+    size_t sel, w, moe, total;
+};
+static VitMoeLayout vit_moe_layout(const mpreid_vit_cfg *c, const mpreid_vit_moe *moe, int B) {
+    const VitLayout v = vit_layout(c, B);
+    VitMoeLayout o{};
+    o.m = moe_layout((int64_t)v.M, c->width, moe->num_experts, moe->top_k);
+    size_t off = v.total;
+    o.sel = off; off += align_up((size_t)v.M * moe->top_k * 4, 256);
+    o.w = off;   off += align_up((size_t)v.M * moe->top_k * 4, 256);
+    o.moe = off; off += o.m.total;
+    o.total = off;
+    return o;
+}
+
+// moe == nullptr: the dense tower (mpreid_vit_forward).  Otherwise blocks l < moe->moe_layers run router (l == 0 only),
+// dispatch (l == 0 only), grouped FC1 / FC2 and combine (csrc/moe.hip) in place of FC1 and FC2; every other launch is the
+// dense tower's own.
+static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_moe *moe,
+                            const mpreid_image_in *img, int B, const float *cv_emb, float *out, void *ws, size_t ws_bytes,
+                            mpreid_stream_t stream_) {
     int rc = vit_check_cfg(cfg);
     if (rc) return rc;
     mpreid_image_in in;
     if ((rc = mpreid_check_image_in(img, &in))) return rc;
     ARG_CHECK(w && out && B > 0 && w->layers);
     const VitLayout v = vit_layout(cfg, B);
-    if (!ws || ws_bytes < v.total) {
-        mpreid_set_error("vit workspace too small: %zu < %zu", ws_bytes, v.total);
+    const int n_moe = moe ? moe->moe_layers : 0;
+    VitMoeLayout vm{};
+    if (moe) {
+        ARG_CHECK(((uintptr_t)ws & 255) == 0 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)cv_emb & 3) == 0);
+        vm = vit_moe_layout(cfg, moe, B);
+    }
+    const size_t ws_need = moe ? vm.total : v.total;
+    if (!ws || ws_bytes < ws_need) {
+        mpreid_set_error("vit workspace too small: %zu < %zu", ws_bytes, ws_need);
         return MPREID_ERR_WORKSPACE;
     }
     hipStream_t stream = (hipStream_t)stream_;
@@ -1711,7 +1740,8 @@ extern "C" int mpreid_vit_forward(const mpreid_vit_cfg *cfg, const mpreid_vit_we
     _Float16 *a_cls = (_Float16 *)(base + v.a_cls);
     _Float16 *h_cls = (_Float16 *)(base + v.h_cls);
     float *y_cls = (float *)(base + v.y_cls);
-    const bool cls_last = cfg->cls_only_last != 0 && cfg->layers > 0;
+    // (an MoE block in the last position runs on all rows: include/mpreid.h)
+    const bool cls_last = cfg->cls_only_last != 0 && cfg->layers > 0 && n_moe < cfg->layers;
     // split precision mode: every linear layer runs hi.hi' + lo.hi' + hi.lo' over fp16 pairs (gemm_f16.h GE_S_*)
     const bool split = cfg->precision != MPREID_VIT_F16;
     const int pr = split ? 2 : 1;   // halfs per logical element of a GEMM operand row
@@ -1814,6 +1844,19 @@ extern "C" int mpreid_vit_forward(const mpreid_vit_cfg *cfg, const mpreid_vit_we
             hipLaunchKernelGGL(layernorm_kernel<1>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, xr,
                                (int64_t)rows, W, ly.ln2_g, ly.ln2_b, (void *)ar, (int64_t)W);
         LAUNCH_CHECK();
+        if (l < n_moe) {   // (never the CLS-only tail: xr == x, ar == a, rows == v.M)
+            char *mws = base + vm.moe;
+            int32_t *sel = (int32_t *)(base + vm.sel);
+            float *rw = (float *)(base + vm.w);
+            if (l == 0) {
+                if ((rc = moe_route_launch(xr, (int64_t)rows, W, ly.ln2_g, ly.ln2_b, moe->layers[0].gate_w, moe->num_experts,
+                                           moe->top_k, sel, rw, nullptr, stream)))
+                    return rc;
+                if ((rc = moe_dispatch_launch(sel, rw, vm.m, mws, stream))) return rc;
+            }
+            if ((rc = moe_mlp_launch(ar, vm.m, &moe->layers[l], xr, mws, stream))) return rc;
+            continue;
+        }
         g = GemmArgs{};
         g.A = ar; g.W = (const _Float16 *)ly.fc_w; g.M = rows_pad; g.N = 4 * W;
         g.out = hr; g.ldo = pr * 4 * W; g.bias = ly.fc_b;
@@ -1832,6 +1875,48 @@ extern "C" int mpreid_vit_forward(const mpreid_vit_cfg *cfg, const mpreid_vit_we
                        neck ? w->bn_proj_scale : nullptr, neck ? w->bn_proj_shift : nullptr, out);
     LAUNCH_CHECK();
     return MPREID_OK;
+}
+
+extern "C" int mpreid_vit_forward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_image_in *img, int B,
+                                  const float *cv_emb, float *out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
+    return vit_forward_impl(cfg, w, nullptr, img, B, cv_emb, out, ws, ws_bytes, stream_);
+}
+
+// ---- MoE image encoder (include/mpreid.h; kernels in csrc/moe.hip) ----
+static int vit_check_moe(const mpreid_vit_cfg *cfg, const mpreid_vit_moe *moe) {
+    int rc = vit_check_cfg(cfg);
+    if (rc) return rc;
+    ARG_CHECK(moe != nullptr);
+    if (cfg->precision != MPREID_VIT_SPLIT) {
+        mpreid_set_error("the MoE image encoder runs in the split precision mode only (include/mpreid.h)");
+        return MPREID_ERR_UNSUPPORTED;
+    }
+    if (moe->moe_layers < 0 || moe->moe_layers > cfg->layers) {
+        mpreid_set_error("MoE: moe_layers %d outside 0 .. layers (%d)", moe->moe_layers, cfg->layers);
+        return MPREID_ERR_UNSUPPORTED;
+    }
+    return moe_check_shape((int64_t)cfg->h_res * cfg->w_res + 1, cfg->width, moe->num_experts, moe->top_k);
+}
+
+extern "C" size_t mpreid_vit_workspace_bytes_moe(const mpreid_vit_cfg *cfg, const mpreid_vit_moe *moe, int batch) {
+    if (!cfg || !moe || batch <= 0 || vit_check_moe(cfg, moe)) return 0;
+    return vit_moe_layout(cfg, moe, batch).total;
+}
+
+extern "C" int mpreid_vit_forward_moe(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_moe *moe,
+                                      const mpreid_image_in *img, int B, const float *cv_emb, float *out, void *ws,
+                                      size_t ws_bytes, mpreid_stream_t stream_) {
+    int rc = vit_check_moe(cfg, moe);
+    if (rc) return rc;
+    ARG_CHECK(B > 0);
+    if ((rc = moe_check_shape((int64_t)B * (cfg->h_res * cfg->w_res + 1), cfg->width, moe->num_experts, moe->top_k))) return rc;
+    if (moe->moe_layers > 0) {
+        ARG_CHECK(moe->layers != nullptr);
+        ARG_CHECK(moe->layers[0].gate_w && ((uintptr_t)moe->layers[0].gate_w & 15) == 0);
+        for (int l = 0; l < moe->moe_layers; ++l)
+            if ((rc = moe_check_layer(&moe->layers[l]))) return rc;
+    }
+    return vit_forward_impl(cfg, w, moe, img, B, cv_emb, out, ws, ws_bytes, stream_);
 }
 
 // =============================================================================================

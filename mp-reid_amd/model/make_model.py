@@ -9,7 +9,9 @@ and ``__call__(x, label=None, cam_label=None, view_label=None) -> Tensor[B, 1280
 Not kept on purpose: the constructor does not download the pretrained CLIP archive (the reference
 does, even at test time, model/make_model.py:137-139); weights are seeded random until
 ``load_param`` is called.  MODEL.NAME 'RN50' selects the CLIP ModifiedResNet tower (2048 + 1024 = 3072-d feature,
-model/make_model.py:40-42, 82-86).  Training-mode forward and the text tower are out of scope.
+model/make_model.py:40-42, 82-86).  MODEL.MOE.ENABLED (ViT-B-16 only) creates the MoE parameters of the reference's
+MoETransformer under ``image_encoder.`` (experts.{e}.c_fc / c_proj, gate.weight) and runs the MoE tower.
+Training-mode forward and the text tower are out of scope.
 """
 import numpy as np
 import torch
@@ -55,6 +57,15 @@ class build_transformer(nn.Module):
         self.vit_cfg = dict(h_res=self.h_resolution, w_res=self.w_resolution, patch=16, stride=stride, width=768,
                             layers=12, heads=12, out_dim=512)
         seed = int(getattr(cfg.MODEL, "INIT_SEED", 7))
+        # MODEL.MOE (reference config/defaults.py:65-73): expert MLPs in the first MOE_LAYERS blocks of the ViT tower
+        moe = getattr(cfg.MODEL, "MOE", None)
+        moe_on = moe is not None and bool(moe.get("ENABLED", False))
+        if moe_on and self.model_name == 'RN50':
+            raise NotImplementedError("MODEL.MOE.ENABLED with MODEL.NAME 'RN50': the reference's ModifiedResNet takes no MoE "
+                                      "arguments (model/clip/model.py:509-517); MoE is a ViT-B-16 option")
+        if moe_on:
+            self.vit_cfg.update(num_experts=int(moe.get("NUM_EXPERTS", 0)), top_k=int(moe.get("TOP_K", 0)),
+                                moe_layers=int(moe.get("MOE_LAYERS", 0)))
         if self.model_name == 'RN50':
             # model/clip/model.py:509-516: heads = width * 32 // 64, attention-pool grid = h_resolution x w_resolution
             self.rn_cfg = dict(_synth.RN50, h_res=self.h_resolution, w_res=self.w_resolution)
@@ -70,6 +81,11 @@ class build_transformer(nn.Module):
                     mod.register_buffer(parts[-1], torch.from_numpy(np.asarray(v)))
                 else:
                     _put(self, path, torch.from_numpy(v))
+        elif moe_on and _ops.resolve_moe(self.vit_cfg)[2]:
+            # the MoE parameters under the reference's key names (experts.{e}.c_fc / c_proj, gate.weight in every MoE block),
+            # so that load_param of an MoE checkpoint finds them
+            for k, v in _synth.vit_moe_state_dict(self.vit_cfg, seed=seed, std=0.02, ln_jitter=0.0).items():
+                _put(self, "image_encoder." + k, torch.from_numpy(v))
         else:
             for k, v in _synth.vit_state_dict(self.vit_cfg, seed=seed).items():
                 _put(self, "image_encoder." + k, torch.from_numpy(v))

@@ -51,6 +51,18 @@ class VitWeights(C.Structure):
                                           "bn_proj_shift")] + [("layers", C.POINTER(VitLayer)), ("conv_s", C.c_float)]
 
 
+MOE_MAX_EXPERTS, MOE_MAX_TOPK = 64, 8   # MPREID_MOE_MAX_EXPERTS, MPREID_MOE_MAX_TOPK
+
+
+class MoeLayer(C.Structure):
+    """mpreid_moe_layer: one MoE block; fc_s / proj_s are DEVICE arrays [E]"""
+    _fields_ = [(k, C.c_void_p) for k in ("gate_w", "fc_w", "fc_b", "proj_w", "proj_b", "fc_s", "proj_s")]
+
+
+class VitMoe(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("num_experts", "top_k", "moe_layers")] + [("layers", C.POINTER(MoeLayer))]
+
+
 TEXT_MAX_TOKENS = 128   # MPREID_TEXT_MAX_TOKENS
 
 
@@ -188,6 +200,12 @@ PROTOTYPES = {
     "mpreid_vit_attention": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "mpreid_vit_workspace_bytes_f32": (sz, [P(VitCfg), i32]),
     "mpreid_vit_forward_f32": (i32, [P(VitCfg), P(VitWeights), P(ImageIn), i32, vp, vp, vp, sz, vp]),
+    # the MoE image encoder: the forward takes the MoE description behind the weights; then the unit seams
+    "mpreid_vit_workspace_bytes_moe": (sz, [P(VitCfg), P(VitMoe), i32]),
+    "mpreid_vit_forward_moe": (i32, [P(VitCfg), P(VitWeights), P(VitMoe), P(ImageIn), i32, vp, vp, vp, sz, vp]),
+    "mpreid_moe_workspace_bytes": (sz, [i64, i32, i32, i32]),
+    "mpreid_moe_route": (i32, [vp, i64, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "mpreid_moe_mlp_split": (i32, [vp, i64, i32, vp, vp, i32, i32, P(MoeLayer), vp, vp, sz, vp]),
     # the text tower: (cfg, weights, prompts, eot rows, B, out, workspace, workspace bytes, stream)
     "mpreid_text_workspace_bytes": (sz, [P(TextCfg), i32]),
     "mpreid_text_forward": (i32, [P(TextCfg), P(TextWeights), vp, vp, i32, vp, vp, sz, vp]),

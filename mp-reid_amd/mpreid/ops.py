@@ -666,23 +666,77 @@ def _forward_images(enc, img, u8: bool, view: int = 0, cv_emb=None, pixel_mean=(
     assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, enc.feat_dim)
     desc = _lib.ImageIn(mean=(C.c_float * 3)(*[float(x) for x in pixel_mean]),
                         std=(C.c_float * 3)(*[float(x) for x in pixel_std]), view=int(view))
+    moe_arg = []
+    if getattr(enc, "c_moe", None) is not None:   # the MoE image tower: its own entry points, the MoE description behind the weights
+        fwd, ws_query, tag, moe_arg = "mpreid_vit_forward_moe", "mpreid_vit_workspace_bytes_moe", "_moe", [C.byref(enc.c_moe)]
     for s in range(0, B, step) if step else (0,):
         n = min(B, s + step) - s if step else B
-        ws = _workspace(enc.ws_tag + tag, getattr(L, ws_query)(C.byref(enc.c_cfg), n), enc.device)
+        ws = _workspace(enc.ws_tag + tag, getattr(L, ws_query)(C.byref(enc.c_cfg), *moe_arg, n), enc.device)
         desc.f32_dev, desc.u8_hwc_dev = (None, img[s:].data_ptr()) if u8 else (img[s:].data_ptr(), None)
         cv_arg = [_ptr(None if cv is None else cv[s:s + n])] if enc.tower == "vit" else []
-        _lib.check(getattr(L, fwd)(C.byref(enc.c_cfg), C.byref(getattr(enc, weights)), C.byref(desc), n, *cv_arg, _ptr(out[s:]),
-                                   _ptr(ws), ws.numel(), _lib.stream_ptr()), fwd)
+        _lib.check(getattr(L, fwd)(C.byref(enc.c_cfg), C.byref(getattr(enc, weights)), *moe_arg, C.byref(desc), n, *cv_arg,
+                                   _ptr(out[s:]), _ptr(ws), ws.numel(), _lib.stream_ptr()), fwd)
     return out
 
 
 # ----------------------------------------------------------------------------------------------
 # ViT image encoder
 # ----------------------------------------------------------------------------------------------
+def resolve_moe(cfg: dict):
+    """(num_experts, top_k, MoE blocks) of a tower cfg, as model/clip/model.py:294, 391 resolve them: the tower uses MoE when
+    num_experts > 0 and top_k > 0; moe_layers == -1 means every block, a value above layers is clipped.  (0, 0, 0) for the
+    dense tower, which includes moe_layers == 0."""
+    n_exp, top_k, n_moe = (int(cfg.get(k, 0) or 0) for k in ("num_experts", "top_k", "moe_layers"))
+    if not (n_exp > 0 and top_k > 0):
+        return 0, 0, 0
+    if top_k > n_exp:
+        raise ValueError(f"MoE: top_k {top_k} > num_experts {n_exp} (torch.topk raises in the reference)")
+    if n_moe < -1:
+        raise ValueError(f"MoE: moe_layers {n_moe} (use -1 for every block)")
+    n_moe = cfg["layers"] if n_moe == -1 else min(n_moe, cfg["layers"])
+    if n_moe == 0:
+        return 0, 0, 0
+    if n_exp > _lib.MOE_MAX_EXPERTS or top_k > _lib.MOE_MAX_TOPK:
+        raise NotImplementedError(f"MoE: num_experts {n_exp} / top_k {top_k} above the kernels' limits "
+                                  f"({_lib.MOE_MAX_EXPERTS} / {_lib.MOE_MAX_TOPK})")
+    return n_exp, top_k, n_moe
+
+
+def _moe_gate_key(i: int) -> str:
+    return f"transformer.resblocks.{i}.gate.weight"
+
+
+def _moe_expert_keys(i: int, e: int):
+    return [f"transformer.resblocks.{i}.experts.{e}.{lin}.{p}" for lin in ("c_fc", "c_proj") for p in ("weight", "bias")]
+
+
+def check_moe_request(cfg: dict, state_dict: dict, precision: str):
+    """Host-side validation of an MoE tower request; returns resolve_moe(cfg).  ValueError: top_k > num_experts, missing
+    expert / gate keys; NotImplementedError: a precision other than 'split'.  Gates of blocks 1.. are accepted and unused."""
+    n_exp, top_k, n_moe = resolve_moe(cfg)
+    if not n_moe:
+        return 0, 0, 0
+    if precision != "split":
+        raise NotImplementedError(f"the MoE image encoder runs in precision 'split' only (asked for {precision!r}): the router is "
+                                  "fp32 end to end and the expert GEMMs keep the split mode's parity bound")
+    have = lambda k: k in state_dict or "image_encoder." + k in state_dict   # noqa: E731
+    for i in range(n_moe):
+        missing = [k for e in range(n_exp) for k in _moe_expert_keys(i, e) if not have(k)]
+        if i == 0 and not have(_moe_gate_key(0)):
+            missing.append(_moe_gate_key(0))
+        if missing:
+            raise ValueError(f"MoE block {i}: the state dict lacks {len(missing)} expert / gate keys, first {missing[0]!r} "
+                             f"(num_experts {n_exp}, moe_layers {n_moe})")
+    return n_exp, top_k, n_moe
+
+
 class VitEncoder:
     """Device-resident CLIP ViT image encoder + feature head.
 
-    cfg keys: h_res, w_res, patch, stride, width, layers, heads, out_dim (mpreid.synth.VIT_B16 layout).
+    cfg keys: h_res, w_res, patch, stride, width, layers, heads, out_dim (mpreid.synth.VIT_B16 layout); optional
+    num_experts, top_k, moe_layers (default 0: the dense tower): the MoE tower of model/clip/model.py:283-330, whose first
+    moe_layers blocks (-1: all) carry experts.{e}.c_fc / c_proj and gate.weight in place of mlp.* (split precision only;
+    include/mpreid.h "MoE image encoder").
     state_dict: CLIP VisionTransformer key names (optionally prefixed 'image_encoder.'), numpy or torch.
     bn: optional dict(bottleneck=(weight, bias, running_mean, running_var), bottleneck_proj=(...)).
     """
@@ -701,6 +755,9 @@ class VitEncoder:
             raise ValueError("ln_fold: the folded-LayerNorm form of the split mode was removed in round 4 (0.5 % slower than the plain "
                              "split mode and not reproducible run to run at small batches: include/mpreid.h)")
         self.precision = precision
+        # MoE tower (num_experts, top_k, moe_layers in cfg; all 0 = the dense tower): the first n_moe blocks carry experts.
+        # Checked on the host, before a device is asked for.
+        n_exp, top_k, n_moe = check_moe_request(cfg, state_dict, precision)
         self.device = device or _lib.require_gpu()
         self.ws_tag = ws_tag   # encoders that run concurrently on different streams need distinct workspaces
         self.cfg = dict(cfg)
@@ -749,18 +806,41 @@ class VitEncoder:
             t = dict(in_proj_w=f16(b + ".attn.in_proj_weight"), in_proj_b=f32(b + ".attn.in_proj_bias"),
                      out_proj_w=f16(b + ".attn.out_proj.weight"), out_proj_b=f32(b + ".attn.out_proj.bias"),
                      ln1_g=f32(b + ".ln_1.weight"), ln1_b=f32(b + ".ln_1.bias"),
-                     ln2_g=f32(b + ".ln_2.weight"), ln2_b=f32(b + ".ln_2.bias"),
-                     fc_w=f16(b + ".mlp.c_fc.weight"), fc_b=f32(b + ".mlp.c_fc.bias"),
-                     proj_w=f16(b + ".mlp.c_proj.weight"), proj_b=f32(b + ".mlp.c_proj.bias"))
+                     ln2_g=f32(b + ".ln_2.weight"), ln2_b=f32(b + ".ln_2.bias"))
+            if i >= n_moe:
+                t.update(fc_w=f16(b + ".mlp.c_fc.weight"), fc_b=f32(b + ".mlp.c_fc.bias"),
+                         proj_w=f16(b + ".mlp.c_proj.weight"), proj_b=f32(b + ".mlp.c_proj.bias"))
             for k, v in t.items():
                 keep(v)
                 setattr(layers[i], k, v.data_ptr())
             if precision == "split":
                 layers[i].in_proj_s = scales[b + ".attn.in_proj_weight"]
                 layers[i].out_proj_s = scales[b + ".attn.out_proj.weight"]
-                layers[i].fc_s = scales[b + ".mlp.c_fc.weight"]
-                layers[i].proj_s = scales[b + ".mlp.c_proj.weight"]
+                if i >= n_moe:
+                    layers[i].fc_s = scales[b + ".mlp.c_fc.weight"]
+                    layers[i].proj_s = scales[b + ".mlp.c_proj.weight"]
         self._layers = layers
+        self.c_moe = None
+        if n_moe:
+            # per MoE block the experts' matrices stacked [E][out][2 * in] as fp16 pairs, one power-of-two scale per expert
+            # matrix by the rule of the dense layers (device arrays: the grouped GEMM looks its expert up on the device);
+            # block 0's gate as fp32.  The gates of later blocks are never read (model/clip/model.py:314-322).
+            moe_layers = (_lib.MoeLayer * n_moe)()
+            for i in range(n_moe):
+                b = f"transformer.resblocks.{i}"
+                t = {}
+                for part, key in (("fc", "c_fc"), ("proj", "c_proj")):
+                    t[part + "_w"], t[part + "_s"] = _pack_experts(
+                        (get(f"{b}.experts.{e}.{key}.weight") for e in range(n_exp)), n_exp, dev)
+                    t[part + "_b"] = torch.stack([f32(f"{b}.experts.{e}.{key}.bias") for e in range(n_exp)]).contiguous()
+                if i == 0:
+                    t["gate_w"] = f32(_moe_gate_key(0))
+                    assert tuple(t["gate_w"].shape) == (n_exp, w), t["gate_w"].shape
+                for k, v in t.items():
+                    keep(v)
+                    setattr(moe_layers[i], k, v.data_ptr())
+            self._moe_layers = moe_layers
+            self.c_moe = _lib.VitMoe(n_exp, top_k, n_moe, C.cast(moe_layers, C.POINTER(_lib.MoeLayer)))
         top = dict(conv_w=f16("conv1.weight", (w, -1)), class_emb=f32("class_embedding"),
                    pos_emb=f32("positional_embedding"), ln_pre_g=f32("ln_pre.weight"), ln_pre_b=f32("ln_pre.bias"),
                    ln_post_g=f32("ln_post.weight"), ln_post_b=f32("ln_post.bias"), proj=f32("proj"))
@@ -974,6 +1054,98 @@ def vit_attention(qkv: torch.Tensor, batch: int, tokens: int, heads: int, q_tile
     _lib.check(_lib.load().mpreid_vit_attention(_ptr(qkv), _lib.VIT_SPLIT if split else _lib.VIT_F16, int(batch), int(tokens),
                                                 width, int(heads), int(q_tiles), _ptr(out), _lib.stream_ptr()),
                "mpreid_vit_attention")
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
+# MoE unit seams (include/mpreid.h: mpreid_moe_route, mpreid_moe_mlp_split)
+# ----------------------------------------------------------------------------------------------
+def moe_route(x: torch.Tensor, gate: torch.Tensor, top_k: int, ln=None, want_logits: bool = False):
+    """The router alone.  x fp32 [rows, width]: the residual stream with ln = (gamma, beta) of the LayerNorm in front of the
+    gate, or h itself with ln = None; gate fp32 [E, width].  Returns (sel int32 [rows, K], w fp32 [rows, K], logits fp32
+    [rows, E] or None)."""
+    dev = _lib.require_gpu()
+    x, gate = _dev_f32(x, dev), _dev_f32(gate, dev)
+    rows, width = x.shape
+    E, K = gate.shape[0], int(top_k)
+    assert gate.shape[1] == width, (gate.shape, width)
+    g = b = None
+    if ln is not None:
+        g, b = _dev_f32(ln[0], dev), _dev_f32(ln[1], dev)
+        assert g.numel() == width and b.numel() == width
+    sel = torch.empty((rows, max(K, 1)), dtype=torch.int32, device=dev)
+    w = torch.empty((rows, max(K, 1)), dtype=torch.float32, device=dev)
+    logits = torch.empty((rows, E), dtype=torch.float32, device=dev) if want_logits else None
+    _lib.check(_lib.load().mpreid_moe_route(_ptr(x), rows, width, _ptr(g), _ptr(b), _ptr(gate), E, K, _ptr(sel), _ptr(w),
+                                            _ptr(logits), _lib.stream_ptr()), "mpreid_moe_route")
+    return sel, w, logits
+
+
+def _pack_experts(mats, n_exp: int, dev):
+    """n_exp fp32 matrices [out, in] (an iterable: one is on the device at a time) -> (fp16 pairs [E][out][2 * in], fp32 [E] of
+    2^-e): every expert is packed straight into its slice of the one stacked buffer, with the scale rule of the dense layers --
+    W * 2^e has its largest finite |entry| in [2^9, 2^10)"""
+    pair, sc = None, []
+    for e, m in enumerate(mats):
+        t = _dev_f32(m, dev)
+        n, k = t.shape
+        if pair is None:
+            pair = torch.empty((n_exp, n, 2 * k), dtype=torch.float16, device=dev)
+        assert tuple(pair.shape[1:]) == (n, 2 * k), (e, tuple(t.shape))
+        amax = float(torch.nan_to_num(t, nan=0.0, posinf=0.0, neginf=0.0).abs().max())
+        ex = 9 - int(np.floor(np.log2(amax))) if amax > 0 else 0
+        _lib.check(_lib.load().mpreid_split_pack_f32(_ptr(t), n, k, float(2.0 ** ex), _ptr(pair[e]), _lib.stream_ptr()),
+                   "mpreid_split_pack_f32")
+        sc.append(2.0 ** -ex)
+        torch.cuda.current_stream().synchronize()   # t is a temporary
+    assert len(sc) == n_exp
+    return pair, torch.tensor(sc, dtype=torch.float32, device=dev)
+
+
+def pack_moe_layer(fc_w, fc_b, proj_w, proj_b, dev=None):
+    """fp32 expert weights [E, 4w, w], [E, 4w], [E, w, 4w], [E, w] -> (mpreid_moe_layer, the tensors it points to): the stacked
+    fp16 pair layout and one power-of-two scale per expert matrix, as VitEncoder builds them (no gate)."""
+    dev = dev or _lib.require_gpu()
+    keep = []
+    layer = _lib.MoeLayer()
+    for part, wt, bs in (("fc", fc_w, fc_b), ("proj", proj_w, proj_b)):
+        bs = _dev_f32(bs, dev)
+        pair, s = _pack_experts(wt, len(wt), dev)
+        keep += [bs, pair, s]
+        setattr(layer, part + "_w", pair.data_ptr())
+        setattr(layer, part + "_b", bs.data_ptr())
+        setattr(layer, part + "_s", s.data_ptr())
+    torch.cuda.current_stream().synchronize()
+    return layer, keep
+
+
+def moe_mlp(a_pairs: torch.Tensor, sel: torch.Tensor, w: torch.Tensor, layer, x: torch.Tensor, num_experts: int,
+            ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The routed MLP alone, in place: x[row] += sum over the row's experts (ascending) of w * expert(a[row]).  a_pairs fp16
+    [rows, 2 * width] ([hi | lo], split_pairs(h)); sel int32 / w fp32 [rows, K]; layer from pack_moe_layer; x fp32, at least
+    rows rows of width.  ws: a uint8 workspace of the caller's (the tests put guard bytes behind it)."""
+    dev = _lib.require_gpu()
+    L = _lib.load()
+    rows, K = sel.shape
+    width = a_pairs.shape[1] // 2
+    assert a_pairs.dtype == torch.float16 and a_pairs.is_cuda and a_pairs.is_contiguous() and a_pairs.shape[0] >= rows
+    assert sel.dtype == torch.int32 and w.dtype == torch.float32 and sel.is_contiguous() and w.is_contiguous() and w.shape == sel.shape
+    assert x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and x.shape[0] >= rows and x.shape[1] == width
+    if ws is None:
+        ws = _workspace("moe_mlp", L.mpreid_moe_workspace_bytes(rows, width, int(num_experts), K), dev)
+    _lib.check(L.mpreid_moe_mlp_split(_ptr(a_pairs), rows, width, _ptr(sel), _ptr(w), int(num_experts), K, C.byref(layer), _ptr(x),
+                                      _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_moe_mlp_split")
+    return x
+
+
+def split_pairs_f32(x: torch.Tensor) -> torch.Tensor:
+    """fp32 [rows, k] -> fp16 pairs [rows, 2k] = [hi | lo] (mpreid_split_pack_f32 with scale 1): the operand layout of the
+    split mode, as layernorm writes it"""
+    dev = _lib.require_gpu()
+    x = _dev_f32(x, dev)
+    out = torch.empty((x.shape[0], 2 * x.shape[1]), dtype=torch.float16, device=dev)
+    _lib.check(_lib.load().mpreid_split_pack_f32(_ptr(x), x.shape[0], x.shape[1], 1.0, _ptr(out), _lib.stream_ptr()),
+               "mpreid_split_pack_f32")
     return out
 
 

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["clustered_features", "labels_for", "vit_state_dict", "synthetic_images", "identity_images", "VIT_B16", "rn50_state_dict",
+__all__ = ["clustered_features", "labels_for", "vit_state_dict", "vit_moe_state_dict", "synthetic_images", "identity_images", "VIT_B16", "rn50_state_dict",
            "RN50", "text_state_dict", "CLIP_TEXT"]
 
 
@@ -74,6 +74,34 @@ def vit_state_dict(cfg: dict, seed: int = 7, std: float = 0.02, ln_jitter: float
         ln(b + ".ln_2", sd)
     ln("ln_post", sd)
     sd["proj"] = nrm(w, od, s=scale)
+    return sd
+
+
+def vit_moe_state_dict(cfg: dict, seed: int = 7, std: float = 0.05, ln_jitter: float = 0.1, gate_std: float = 0.3):
+    """``vit_state_dict`` for an MoE tower (model/clip/model.py:283-302): cfg carries num_experts, top_k, moe_layers (-1: all);
+    the first min(moe_layers, layers) blocks have ``experts.{e}.c_fc / c_proj`` (weight, bias) and ``gate.weight``
+    [num_experts, width] in place of ``mlp.*``, the remaining blocks are dense.  Every MoE block gets a gate, as in a
+    checkpoint of the reference; only block 0's is ever read.  gate_std ~ 0.2-0.5 separates the experts: at the 0.02 of the
+    other weights the gate is near uniform and every routing margin is tiny.  float32 numpy arrays."""
+    n_exp, n_moe = int(cfg["num_experts"]), int(cfg["moe_layers"])
+    w, nl = cfg["width"], cfg["layers"]
+    n_moe = nl if n_moe == -1 else min(n_moe, nl)
+    sd = vit_state_dict(cfg, seed=seed, std=std, ln_jitter=ln_jitter)
+    rng = np.random.default_rng([seed, 0x4D6F45])   # a stream of its own: the dense keys keep vit_state_dict's bytes
+
+    def nrm(*shape, s):
+        return (rng.standard_normal(shape) * s).astype(np.float32)
+
+    for i in range(n_moe):
+        b = f"transformer.resblocks.{i}"
+        for k in ("c_fc.weight", "c_fc.bias", "c_proj.weight", "c_proj.bias"):
+            del sd[f"{b}.mlp.{k}"]
+        for e in range(n_exp):
+            sd[f"{b}.experts.{e}.c_fc.weight"] = nrm(4 * w, w, s=std)
+            sd[f"{b}.experts.{e}.c_fc.bias"] = nrm(4 * w, s=0.01)
+            sd[f"{b}.experts.{e}.c_proj.weight"] = nrm(w, 4 * w, s=std)
+            sd[f"{b}.experts.{e}.c_proj.bias"] = nrm(w, s=0.01)
+        sd[f"{b}.gate.weight"] = nrm(n_exp, w, s=gate_std)
     return sd
 
 
