@@ -1467,6 +1467,20 @@ __global__ __launch_bounds__(256) void gather_cls_kernel(const float *__restrict
 // ---------------------------------------------------------------------------------------------
 // host driver
 // ---------------------------------------------------------------------------------------------
+// the 256-byte aligned bump cursor of every workspace layout in this file: take(bytes) -> offset
+struct WsCursor {
+    size_t off = 0;
+    size_t operator()(size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; }
+};
+
+// What every tower's kernels ask of (width, heads): 64-wide heads (the attention kernels), a width that is a multiple of
+// 128 up to 1024 (LayerNorm, the GEMM tiles).  Each caller words its own error.
+enum { SHAPE_OK = 0, SHAPE_HEAD_DIM, SHAPE_WIDTH };
+static int check_width_heads(int width, int heads) {
+    if (heads <= 0 || width != heads * 64) return SHAPE_HEAD_DIM;
+    return (width % 128 != 0 || width > 1024) ? SHAPE_WIDTH : SHAPE_OK;
+}
+
 struct VitLayout {
     int L, P, M, Mpad, MPpad, Kp, Bpad;
     size_t patches, x, a, qkv, hbuf, x_cls, a_cls, h_cls, y_cls, total;
@@ -1480,12 +1494,7 @@ static VitLayout vit_layout(const mpreid_vit_cfg *c, int B) {
     v.Mpad = (int)align_up((size_t)v.M, 256);   // 256-row tiles of the big GEMM kernel
     v.MPpad = (int)align_up((size_t)B * v.P, 256);
     v.Kp = 3 * c->patch * c->patch;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += align_up(bytes, 256);
-        return o;
-    };
+    WsCursor take;
     const size_t W = (size_t)c->width;
     // split precision mode: every GEMM operand is an fp16 pair (2x the halfs per row), q | k | v are fp32
     const size_t pr = c->precision != MPREID_VIT_F16 ? 2 : 1;
@@ -1499,7 +1508,7 @@ static VitLayout vit_layout(const mpreid_vit_cfg *c, int B) {
     v.a_cls = take((size_t)v.Bpad * W * 2 * pr);
     v.h_cls = take((size_t)v.Bpad * 4 * W * 2 * pr);
     v.y_cls = take((size_t)v.Bpad * W * 4);
-    v.total = off;
+    v.total = take.off;
     return v;
 }
 
@@ -1512,11 +1521,12 @@ static int vit_check_cfg(const mpreid_vit_cfg *c) {
         return MPREID_ERR_UNSUPPORTED;
     }
     ARG_CHECK(c->precision == MPREID_VIT_F16 || c->precision == MPREID_VIT_SPLIT);
-    if (c->width != c->heads * 64) {
+    const int shape = check_width_heads(c->width, c->heads);
+    if (shape == SHAPE_HEAD_DIM) {
         mpreid_set_error("head dim must be 64 (width %d, heads %d)", c->width, c->heads);
         return MPREID_ERR_UNSUPPORTED;
     }
-    if (c->width % 128 != 0 || c->width > 1024 || (3 * c->patch * c->patch) % 64 != 0 || c->patch % 8 != 0) {
+    if (shape != SHAPE_OK || (3 * c->patch * c->patch) % 64 != 0 || c->patch % 8 != 0) {
         mpreid_set_error("unsupported ViT geometry (width %d, patch %d)", c->width, c->patch);
         return MPREID_ERR_UNSUPPORTED;
     }
@@ -1667,6 +1677,11 @@ static int attention_dispatch(const _Float16 *qkv, int B, int L, int W, int head
     return launch_attention<16, 8, true>(qkv, B, L, W, heads, out, q_tiles, stream);   // kt is 15 or 16: always EXACT
 }
 
+// the work figure of every attention profile record, algorithmic bytes: k, v of every token + q and the output of the query rows
+static double attention_bytes(int64_t M, int64_t qrows, int W, int pr) {
+    return ((double)M * 2.0 * W + (double)qrows * 2.0 * W) * 2.0 * pr;
+}
+
 extern "C" int mpreid_vit_attention(const void *qkv, int precision, int B, int L, int W, int heads, int q_tiles, void *out,
                                     mpreid_stream_t stream) {
     ARG_CHECK(qkv && out && B > 0 && heads > 0 && q_tiles >= 0);
@@ -1684,7 +1699,7 @@ extern "C" int mpreid_vit_attention(const void *qkv, int precision, int B, int L
                                                   reinterpret_cast<_Float16 *>(out), q_tiles, s)
                        : attention_dispatch(reinterpret_cast<const _Float16 *>(qkv), B, L, W, heads,
                                             reinterpret_cast<_Float16 *>(out), q_tiles, s);
-    mpreid_prof_end(ptok, s, MPREID_PROF_ATTENTION, M, q_tiles ? 1 : 0, pr, ((double)M * 2.0 * W + (double)qrows * 2.0 * W) * 2.0 * pr);
+    mpreid_prof_end(ptok, s, MPREID_PROF_ATTENTION, M, q_tiles ? 1 : 0, pr, attention_bytes(M, qrows, W, pr));
     return rc;
 }
 
@@ -1697,17 +1712,112 @@ static VitMoeLayout vit_moe_layout(const mpreid_vit_cfg *c, const mpreid_vit_moe
     const VitLayout v = vit_layout(c, B);
     VitMoeLayout o{};
     o.m = moe_layout((int64_t)v.M, c->width, moe->num_experts, moe->top_k);
-    size_t off = v.total;
-    o.sel = off; off += align_up((size_t)v.M * moe->top_k * 4, 256);
-    o.w = off;   off += align_up((size_t)v.M * moe->top_k * 4, 256);
-    o.moe = off; off += o.m.total;
-    o.total = off;
+    WsCursor take{v.total};
+    o.sel = take((size_t)v.M * moe->top_k * 4);
+    o.w = take((size_t)v.M * moe->top_k * 4);
+    o.moe = take(o.m.total);   // (a multiple of 256 already: moe_layout)
+    o.total = take.off;
     return o;
 }
 
-// moe == nullptr: the dense tower (mpreid_vit_forward).  Otherwise blocks l < moe->moe_layers run router (l == 0 only),
-// dispatch (l == 0 only), grouped FC1 / FC2 and combine (csrc/moe.hip) in place of FC1 and FC2; every other launch is the
-// dense tower's own.
+// The residual block of the fp16 / split towers, x += out_proj(attn(ln_1(x))); x += mlp(ln_2(x)): the ONE launch sequence of
+// the image tower (dense and MoE) and the text tower.  Two parts: the image tower's CLS-only tail block gathers the CLS rows
+// between them and runs the second part on those alone.
+struct BlockCtx {
+    hipStream_t stream;
+    bool split;   // every linear layer runs hi.hi' + lo.hi' + hi.lo' over fp16 pairs (gemm_f16.h GE_S_*); q | k | v are fp32
+    int pr;       // halfs per logical element of a GEMM operand row: 2 in the split mode, else 1
+    int W, heads, B, L;
+};
+enum AttnKind { ATTN_ALL_ROWS, ATTN_CLS_TILE, ATTN_CAUSAL };   // which query rows / which mask the block's attention runs
+
+static int linear(const BlockCtx &c, GemmArgs &g, int kdim, float wscale, int epi_f16, int epi_split) {
+    g.K = c.pr * kdim;
+    if (c.split) {
+        g.kseg = kdim;
+        g.oscale = wscale;
+    }
+    return launch_gemm_f16(g, c.split ? epi_split : epi_f16, c.stream);
+}
+
+// a = ln(x) as the next GEMM's operand (fp16, or the fp16 pair of the split mode)
+static void block_layernorm(const BlockCtx &c, const float *x, int rows, const float *g, const float *b, _Float16 *a) {
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (c.split)
+        hipLaunchKernelGGL(layernorm_kernel<2>, grid, dim3(256), 0, c.stream, x, (int64_t)rows, c.W, g, b, (void *)a, (int64_t)c.W);
+    else
+        hipLaunchKernelGGL(layernorm_kernel<1>, grid, dim3(256), 0, c.stream, x, (int64_t)rows, c.W, g, b, (void *)a, (int64_t)c.W);
+}
+
+static int attention_causal_dispatch(const float *qkv, int B, int L, int W, int heads, _Float16 *out, hipStream_t stream);
+
+// the attention of a block inside its profiling bracket: class (MPREID_PROF_ATTENTION, M, CLS tile only, pr)
+static int attention_profiled(const BlockCtx &c, const void *qkv, _Float16 *out, AttnKind kind) {
+    const int64_t M = (int64_t)c.B * c.L;
+    const int cls = kind == ATTN_CLS_TILE ? 1 : 0;   // q_tiles of the dispatchers: the first 16-query tile, or 0 = all rows
+    void *ptok = mpreid_prof_begin(c.stream);
+    int rc;
+    if (kind == ATTN_CAUSAL)
+        rc = attention_causal_dispatch(reinterpret_cast<const float *>(qkv), c.B, c.L, c.W, c.heads, out, c.stream);
+    else if (c.split)
+        rc = attention_split_dispatch(reinterpret_cast<const float *>(qkv), c.B, c.L, c.W, c.heads, out, cls, c.stream);
+    else
+        rc = attention_dispatch(reinterpret_cast<const _Float16 *>(qkv), c.B, c.L, c.W, c.heads, out, cls, c.stream);
+    mpreid_prof_end(ptok, c.stream, MPREID_PROF_ATTENTION, M, cls, c.pr, attention_bytes(M, cls ? (int64_t)c.B * 16 : M, c.W, c.pr));
+    return rc;
+}
+
+// a = attn(in_proj(ln_1(x))) over the M rows of x (Mpad: the GEMM's row count)
+static int block_attention_part(const BlockCtx &c, const mpreid_vit_layer &ly, const float *x, _Float16 *a, void *qkv, int M,
+                                int Mpad, AttnKind kind) {
+    const int W = c.W;
+    void *ptok = mpreid_prof_begin(c.stream);
+    block_layernorm(c, x, M, ly.ln1_g, ly.ln1_b, a);
+    mpreid_prof_end(ptok, c.stream, MPREID_PROF_LAYERNORM, M, W, c.pr, (double)M * W * (4.0 + 2.0 * c.pr));
+    LAUNCH_CHECK();
+    GemmArgs g{};
+    g.A = a; g.W = (const _Float16 *)ly.in_proj_w; g.M = Mpad; g.N = 3 * W;
+    g.out = qkv; g.ldo = 3 * W; g.bias = ly.in_proj_b;
+    const int rc = linear(c, g, W, ly.in_proj_s, GE_BIAS_F16, GE_S_BIAS_F32);
+    return rc ? rc : attention_profiled(c, qkv, a, kind);
+}
+
+// xr += out_proj(ar); xr += mlp(ln_2(xr)) over `rows` rows (rows_pad: the GEMMs' row count; hr: the MLP's hidden buffer).
+// Blocks l < moe->moe_layers of an MoE tower (moe != nullptr; vm places its workspace share behind base) run router and
+// dispatch (l == 0 only), grouped FC1 / FC2 and combine (csrc/moe.hip) in place of FC1 and FC2
+static int block_mlp_part(const BlockCtx &c, const mpreid_vit_layer &ly, float *xr, _Float16 *ar, _Float16 *hr, int rows,
+                          int rows_pad, const mpreid_vit_moe *moe, int l, const VitMoeLayout *vm, char *base) {
+    const int W = c.W;
+    int rc;
+    GemmArgs g{};
+    g.A = ar; g.W = (const _Float16 *)ly.out_proj_w; g.M = rows_pad; g.N = W;
+    g.out = xr; g.ldo = W; g.bias = ly.out_proj_b;
+    if ((rc = linear(c, g, W, ly.out_proj_s, GE_BIAS_RES, GE_S_BIAS_RES))) return rc;
+    block_layernorm(c, xr, rows, ly.ln2_g, ly.ln2_b, ar);
+    LAUNCH_CHECK();
+    if (moe && l < moe->moe_layers) {
+        char *mws = base + vm->moe;
+        int32_t *sel = (int32_t *)(base + vm->sel);
+        float *rw = (float *)(base + vm->w);
+        if (l == 0) {
+            if ((rc = moe_route_launch(xr, (int64_t)rows, W, ly.ln2_g, ly.ln2_b, moe->layers[0].gate_w, moe->num_experts,
+                                       moe->top_k, sel, rw, nullptr, c.stream)))
+                return rc;
+            if ((rc = moe_dispatch_launch(sel, rw, vm->m, mws, c.stream))) return rc;
+        }
+        return moe_mlp_launch(ar, vm->m, &moe->layers[l], xr, mws, c.stream);
+    }
+    g = GemmArgs{};
+    g.A = ar; g.W = (const _Float16 *)ly.fc_w; g.M = rows_pad; g.N = 4 * W;
+    g.out = hr; g.ldo = c.pr * 4 * W; g.bias = ly.fc_b;
+    if ((rc = linear(c, g, W, ly.fc_s, GE_BIAS_GELU, GE_S_BIAS_GELU))) return rc;
+    g = GemmArgs{};
+    g.A = hr; g.W = (const _Float16 *)ly.proj_w; g.M = rows_pad; g.N = W;
+    g.out = xr; g.ldo = W; g.bias = ly.proj_b;
+    return linear(c, g, 4 * W, ly.proj_s, GE_BIAS_RES, GE_S_BIAS_RES);
+}
+
+// moe == nullptr: the dense tower (mpreid_vit_forward).  Otherwise blocks l < moe->moe_layers run the routed MLP.
 static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_moe *moe,
                             const mpreid_image_in *img, int B, const float *cv_emb, float *out, void *ws, size_t ws_bytes,
                             mpreid_stream_t stream_) {
@@ -1742,17 +1852,8 @@ static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights 
     float *y_cls = (float *)(base + v.y_cls);
     // (an MoE block in the last position runs on all rows: include/mpreid.h)
     const bool cls_last = cfg->cls_only_last != 0 && cfg->layers > 0 && n_moe < cfg->layers;
-    // split precision mode: every linear layer runs hi.hi' + lo.hi' + hi.lo' over fp16 pairs (gemm_f16.h GE_S_*)
     const bool split = cfg->precision != MPREID_VIT_F16;
-    const int pr = split ? 2 : 1;   // halfs per logical element of a GEMM operand row
-    auto linear = [&](GemmArgs &g, int kdim, float wscale, int epi_f16, int epi_split) -> int {
-        g.K = pr * kdim;
-        if (split) {
-            g.kseg = kdim;
-            g.oscale = wscale;
-        }
-        return launch_gemm_f16(g, split ? epi_split : epi_f16, stream);
-    };
+    const BlockCtx ctx{stream, split, split ? 2 : 1, W, cfg->heads, B, L};
 
     // patch embedding (conv1, no bias) + positional embedding; CLS row; ln_pre
     {
@@ -1787,7 +1888,7 @@ static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights 
         g.m_valid = B * v.P;
         g.P = v.P;
         g.L = L;
-        rc = linear(g, v.Kp, w->conv_s, GE_PATCH, GE_S_PATCH);
+        rc = linear(ctx, g, v.Kp, w->conv_s, GE_PATCH, GE_S_PATCH);
         if (rc) return rc;
         hipLaunchKernelGGL(cls_token_kernel, dim3((unsigned)B), dim3(256), 0, stream, w->class_emb, w->pos_emb, cv_emb,
                            B, L, W, x);
@@ -1797,74 +1898,17 @@ static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights 
     }
     for (int l = 0; l < cfg->layers; ++l) {
         const mpreid_vit_layer &ly = w->layers[l];
-        const bool tail = cls_last && (l == cfg->layers - 1);
-        GemmArgs g{};
-        // x = x + out_proj(attn(ln_1(x)))
-        void *ptok = mpreid_prof_begin(stream);
-        if (split)
-            hipLaunchKernelGGL(layernorm_kernel<2>, dim3((unsigned)((v.M + 3) / 4)), dim3(256), 0, stream, x,
-                               (int64_t)v.M, W, ly.ln1_g, ly.ln1_b, (void *)a, (int64_t)W);
-        else
-            hipLaunchKernelGGL(layernorm_kernel<1>, dim3((unsigned)((v.M + 3) / 4)), dim3(256), 0, stream, x,
-                               (int64_t)v.M, W, ly.ln1_g, ly.ln1_b, (void *)a, (int64_t)W);
-        mpreid_prof_end(ptok, stream, MPREID_PROF_LAYERNORM, v.M, W, pr, (double)v.M * W * (4.0 + 2.0 * pr));
-        LAUNCH_CHECK();
-        g = GemmArgs{};
-        g.A = a; g.W = (const _Float16 *)ly.in_proj_w; g.M = v.Mpad; g.N = 3 * W;
-        g.out = qkv; g.ldo = 3 * W; g.bias = ly.in_proj_b;
-        if ((rc = linear(g, W, ly.in_proj_s, GE_BIAS_F16, GE_S_BIAS_F32))) return rc;
         // in the last block only the CLS row reaches the output (model/make_model.py:98-100): the
         // attention runs the first query tile only and everything after it runs on the B CLS rows.
-        ptok = mpreid_prof_begin(stream);
-        if (split)
-            rc = attention_split_dispatch(reinterpret_cast<const float *>(qkv), B, L, W, cfg->heads, a, tail ? 1 : 0, stream);
-        else
-            rc = attention_dispatch(qkv, B, L, W, cfg->heads, a, tail ? 1 : 0, stream);
-        // algorithmic bytes: k, v of every token + q and the output of the query rows (all of them, or the CLS tile's 16)
-        mpreid_prof_end(ptok, stream, MPREID_PROF_ATTENTION, v.M, tail ? 1 : 0, pr,
-                        ((double)v.M * 2.0 * W + (tail ? (double)B * 16 : (double)v.M) * 2.0 * W) * 2.0 * pr);
-        if (rc) return rc;
-        float *xr = x;
-        _Float16 *ar = a, *hr = hbuf;
-        int rows = v.M, rows_pad = v.Mpad;
-        if (tail) {
-            hipLaunchKernelGGL(gather_cls_kernel, dim3((unsigned)B), dim3(256), 0, stream, x, a, B, L, W, pr * W, x_cls, a_cls);
+        const bool tail = cls_last && (l == cfg->layers - 1);
+        if ((rc = block_attention_part(ctx, ly, x, a, qkv, v.M, v.Mpad, tail ? ATTN_CLS_TILE : ATTN_ALL_ROWS))) return rc;
+        if (tail) {   // (never an MoE block)
+            hipLaunchKernelGGL(gather_cls_kernel, dim3((unsigned)B), dim3(256), 0, stream, x, a, B, L, W, ctx.pr * W, x_cls, a_cls);
             LAUNCH_CHECK();
-            xr = x_cls; ar = a_cls; hr = h_cls; rows = B; rows_pad = v.Bpad;
         }
-        g = GemmArgs{};
-        g.A = ar; g.W = (const _Float16 *)ly.out_proj_w; g.M = rows_pad; g.N = W;
-        g.out = xr; g.ldo = W; g.bias = ly.out_proj_b;
-        if ((rc = linear(g, W, ly.out_proj_s, GE_BIAS_RES, GE_S_BIAS_RES))) return rc;
-        // x = x + c_proj(quickgelu(c_fc(ln_2(x))))
-        if (split)
-            hipLaunchKernelGGL(layernorm_kernel<2>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, xr,
-                               (int64_t)rows, W, ly.ln2_g, ly.ln2_b, (void *)ar, (int64_t)W);
-        else
-            hipLaunchKernelGGL(layernorm_kernel<1>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, xr,
-                               (int64_t)rows, W, ly.ln2_g, ly.ln2_b, (void *)ar, (int64_t)W);
-        LAUNCH_CHECK();
-        if (l < n_moe) {   // (never the CLS-only tail: xr == x, ar == a, rows == v.M)
-            char *mws = base + vm.moe;
-            int32_t *sel = (int32_t *)(base + vm.sel);
-            float *rw = (float *)(base + vm.w);
-            if (l == 0) {
-                if ((rc = moe_route_launch(xr, (int64_t)rows, W, ly.ln2_g, ly.ln2_b, moe->layers[0].gate_w, moe->num_experts,
-                                           moe->top_k, sel, rw, nullptr, stream)))
-                    return rc;
-                if ((rc = moe_dispatch_launch(sel, rw, vm.m, mws, stream))) return rc;
-            }
-            if ((rc = moe_mlp_launch(ar, vm.m, &moe->layers[l], xr, mws, stream))) return rc;
-            continue;
-        }
-        g = GemmArgs{};
-        g.A = ar; g.W = (const _Float16 *)ly.fc_w; g.M = rows_pad; g.N = 4 * W;
-        g.out = hr; g.ldo = pr * 4 * W; g.bias = ly.fc_b;
-        if ((rc = linear(g, W, ly.fc_s, GE_BIAS_GELU, GE_S_BIAS_GELU))) return rc;
-        g = GemmArgs{};
-        g.A = hr; g.W = (const _Float16 *)ly.proj_w; g.M = rows_pad; g.N = W;
-        g.out = xr; g.ldo = W; g.bias = ly.proj_b;
-        if ((rc = linear(g, 4 * W, ly.proj_s, GE_BIAS_RES, GE_S_BIAS_RES))) return rc;
+        if ((rc = tail ? block_mlp_part(ctx, ly, x_cls, a_cls, h_cls, B, v.Bpad, moe, l, &vm, base)
+                       : block_mlp_part(ctx, ly, x, a, hbuf, v.M, v.Mpad, moe, l, &vm, base)))
+            return rc;
     }
     const bool neck = cfg->neck_after != 0 && w->bn_scale && w->bn_proj_scale;
     hipLaunchKernelGGL(cls_ln_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, stream, cls_last ? x_cls : x,
@@ -2069,19 +2113,14 @@ static VitLayoutF32 vit_layout_f32(const mpreid_vit_cfg *c, int B) {
     v.L = v.P + 1;
     v.M = B * v.L;
     v.Kp = 3 * c->patch * c->patch;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += align_up(bytes, 256);
-        return o;
-    };
+    WsCursor take;
     v.patches = take((size_t)B * v.P * v.Kp * 4);
     v.x = take((size_t)v.M * c->width * 4);
     v.a = take((size_t)v.M * c->width * 4);
     v.qkv = take((size_t)v.M * 3 * c->width * 4);
     v.hbuf = take((size_t)v.M * 4 * c->width * 4);
     v.y_cls = take((size_t)B * c->width * 4);
-    v.total = off;
+    v.total = take.off;
     return v;
 }
 
@@ -2097,10 +2136,6 @@ extern "C" int mpreid_vit_forward_f32(const mpreid_vit_cfg *cfg, const mpreid_vi
     mpreid_image_in in;
     if ((rc = mpreid_check_image_in(img, &in))) return rc;
     ARG_CHECK(w && out && B > 0 && w->layers);
-    if (cfg->width / cfg->heads != 64) {
-        mpreid_set_error("fp32 attention: head dimension %d != 64", cfg->width / cfg->heads);
-        return MPREID_ERR_UNSUPPORTED;
-    }
     const VitLayoutF32 v = vit_layout_f32(cfg, B);
     if (!ws || ws_bytes < v.total) {
         mpreid_set_error("vit fp32 workspace too small: %zu < %zu", ws_bytes, v.total);
@@ -2408,7 +2443,7 @@ static int attention_causal_dispatch(const float *qkv, int B, int L, int W, int 
 }
 
 static int text_check_shape(int tokens, int width, int heads) {
-    if (heads <= 0 || width != 64 * heads || width % 128 != 0 || width > 1024) {
+    if (check_width_heads(width, heads) != SHAPE_OK) {
         mpreid_set_error("text tower: head dim must be 64 and the width a multiple of 128 up to 1024 (width %d, heads %d)", width, heads);
         return MPREID_ERR_UNSUPPORTED;
     }
@@ -2421,11 +2456,8 @@ static int text_check_shape(int tokens, int width, int heads) {
 }
 
 static int text_attention_profiled(const float *qkv, int B, int L, int W, int heads, _Float16 *out, hipStream_t s) {
-    const int64_t M = (int64_t)B * L;
-    void *ptok = mpreid_prof_begin(s);   // filed like the encoder's launches: (MPREID_PROF_ATTENTION, M, every row, pairs)
-    const int rc = attention_causal_dispatch(qkv, B, L, W, heads, out, s);
-    mpreid_prof_end(ptok, s, MPREID_PROF_ATTENTION, M, 0, 2, (double)M * 4.0 * W * 2.0 * 2);
-    return rc;
+    // filed like the encoder's launches: (MPREID_PROF_ATTENTION, M, every row, pairs)
+    return attention_profiled(BlockCtx{s, true, 2, W, heads, B, L}, qkv, out, ATTN_CAUSAL);
 }
 
 extern "C" int mpreid_text_attention(const void *qkv, int B, int L, int W, int heads, void *out, mpreid_stream_t stream) {
@@ -2515,19 +2547,14 @@ static TextLayout text_layout(const mpreid_text_cfg *c, int B) {
     TextLayout v{};
     v.M = (int64_t)B * c->tokens;
     v.Mpad = (int64_t)align_up((size_t)v.M, 256);   // 256-row tiles of the big GEMM kernel
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += align_up(bytes, 256);
-        return o;
-    };
+    WsCursor take;
     const size_t W = (size_t)c->width;
     v.x = take((size_t)v.Mpad * W * 4);          // residual stream, fp32
     v.a = take((size_t)v.Mpad * 2 * W * 2);      // LN output, then attention output: fp16 pairs
     v.qkv = take((size_t)v.Mpad * 3 * W * 4);    // q | k | v, fp32
     v.hbuf = take((size_t)v.Mpad * 8 * W * 2);   // MLP hidden, fp16 pairs
     v.y = take((size_t)B * W * 4);               // ln_final of the end-of-text rows
-    v.total = off;
+    v.total = take.off;
     return v;
 }
 
@@ -2559,19 +2586,13 @@ extern "C" int mpreid_text_forward(const mpreid_text_cfg *cfg, const mpreid_text
     ARG_CHECK(((uintptr_t)ws & 255) == 0);
     hipStream_t stream = (hipStream_t)stream_;
     const int W = cfg->width, L = cfg->tokens;
-    const int M = (int)v.M, Mpad = (int)v.Mpad;
     char *base = (char *)ws;
     float *x = (float *)(base + v.x);
     _Float16 *a = (_Float16 *)(base + v.a);
     float *qkv = (float *)(base + v.qkv);
     _Float16 *hbuf = (_Float16 *)(base + v.hbuf);
     float *y = (float *)(base + v.y);
-    auto linear = [&](GemmArgs &g, int kdim, float wscale, int epi) -> int {   // a split-mode linear layer (mpreid_vit_forward)
-        g.K = 2 * kdim;
-        g.kseg = kdim;
-        g.oscale = wscale;
-        return launch_gemm_f16(g, epi, stream);
-    };
+    const BlockCtx ctx{stream, true, 2, W, cfg->heads, B, L};   // the split mode's blocks (mpreid_vit_forward), causal
     {
         const int64_t n4 = v.M * (W / 4);
         hipLaunchKernelGGL(text_add_pos_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, prompts, w->pos_emb, v.M, L,
@@ -2580,33 +2601,8 @@ extern "C" int mpreid_text_forward(const mpreid_text_cfg *cfg, const mpreid_text
     }
     for (int l = 0; l < cfg->layers; ++l) {
         const mpreid_vit_layer &ly = w->layers[l];
-        GemmArgs g{};
-        // x = x + out_proj(causal_attn(ln_1(x)))
-        void *ptok = mpreid_prof_begin(stream);
-        hipLaunchKernelGGL(layernorm_kernel<2>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, x, (int64_t)M, W, ly.ln1_g,
-                           ly.ln1_b, (void *)a, (int64_t)W);
-        mpreid_prof_end(ptok, stream, MPREID_PROF_LAYERNORM, M, W, 2, (double)M * W * 8.0);
-        LAUNCH_CHECK();
-        g.A = a; g.W = (const _Float16 *)ly.in_proj_w; g.M = Mpad; g.N = 3 * W;
-        g.out = qkv; g.ldo = 3 * W; g.bias = ly.in_proj_b;
-        if ((rc = linear(g, W, ly.in_proj_s, GE_S_BIAS_F32))) return rc;
-        if ((rc = text_attention_profiled(qkv, B, L, W, cfg->heads, a, stream))) return rc;
-        g = GemmArgs{};
-        g.A = a; g.W = (const _Float16 *)ly.out_proj_w; g.M = Mpad; g.N = W;
-        g.out = x; g.ldo = W; g.bias = ly.out_proj_b;
-        if ((rc = linear(g, W, ly.out_proj_s, GE_S_BIAS_RES))) return rc;
-        // x = x + c_proj(quickgelu(c_fc(ln_2(x))))
-        hipLaunchKernelGGL(layernorm_kernel<2>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, x, (int64_t)M, W, ly.ln2_g,
-                           ly.ln2_b, (void *)a, (int64_t)W);
-        LAUNCH_CHECK();
-        g = GemmArgs{};
-        g.A = a; g.W = (const _Float16 *)ly.fc_w; g.M = Mpad; g.N = 4 * W;
-        g.out = hbuf; g.ldo = 2 * 4 * W; g.bias = ly.fc_b;
-        if ((rc = linear(g, W, ly.fc_s, GE_S_BIAS_GELU))) return rc;
-        g = GemmArgs{};
-        g.A = hbuf; g.W = (const _Float16 *)ly.proj_w; g.M = Mpad; g.N = W;
-        g.out = x; g.ldo = W; g.bias = ly.proj_b;
-        if ((rc = linear(g, 4 * W, ly.proj_s, GE_S_BIAS_RES))) return rc;
+        if ((rc = block_attention_part(ctx, ly, x, a, qkv, (int)v.M, (int)v.Mpad, ATTN_CAUSAL))) return rc;
+        if ((rc = block_mlp_part(ctx, ly, x, a, hbuf, (int)v.M, (int)v.Mpad, nullptr, l, nullptr, nullptr))) return rc;
     }
     // ln_final on the end-of-text row alone (LayerNorm is per row: the same values as normalising every row first), @ proj
     hipLaunchKernelGGL(text_eot_ln_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, stream, x, eot, B, L, W, w->ln_final_g,

@@ -730,6 +730,66 @@ def check_moe_request(cfg: dict, state_dict: dict, precision: str):
     return n_exp, top_k, n_moe
 
 
+def _state_getter(state_dict, prefix: str):
+    """get(name) -> the torch tensor of a state dict (numpy or torch) whose keys may carry `prefix`; a missing key is a
+    KeyError, or None with required=False"""
+    def get(name, required=True):
+        for k in (name, prefix + name):
+            if k in state_dict:
+                v = state_dict[k]
+                return torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach()
+        if required:
+            raise KeyError(name)
+        return None
+    return get
+
+
+def _split_pack(t: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """A GEMM weight of the split precision: fp32 device matrix [n, k] -> (pair, 2^-e, src).  pair: fp16 [n][hi(k) | lo(k)] of
+    W * 2^e with the largest finite |entry| in [2^9, 2^10) -- hi + lo carries 22 significant bits of every entry that matters,
+    and 2^-e is undone in the GEMM epilogue (exact); written into `out` when given.  src: what the pack kernel reads on the
+    current stream, so the caller keeps it alive until it has synchronised."""
+    src = t.contiguous()
+    n, k = src.shape
+    amax = float(torch.nan_to_num(src, nan=0.0, posinf=0.0, neginf=0.0).abs().max())
+    e = 9 - int(np.floor(np.log2(amax))) if amax > 0 else 0
+    if out is None:
+        out = torch.empty((n, 2 * k), dtype=torch.float16, device=src.device)
+    _lib.check(_lib.load().mpreid_split_pack_f32(_ptr(src), n, k, float(2.0 ** e), _ptr(out), _lib.stream_ptr()),
+               "mpreid_split_pack_f32")
+    return out, float(2.0 ** -e), src
+
+
+def _gemm_weight(t: torch.Tensor, precision: str):
+    """fp32 device matrix -> (the GEMM operand of `precision`, its scale, the pack source): _split_pack, or the fp16 / fp32
+    matrix itself with no scale and nothing to keep"""
+    if precision == "split":
+        return _split_pack(t)
+    return (t.contiguous() if precision == "fp32" else t.to(torch.float16).contiguous()), None, None
+
+
+def _fill_block(layer, load, i: int, w: int, dense_mlp: bool, precision: str = "split"):
+    """Fills `layer` (a _lib.VitLayer, the *_s scales included) from CLIP's transformer.resblocks.{i}.* of width w; mlp.* only
+    with dense_mlp.  load(name, shape) -> the fp32 device tensor of a key.  Returns (the tensors the struct points to, the
+    pack sources of _split_pack)."""
+    b = f"transformer.resblocks.{i}."
+    lin = [("in_proj", "attn.in_proj_", 3 * w, w), ("out_proj", "attn.out_proj.", w, w)]
+    if dense_mlp:
+        lin += [("fc", "mlp.c_fc.", 4 * w, w), ("proj", "mlp.c_proj.", w, 4 * w)]
+    t, src = {}, []
+    for part, key, n, k in lin:
+        t[part + "_w"], scale, s = _gemm_weight(load(b + key + "weight", (n, k)), precision)
+        t[part + "_b"] = load(b + key + "bias", (n,))
+        if scale is not None:
+            setattr(layer, part + "_s", scale)
+            src.append(s)
+    for part, key in (("ln1", "ln_1."), ("ln2", "ln_2.")):
+        t[part + "_g"], t[part + "_b"] = load(b + key + "weight", (w,)), load(b + key + "bias", (w,))
+    for k, v in t.items():
+        setattr(layer, k, v.data_ptr())
+    return list(t.values()), src
+
+
 class VitEncoder:
     """Device-resident CLIP ViT image encoder + feature head.
 
@@ -764,61 +824,24 @@ class VitEncoder:
         self.img_hw = tuple(img_hw)
         dev = self.device
 
-        def get(name):
-            for k in (name, "image_encoder." + name):
-                if k in state_dict:
-                    v = state_dict[k]
-                    return torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach()
-            raise KeyError(name)
+        get = _state_getter(state_dict, "image_encoder.")
 
-        def f32(name):
+        def f32(name, shape=None):   # (shapes are not checked here: the library's own checks and the asserts below)
             return get(name).to(device=dev, dtype=torch.float32).contiguous()
-
-        scales = {}
-
-        def f16(name, shape=None, tensor=None):   # a GEMM weight: fp16 for the MFMA path, fp32 in the all-fp32 mode
-            t = (get(name) if tensor is None else tensor).to(device=dev, dtype=torch.float32)
-            if shape is not None:
-                t = t.reshape(shape)
-            if precision == "split":
-                # fp16 pair [out][hi(in) | lo(in)] of W * 2^e with the largest |entry| in [2^9, 2^10): hi + lo carries
-                # 22 significant bits of every entry that matters; 2^-e is undone in the GEMM epilogue (exact)
-                t = t.contiguous()
-                amax = float(t.abs().max())
-                e = 9 - int(np.floor(np.log2(amax))) if amax > 0 and np.isfinite(amax) else 0
-                pair = torch.empty((t.shape[0], 2 * t.shape[1]), dtype=torch.float16, device=dev)
-                _lib.check(_lib.load().mpreid_split_pack_f32(_ptr(t), t.shape[0], t.shape[1], float(2.0 ** e), _ptr(pair),
-                                                             _lib.stream_ptr()), "mpreid_split_pack_f32")
-                scales[name] = float(2.0 ** -e)
-                return pair
-            return t.contiguous() if precision == "fp32" else t.to(torch.float16).contiguous()
 
         w = cfg["width"]
         self._keep = []  # owns every device tensor referenced by the C structs
         keep = self._keep.append
+        pack_src = []   # the pack kernels' fp32 sources: alive until the synchronize at the end
         self.c_cfg = _lib.VitCfg(self.img_hw[0], self.img_hw[1], cfg["patch"], cfg["stride"], cfg["h_res"],
                                  cfg["w_res"], w, cfg["layers"], cfg["heads"], cfg["out_dim"], int(bool(neck_after)),
                                  int(bool(cls_only_last)),
                                  _lib.VIT_SPLIT if precision == "split" else _lib.VIT_F16)
         layers = (_lib.VitLayer * max(cfg["layers"], 1))()
         for i in range(cfg["layers"]):
-            b = f"transformer.resblocks.{i}"
-            t = dict(in_proj_w=f16(b + ".attn.in_proj_weight"), in_proj_b=f32(b + ".attn.in_proj_bias"),
-                     out_proj_w=f16(b + ".attn.out_proj.weight"), out_proj_b=f32(b + ".attn.out_proj.bias"),
-                     ln1_g=f32(b + ".ln_1.weight"), ln1_b=f32(b + ".ln_1.bias"),
-                     ln2_g=f32(b + ".ln_2.weight"), ln2_b=f32(b + ".ln_2.bias"))
-            if i >= n_moe:
-                t.update(fc_w=f16(b + ".mlp.c_fc.weight"), fc_b=f32(b + ".mlp.c_fc.bias"),
-                         proj_w=f16(b + ".mlp.c_proj.weight"), proj_b=f32(b + ".mlp.c_proj.bias"))
-            for k, v in t.items():
-                keep(v)
-                setattr(layers[i], k, v.data_ptr())
-            if precision == "split":
-                layers[i].in_proj_s = scales[b + ".attn.in_proj_weight"]
-                layers[i].out_proj_s = scales[b + ".attn.out_proj.weight"]
-                if i >= n_moe:
-                    layers[i].fc_s = scales[b + ".mlp.c_fc.weight"]
-                    layers[i].proj_s = scales[b + ".mlp.c_proj.weight"]
+            kept, src = _fill_block(layers[i], f32, i, w, i >= n_moe, precision)
+            self._keep += kept
+            pack_src += src
         self._layers = layers
         self.c_moe = None
         if n_moe:
@@ -841,7 +864,9 @@ class VitEncoder:
                     setattr(moe_layers[i], k, v.data_ptr())
             self._moe_layers = moe_layers
             self.c_moe = _lib.VitMoe(n_exp, top_k, n_moe, C.cast(moe_layers, C.POINTER(_lib.MoeLayer)))
-        top = dict(conv_w=f16("conv1.weight", (w, -1)), class_emb=f32("class_embedding"),
+        conv_w, conv_s, src = _gemm_weight(f32("conv1.weight").reshape(w, -1), precision)   # fp32 in the all-fp32 mode
+        pack_src.append(src)
+        top = dict(conv_w=conv_w, class_emb=f32("class_embedding"),
                    pos_emb=f32("positional_embedding"), ln_pre_g=f32("ln_pre.weight"), ln_pre_b=f32("ln_pre.bias"),
                    ln_post_g=f32("ln_post.weight"), ln_post_b=f32("ln_post.bias"), proj=f32("proj"))
         L = cfg["h_res"] * cfg["w_res"] + 1
@@ -851,8 +876,7 @@ class VitEncoder:
             keep(v)
             setattr(self.c_w, k, v.data_ptr())
         if precision == "split":
-            self.c_w.conv_s = scales["conv1.weight"]
-            torch.cuda.current_stream().synchronize()   # the pack kernels read temporaries of this constructor
+            self.c_w.conv_s = conv_s
         if bn is not None:
             for name, (sk, bk) in (("bottleneck", ("bn_scale", "bn_shift")),
                                    ("bottleneck_proj", ("bn_proj_scale", "bn_proj_shift"))):
@@ -865,6 +889,7 @@ class VitEncoder:
                 setattr(self.c_w, bk, shift.data_ptr())
         self.c_w.layers = C.cast(layers, C.POINTER(_lib.VitLayer))
         self.feat_dim = w + cfg["out_dim"]
+        torch.cuda.current_stream().synchronize()   # the pack kernels are done with their fp32 sources
 
     def forward(self, img: torch.Tensor, cv_emb: Optional[torch.Tensor] = None,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1083,8 +1108,7 @@ def moe_route(x: torch.Tensor, gate: torch.Tensor, top_k: int, ln=None, want_log
 
 def _pack_experts(mats, n_exp: int, dev):
     """n_exp fp32 matrices [out, in] (an iterable: one is on the device at a time) -> (fp16 pairs [E][out][2 * in], fp32 [E] of
-    2^-e): every expert is packed straight into its slice of the one stacked buffer, with the scale rule of the dense layers --
-    W * 2^e has its largest finite |entry| in [2^9, 2^10)"""
+    2^-e): every expert is packed straight into its slice of the one stacked buffer, by the dense layers' packer (_split_pack)"""
     pair, sc = None, []
     for e, m in enumerate(mats):
         t = _dev_f32(m, dev)
@@ -1092,12 +1116,10 @@ def _pack_experts(mats, n_exp: int, dev):
         if pair is None:
             pair = torch.empty((n_exp, n, 2 * k), dtype=torch.float16, device=dev)
         assert tuple(pair.shape[1:]) == (n, 2 * k), (e, tuple(t.shape))
-        amax = float(torch.nan_to_num(t, nan=0.0, posinf=0.0, neginf=0.0).abs().max())
-        ex = 9 - int(np.floor(np.log2(amax))) if amax > 0 else 0
-        _lib.check(_lib.load().mpreid_split_pack_f32(_ptr(t), n, k, float(2.0 ** ex), _ptr(pair[e]), _lib.stream_ptr()),
-                   "mpreid_split_pack_f32")
-        sc.append(2.0 ** -ex)
-        torch.cuda.current_stream().synchronize()   # t is a temporary
+        _, scale, src = _split_pack(t, out=pair[e])
+        sc.append(scale)
+        torch.cuda.current_stream().synchronize()   # t (= src) is a temporary: one expert's fp32 matrix on the device at a time
+        del t, src
     assert len(sc) == n_exp
     return pair, torch.tensor(sc, dtype=torch.float32, device=dev)
 
@@ -1204,20 +1226,7 @@ class TextEncoder:
         self.device = dev = device or _lib.require_gpu()
         self.ws_tag = ws_tag
         self.cfg = {k: int(cfg[k]) for k in ("tokens", "width", "layers", "heads", "out_dim")}
-        L = _lib.load()
-
-        def find(name):
-            for k in (name, "text_encoder." + name):
-                if k in state_dict:
-                    v = state_dict[k]
-                    return torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach()
-            return None
-
-        def get(name):
-            v = find(name)
-            if v is None:
-                raise KeyError(name)
-            return v
+        get = _state_getter(state_dict, "text_encoder.")
 
         def f32(name, shape):
             t = get(name).to(device=dev, dtype=torch.float32).contiguous()
@@ -1225,38 +1234,15 @@ class TextEncoder:
                 raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
             return t
 
-        scales, pack_src = {}, []
-
-        def pair(name, shape):   # a GEMM weight as VitEncoder packs it for the split precision
-            t = f32(name, shape)
-            amax = float(t.abs().max())
-            e = 9 - int(np.floor(np.log2(amax))) if amax > 0 and np.isfinite(amax) else 0
-            p = torch.empty((t.shape[0], 2 * t.shape[1]), dtype=torch.float16, device=dev)
-            _lib.check(L.mpreid_split_pack_f32(_ptr(t), t.shape[0], t.shape[1], float(2.0 ** e), _ptr(p), _lib.stream_ptr()),
-                       "mpreid_split_pack_f32")
-            pack_src.append(t)   # read by the pack kernel: alive until the synchronize below
-            scales[name] = float(2.0 ** -e)
-            return p
-
         w, nl = self.cfg["width"], self.cfg["layers"]
         self._keep = []   # owns every device tensor referenced by the C structs
         self.c_cfg = _lib.TextCfg(self.cfg["tokens"], w, nl, self.cfg["heads"], self.cfg["out_dim"])
         layers = (_lib.VitLayer * max(nl, 1))()
+        pack_src = []   # the pack kernels' fp32 sources: alive until the synchronize at the end
         for i in range(nl):
-            b = f"transformer.resblocks.{i}"
-            t = dict(in_proj_w=pair(b + ".attn.in_proj_weight", (3 * w, w)), in_proj_b=f32(b + ".attn.in_proj_bias", (3 * w,)),
-                     out_proj_w=pair(b + ".attn.out_proj.weight", (w, w)), out_proj_b=f32(b + ".attn.out_proj.bias", (w,)),
-                     ln1_g=f32(b + ".ln_1.weight", (w,)), ln1_b=f32(b + ".ln_1.bias", (w,)),
-                     ln2_g=f32(b + ".ln_2.weight", (w,)), ln2_b=f32(b + ".ln_2.bias", (w,)),
-                     fc_w=pair(b + ".mlp.c_fc.weight", (4 * w, w)), fc_b=f32(b + ".mlp.c_fc.bias", (4 * w,)),
-                     proj_w=pair(b + ".mlp.c_proj.weight", (w, 4 * w)), proj_b=f32(b + ".mlp.c_proj.bias", (w,)))
-            for k, v in t.items():
-                self._keep.append(v)
-                setattr(layers[i], k, v.data_ptr())
-            layers[i].in_proj_s = scales[b + ".attn.in_proj_weight"]
-            layers[i].out_proj_s = scales[b + ".attn.out_proj.weight"]
-            layers[i].fc_s = scales[b + ".mlp.c_fc.weight"]
-            layers[i].proj_s = scales[b + ".mlp.c_proj.weight"]
+            kept, src = _fill_block(layers[i], f32, i, w, True)
+            self._keep += kept
+            pack_src += src
         self._layers = layers
         top = dict(pos_emb=f32("positional_embedding", (self.cfg["tokens"], w)), ln_final_g=f32("ln_final.weight", (w,)),
                    ln_final_b=f32("ln_final.bias", (w,)), proj=f32("text_projection", (w, self.cfg["out_dim"])))
@@ -1265,10 +1251,9 @@ class TextEncoder:
             self._keep.append(v)
             setattr(self.c_w, k, v.data_ptr())
         self.c_w.layers = C.cast(layers, C.POINTER(_lib.VitLayer))
-        emb = find("token_embedding.weight")
+        emb = get("token_embedding.weight", required=False)
         self.token_embedding = None if emb is None else emb.to(device=dev, dtype=torch.float32).contiguous()
         torch.cuda.current_stream().synchronize()   # the pack kernels are done with their fp32 sources
-        del pack_src[:]
 
     @torch.no_grad()
     def forward(self, prompts: torch.Tensor, eot, out: Optional[torch.Tensor] = None) -> torch.Tensor:
