@@ -71,6 +71,18 @@ int mpreid_dyn_lds(const void *kernel, size_t bytes) {
     return MPREID_OK;
 }
 
+// CU count of the current device: see common.h.  Benign race: every writer stores the same value.
+int mpreid_device_cus(int *cus) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    static int cus_of[64] = {0};
+    int uncached = 0;
+    int *n = dev >= 0 && dev < 64 ? &cus_of[dev] : &uncached;
+    if (*n <= 0) HIP_TRY(hipDeviceGetAttribute(n, hipDeviceAttributeMultiprocessorCount, dev));
+    *cus = *n;
+    return MPREID_OK;
+}
+
 extern "C" int mpreid_version(void) { return 101; } /* 0.1.1: mpreid/_lib.py (VERSION) loads exactly this one */
 
 // 1 for a library compiled with -DMPREID_ABLATION (timing-ablation switches honoured: WRONG RESULTS by design), else 0

@@ -61,7 +61,8 @@ __host__ __device__ static inline size_t align_up(size_t x, size_t a) { return (
 // Timing-ablation switches (MPREID_GEMM_DBG, MPREID_ATT_DBG, MPREID_CAND_DBG, MPREID_JACCARD_DBG: kernels that skip loads,
 // matrix instructions or stores -- WRONG RESULTS by design) are honoured only by a library built with -DMPREID_ABLATION
 // (MPREID_ABLATION=1 python mp-reid_amd/mpreid/build.py); the shipped library ignores them, so a stray environment
-// variable cannot change results.
+// variable cannot change results.  The GEMM kernels' ablation INSTANCES (template arguments, the lists in
+// gemm_plan.h) are named inside #ifdef MPREID_ABLATION only, so the shipped library does not even contain them.
 static inline int mpreid_ablation_env(const char *name) {
 #ifdef MPREID_ABLATION
     const char *e = getenv(name);
@@ -163,6 +164,10 @@ template <typename F>
 static inline int mpreid_dyn_lds(F *kernel, size_t bytes) {
     return mpreid_dyn_lds(reinterpret_cast<const void *>(kernel), bytes);
 }
+
+// CU count of the CURRENT HIP device, for the launchers that size a persistent grid by it: asked of the runtime once per
+// device and cached (api.cpp); devices numbered 64 or higher are not cached, as in PerDeviceOnce.
+int mpreid_device_cus(int *cus);
 
 // Run `f` (returns an mpreid/hip status) once per HIP device for the call site that owns this object: whatever else is
 // per device (occupancy queries, a verbose line) -- one process may drive several GPUs.  The dynamic-LDS attribute has

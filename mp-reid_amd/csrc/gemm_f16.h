@@ -25,6 +25,18 @@ constexpr int GBM = 128, GBN = 128, GBK = 64;
 constexpr int G_TILE_BYTES = GBM * GBK * 2;        // 16 KB per operand tile
 constexpr int G_STAGE_BYTES = 2 * G_TILE_BYTES;    // A + B
 constexpr int G_LDS_BYTES = 2 * G_STAGE_BYTES;     // double buffered: 64 KB
+// gemm_f16_big_kernel (persistent 256x256) and dist_sym_p2_kernel (256x128): described in gemm_f16.hip, read by gemm_plan.h too
+constexpr int BBM = 256, BBN = 256, BBK = 32, B_NSTAGE = 4;
+constexpr int B_PART_BYTES = BBM * BBK * 2;          // 16 KB
+constexpr int B_STAGE_BYTES = 2 * B_PART_BYTES;      // 32 KB
+constexpr int B_LDS_BYTES = B_NSTAGE * B_STAGE_BYTES; // 128 KB ring
+constexpr int B_LDS_TOTAL = B_LDS_BYTES + 8 * 4096;   // + 32 KB of epilogue patches = the CU's whole 160 KB
+constexpr int PBM = 256, PBN = 128, PBK = 32, P_NSTAGE = 3;
+constexpr int P_A_BYTES = PBM * PBK * 2;                 // 16 KB
+constexpr int P_B_BYTES = PBN * PBK * 2;                 // 8 KB
+constexpr int P_STAGE_BYTES = P_A_BYTES + P_B_BYTES;     // 24 KB
+constexpr int P_RING_BYTES = P_NSTAGE * P_STAGE_BYTES;   // 72 KB
+constexpr int P_LDS_BYTES = P_RING_BYTES + 4 * 1024;     // + the four waves' row tables: 76 KB, two workgroups per CU
 
 enum GemmEpi {
     GE_F32 = 0,        // C fp32 = acc
@@ -55,6 +67,11 @@ enum GemmEpi {
                                // identity of the next block and once as the pair operand of its first convolution
 };
 constexpr bool gemm_epi_is_split(int epi) { return epi >= GE_S_BIAS_F32 && epi <= GE_S_BIAS_RES_PAIR; }
+// epilogues gemm_f16_big_kernel is instantiated for
+constexpr bool gemm_epi_has_big(int epi) {
+    return epi == GE_F32 || epi == GE_BIAS_F16 || epi == GE_BIAS_RES || epi == GE_BIAS_GELU || epi == GE_EUCLID || epi == GE_PATCH ||
+           epi == GE_BIAS_RELU || epi == GE_BIAS_ADD_RELU || epi == GE_CAND || gemm_epi_is_split(epi);
+}
 
 struct GemmArgs {
     const _Float16 *A;   // [M][K]

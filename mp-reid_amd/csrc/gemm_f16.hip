@@ -3,7 +3,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "gemm_f16.h"
+#include "gemm_plan.h"
 
 typedef __attribute__((address_space(3))) void lds_ptr_t;
 typedef const __attribute__((address_space(1))) void glb_ptr_t;
@@ -512,11 +512,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(GemmArgs g, int tiles_
 // 16-lane groups): 16-byte chunk index ^= 3 * ((row >> 3) & 1) -- conflict-free for all groups;
 // applied to the DMA source address and to the read address (rule 21).
 // ---------------------------------------------------------------------------------------------
-constexpr int BBM = 256, BBN = 256, BBK = 32, B_NSTAGE = 4;
-constexpr int B_PART_BYTES = BBM * BBK * 2;          // 16 KB
-constexpr int B_STAGE_BYTES = 2 * B_PART_BYTES;      // 32 KB
-constexpr int B_LDS_BYTES = B_NSTAGE * B_STAGE_BYTES; // 128 KB ring
-constexpr int B_LDS_TOTAL = B_LDS_BYTES + 8 * 4096;   // + 32 KB of epilogue patches = the CU's whole 160 KB
 
 // DBG (timing-only ablation builds, never used by the product path): 1 no DMA in the steady loop,
 // 2 no MFMA, 4 no fragment reads in the steady loop, 8 no epilogue
@@ -1771,12 +1766,6 @@ __global__ __launch_bounds__(512) void gemm_f16_big_kernel(GemmArgs g, int tiles
 //   cut into eight EQUAL contiguous ranges, one per XCD (closed-form position -> tile map, no list in memory).
 //   Same products in the same k order as the kernels above: same bits (tests/test_gpu_distance.py).
 // ---------------------------------------------------------------------------------------------
-constexpr int PBM = 256, PBN = 128, PBK = 32, P_NSTAGE = 3;
-constexpr int P_A_BYTES = PBM * PBK * 2;                 // 16 KB
-constexpr int P_B_BYTES = PBN * PBK * 2;                 // 8 KB
-constexpr int P_STAGE_BYTES = P_A_BYTES + P_B_BYTES;     // 24 KB
-constexpr int P_RING_BYTES = P_NSTAGE * P_STAGE_BYTES;   // 72 KB
-constexpr int P_LDS_BYTES = P_RING_BYTES + 4 * 1024;     // + the four waves' row tables: 76 KB, two workgroups per CU
 
 // number of tiles of strip br (tile rows 8 br .. 8 br + R - 1, tile columns 16 br .. tiles_n - 1): column j of the strip
 // holds min(R, j / 2 + 1) tiles
@@ -2100,26 +2089,9 @@ __global__ __launch_bounds__(256, 2) void dist_sym_p2_kernel(GemmArgs g, int til
 #include <tuple>
 #include <vector>
 namespace {
-// The tile walk gemm_f16_big_kernel takes, for the line below: a COPY of the kernel's three expressions GR / owned / blocked (nb = grid
-// size, walk = GemmArgs::walk, sym = a symmetric problem on an epilogue that knows them; neither mode = the plain strided walk).
-// A copy, not a function the kernel shares: routed through one, every instantiation of the kernel compiled to a different scalar
-// prologue and register assignment.  Whoever changes the kernel's rule changes this one with it; the walk names the tests expect
-// (tests/test_gpu_rn50_split_layers.py) are written down by hand and would disagree with a stale copy's.
-struct BigWalk {
-    int GR;
-    bool owned, blocked;
-};
-BigWalk big_walk_of(int tiles_m, int tiles_n, int nb, int walk, bool sym) {
-    BigWalk w;
-    w.GR = ((walk & 7) == 3 || (walk & 8)) ? 4 : ((walk & 7) == 4 ? 16 : 8);
-    const int ngroups = (tiles_m + w.GR - 1) / w.GR;
-    w.owned = (nb % 8 == 0) && (tiles_m % (8 * w.GR) == 0 || (ngroups >= 24 && !(walk & 16) && !sym));
-    w.blocked = !w.owned && (nb % 64 == 0) && tiles_m * tiles_n >= nb;
-    return w;
-}
-// MPREID_TUNE=verbose=1: launch_one names the kernel (and the persistent kernel's tile walk) it launches on stderr, one line per
-// distinct (epilogue, kernel, walk, tiles_m, tiles_n, grid) of the process -- tests assert on these lines that a shape reached the
-// kernel and the walk it was chosen for.  Never called unless verbose is set.
+// MPREID_TUNE=verbose=1: launch_one names the kernel (and the persistent kernel's tile walk) it launches on stderr (the plan's
+// line, gemm_plan.h), one line per distinct (epilogue, kernel, walk, tiles_m, tiles_n, grid) of the process -- tests assert on
+// these lines that a shape reached the kernel and the walk it was chosen for.  Never called unless verbose is set.
 void gemm_verbose_line(const char *line) {
     static std::mutex mu;
     static std::set<std::string> said;
@@ -2132,12 +2104,8 @@ struct ProfClass {
     int64_t m = 0; // largest M seen in the class
 };
 bool g_prof_on = false;
-// MPREID_TUNE gemm_big: 0 = never use the 256x256 kernel, 1 = when the grid fills the chip (default),
-// 2 = whenever the shape is divisible (tests)
-int big_mode() {
-    static const int mode = mpreid_tune("gemm_big", 1);
-    return mode;
-}
+// the launcher's MPREID_TUNE keys (gemm_plan.h: GemmTune), read once per process
+const GemmTune &gemm_tune() { static const GemmTune t = gemm_tune_read(mpreid_tune); return t; }
 std::mutex g_prof_mu;
 std::map<std::tuple<int, int, int, int>, ProfClass> g_prof;   // (epilogue, M, N, K)
 } // namespace
@@ -2222,246 +2190,90 @@ void mpreid_prof_end(void *token, hipStream_t stream, int cls, int64_t m, int n,
     delete t;
 }
 
-// CU count of the current device (cached per device ordinal; benign race: every writer stores the same value)
-static int current_device_cus(int *cus) {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    static int cus_of[64] = {0};
-    if (dev >= 0 && dev < 64 && cus_of[dev] > 0) {
-        *cus = cus_of[dev];
-        return MPREID_OK;
-    }
-    int n = 0;
-    HIP_TRY(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-    if (dev >= 0 && dev < 64) cus_of[dev] = n;
-    *cus = n;
+// The ONE launch site of this file: the dynamic-LDS attribute of the kernel that is about to run (and of no other), then the
+// launch inside the shared profiling bracket, filed under (cls, M, N, K).  Everything that can fail without launching -- the
+// plan, the CU count, the attribute -- has happened when mpreid_prof_begin runs, and the bracket is closed before a failed
+// launch's status is returned: no path leaves an event behind.
+template <typename... P, typename... A>
+static int launch_profiled(void (*kernel)(P...), const GemmPlan &p, hipStream_t stream, int cls, double work, const GemmArgs &a, A... rest) {
+    if (const int rc = mpreid_dyn_lds(kernel, p.lds)) return rc;
+    void *ptok = mpreid_prof_begin(stream);
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds, stream, a, rest...);
+    const hipError_t kernel_launch = hipGetLastError();
+    mpreid_prof_end(ptok, stream, cls, a.M, a.N, a.K, work);
+    HIP_TRY(kernel_launch);
     return MPREID_OK;
 }
+using GemmKernel = void (*)(GemmArgs, int, int);             // gemm_f16_kernel, gemm_f16_big_kernel
+using P2Kernel = void (*)(GemmArgs, int, int, int, int);     // dist_sym_p2_kernel
+
+#ifdef MPREID_ABLATION
+// MPREID_GEMM_DBG and MPREID_TUNE=dist_sym_p2_abl (the lists of values: gemm_plan.h), read once per process
+static int gemm_dbg_env() { static const int dbg = mpreid_ablation_env("MPREID_GEMM_DBG"); return dbg; }
+static int p2_abl_tune() { static const int abl = mpreid_tune("dist_sym_p2_abl", 0); return abl; }
+// MPREID_GEMM_STAMPS = device pointer (hex) of the per-tile phase stamps; read at each launch that takes them (the tools
+// allocate the buffer, and set the variable, after the library is loaded)
+static unsigned long long *gemm_stamps_env() {
+    const char *sp = getenv("MPREID_GEMM_STAMPS");
+    return sp ? reinterpret_cast<unsigned long long *>(strtoull(sp, nullptr, 16)) : nullptr;
+}
+// MPREID_GEMM_GRID: the persistent kernel planned as if the device had this many CUs (fewer workgroups than CUs)
+static int gemm_grid_env(int cus) { const char *gg = getenv("MPREID_GEMM_GRID"); return gg ? atoi(gg) : cus; }
+#endif
 
 template <int EPI>
 static int launch_one(const GemmArgs &a_in, hipStream_t stream) {
-    const GemmArgs &a = a_in;
-    if (const int rc = mpreid_dyn_lds(gemm_f16_kernel<EPI>, G_LDS_BYTES)) return rc;
-    constexpr bool HAS_BIG = (EPI == GE_F32 || EPI == GE_BIAS_F16 || EPI == GE_BIAS_RES || EPI == GE_BIAS_GELU ||
-                              EPI == GE_EUCLID || EPI == GE_PATCH || EPI == GE_BIAS_RELU || EPI == GE_BIAS_ADD_RELU ||
-                              EPI == GE_CAND || gemm_epi_is_split(EPI));
-    if constexpr (gemm_epi_is_split(EPI)) {
-        if (a.kseg <= 0 || a.kseg % GBK || a.K != 2 * a.kseg) {
-            mpreid_set_error("gemm_f16: split epilogue %d needs K == 2 * kseg, kseg a multiple of %d (K=%d kseg=%d)", EPI, GBK,
-                             a.K, a.kseg);
-            return MPREID_ERR_ARG;
-        }
+    const GemmTune &t = gemm_tune();
+    int cus = 0;
+    if (const int rc = mpreid_device_cus(&cus)) return rc;
+    GemmPlan p = plan_gemm(EPI, a_in, cus, t);
+    if (p.status) {
+        mpreid_set_error("%s", p.text);
+        return p.status;
     }
-    if constexpr (EPI == GE_CAND) {
-        if (a.M % BBM || a.N % BBN) {
-            mpreid_set_error("gemm_f16: the candidate epilogue needs M, N multiples of %d", BBM);
-            return MPREID_ERR_ARG;
-        }
-    }
-    const int bm = big_mode();
-    const bool use_big = HAS_BIG && (EPI == GE_CAND || (bm > 0 && (a.M % BBM == 0) && (a.N % BBN == 0) &&
-                                                        (bm >= 2 || (int64_t)(a.M / BBM) * (a.N / BBN) >= 128)));
-    if constexpr (HAS_BIG) {
-        if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI>, B_LDS_TOTAL)) return rc;
-    }
-    const int tiles_m = use_big ? a.M / BBM : a.M / GBM, tiles_n = use_big ? a.N / BBN : a.N / GBN;
-    static const int verbose = mpreid_tune("verbose", 0);
-    char vline[160];
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (g_prof_on) {
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, stream));
-    }
-    // MPREID_TUNE dist_sym_p2: 0 = never, 1 = symmetric stored distance problems of at least 16 tile rows (default),
-    // 2 = every symmetric problem whose padded size allows it (tests)
-    bool use_p2 = false, p2_full = false;
+    GemmArgs a = a_in;
+    // the instance the plan names
+    GemmKernel k3 = gemm_f16_kernel<EPI>;
+    [[maybe_unused]] P2Kernel k5 = nullptr;
+    [[maybe_unused]] const bool is_p2 = p.form == GF_P2_SYM || p.form == GF_P2_FULL;
+    if constexpr (gemm_epi_has_big(EPI))
+        if (p.form == GF_BIG) k3 = gemm_f16_big_kernel<EPI>;
     if constexpr (EPI == GE_EUCLID) {
-        static const int p2_mode = mpreid_tune("dist_sym_p2", 1);
-        use_p2 = a.sym && p2_mode > 0 && a.M == a.N && (a.A == a.W || p2_mode >= 3) && (a.M % PBM == 0) && (a.K % PBK == 0) &&
-                 (p2_mode >= 2 || a.M / PBM >= 16);   // (3: also the 3-term split operands, A != W: measured slower, see DESIGN)
-        // MPREID_TUNE dist_p2_full: the two-workgroups-per-CU kernel for TWO tensors (stored distances, one-pass fp16 and
-        // 3-term split operands): 0 never (default: measured slower), 1 problems of at least 16 x 32 tiles, 2 whenever
-        // the padded sizes allow (tests)
-        static const int full_mode = mpreid_tune("dist_p2_full", 0);
-        if (!use_p2 && !a.sym && full_mode > 0 && a.out && (a.M % PBM == 0) && (a.N % PBN == 0) && (a.K % PBK == 0) &&
-            (full_mode >= 2 || (a.M / PBM >= 16 && a.N / PBN >= 32)))
-            use_p2 = p2_full = true;
+        if (p.form == GF_BIG_SYM) k3 = gemm_f16_big_kernel<EPI, 0, true>;
+        k5 = p.form == GF_P2_FULL ? dist_sym_p2_kernel<0, true> : dist_sym_p2_kernel<0>;
     }
-    if (use_p2) {
-        if constexpr (EPI == GE_EUCLID) {
-            if (const int rc = mpreid_dyn_lds(dist_sym_p2_kernel<0>, P_LDS_BYTES)) return rc;
-            int cus = 0;
-            if (const int rcc = current_device_cus(&cus)) return rcc;
-            const int grid = std::max(8, (2 * cus) & ~7);
-            static const int naps_tune = mpreid_tune("dist_sym_p2_naps", -1);
-            const int naps = naps_tune >= 0 ? naps_tune : 0;   // (experiments) late start of every CU's second workgroup, units of s_sleep 8
-            [[maybe_unused]] static const int abl = mpreid_tune("dist_sym_p2_abl", 0);
-            GemmArgs a = a_in;
-            static const int gridt = mpreid_tune("dist_sym_p2_grid", 0);
-            static const int strip = std::max(1, mpreid_tune("dist_sym_p2_strip", 8));   // tile rows per strip of the walk
-            const dim3 gdim((unsigned)(gridt ? gridt : grid));
-            if (verbose) {
-                snprintf(vline, sizeof vline, "gemm epi %d: two workgroups per CU 256x128%s, %dx%d tiles, grid %u", EPI,
-                         p2_full ? " (two tensors)" : " (symmetric)", a.M / PBM, a.N / PBN, gdim.x);
-                gemm_verbose_line(vline);
-            }
 #ifdef MPREID_ABLATION
-            if (const char *sp = getenv("MPREID_GEMM_STAMPS")) a.stamps = reinterpret_cast<unsigned long long *>(strtoull(sp, nullptr, 16));
-#define MPREID_P2_CASE(V)                                                                                      \
-    case V:                                                                                                    \
-        if (const int rc = mpreid_dyn_lds(dist_sym_p2_kernel<V>, P_LDS_BYTES)) return rc;                      \
-        hipLaunchKernelGGL(dist_sym_p2_kernel<V>, gdim, dim3(256), P_LDS_BYTES, stream, a, a.M / PBM, a.N / PBN, naps, strip); \
-        break;
-            if (p2_full) {
-                if (const int rc = mpreid_dyn_lds(dist_sym_p2_kernel<0, true>, P_LDS_BYTES)) return rc;
-                hipLaunchKernelGGL((dist_sym_p2_kernel<0, true>), gdim, dim3(256), P_LDS_BYTES, stream, a, a.M / PBM, a.N / PBN, naps, strip);
-            } else
-            switch (abl) {
-                MPREID_P2_CASE(1) MPREID_P2_CASE(2) MPREID_P2_CASE(3) MPREID_P2_CASE(4) MPREID_P2_CASE(8) MPREID_P2_CASE(9)
-                MPREID_P2_CASE(16) MPREID_P2_CASE(24) MPREID_P2_CASE(32) MPREID_P2_CASE(33)
-            default:
-                hipLaunchKernelGGL(dist_sym_p2_kernel<0>, gdim, dim3(256), P_LDS_BYTES, stream, a, a.M / PBM, a.N / PBN, naps, strip);
-            }
-#undef MPREID_P2_CASE
-#else
-            if (p2_full) {
-                if (const int rc = mpreid_dyn_lds(dist_sym_p2_kernel<0, true>, P_LDS_BYTES)) return rc;
-                hipLaunchKernelGGL((dist_sym_p2_kernel<0, true>), gdim, dim3(256), P_LDS_BYTES, stream, a, a.M / PBM, a.N / PBN, naps, strip);
-            } else {
-                hipLaunchKernelGGL(dist_sym_p2_kernel<0>, gdim, dim3(256), P_LDS_BYTES, stream, a, a.M / PBM, a.N / PBN, naps, strip);
-            }
-#endif
+    // Everything a timing-ablation build does differently (WRONG RESULTS by design): an instance of the lists in gemm_plan.h in
+    // place of the plan's, the stamps buffer, a persistent grid of fewer workgroups than CUs.
+    if constexpr (gemm_epi_has_big(EPI)) {
+        // (DBG 64: instantiated for every epilogue, selectable on the split ones only -- an ablation build keeps its kernels)
+        [[maybe_unused]] static constexpr GemmKernel aliased_panels = gemm_f16_big_kernel<EPI, 64>;
+        if (p.form == GF_BIG || p.form == GF_BIG_SYM) {
+            if (const int wgs = gemm_grid_env(cus); wgs != cus) p = plan_gemm(EPI, a_in, wgs, t);
+            k3 = gemm_dbg_select<GEMM_DBG_LIST<EPI>>(gemm_dbg_env(), [&a, k3](auto d) -> GemmKernel {
+                constexpr int D = decltype(d)::value;
+                if constexpr (gemm_dbg_takes_stamps(D)) a.stamps = gemm_stamps_env();
+                if constexpr (D != 0) return gemm_f16_big_kernel<EPI, D>;
+                else return k3;
+            });
         }
-    } else if (use_big) {
-        if constexpr (HAS_BIG) {
-            static const int dbg = mpreid_ablation_env("MPREID_GEMM_DBG");
-            // persistent: one workgroup per CU (the kernel owns the CU's whole LDS), each walking tiles
-            int big_cus = 0;
-            if (const int rcc = current_device_cus(&big_cus)) return rcc;
-            static const int stag_all = mpreid_tune("gemm_stagger_all", 0);
-            // tile order inside an XCD's row group (bit-identical results; tools/walk_ab.sh on one device, M = 65 536, split
-            // operands): column-fastest takes FC2 (N = 768, 12 KB operand rows) from 711 / 709 to 693 / 693 us and leaves
-            // out-proj (3 KB rows) 0.5-1 % SLOWER (219.6 / 217.7 -> 221.5 / 220.7); groups of 4 tile rows (an A panel that fits
-            // the 4 MB L2) change nothing (QKV 552.6 / 554.0, FC1 755 / 756), groups of 16 lose 1-3 %.  auto (-1) = column-fastest
-            // for narrow outputs with operand rows of >= 8 KB, i.e. the split FC2.
-            static const int walk_tune = mpreid_tune("gemm_walk", -1);   // 0 row-fastest; 1 column-fastest when tiles_n <= 4; 2 always; 3 / 4: groups of 4 / 16 rows
-            GemmArgs a = a_in;
-            if (stag_all > 0) {
-                a.stagger = stag_all;
-                a.stagger_mode = 1;
-            }
-            a.walk = walk_tune >= 3 ? walk_tune
-                   : (walk_tune == 2 || (walk_tune == 1 && tiles_n <= 4) || (walk_tune < 0 && tiles_n <= 4 && (int64_t)a.K * 2 >= 8192)) ? 1 : 0;
-            // row groups of 4 tile rows when groups of 8 do not divide among the XCDs but groups of 4 do (e.g. tiles_m = 224):
-            // bit 3 of walk
-            if (walk_tune < 3 && tiles_m % 64 != 0 && tiles_m % 32 == 0) a.walk |= 8;
-            static const int ragged_tune = mpreid_tune("gemm_ragged", 1);   // 0: round 5's rule (owned walk only for exact divisions)
-            if (!ragged_tune) a.walk |= 16;
-            const unsigned total_tiles = (unsigned)tiles_m * (unsigned)tiles_n;
-#ifdef MPREID_ABLATION
-            if (const char *gg = getenv("MPREID_GEMM_GRID")) big_cus = atoi(gg);   // (ablation) fewer workgroups than CUs
+    }
+    if constexpr (EPI == GE_EUCLID) {
+        if (is_p2)
+            if (unsigned long long *sp = gemm_stamps_env()) a.stamps = sp;
+        if (p.form == GF_P2_SYM)
+            k5 = gemm_dbg_select<P2_ABL_LIST>(p2_abl_tune(), [](auto d) -> P2Kernel { return dist_sym_p2_kernel<decltype(d)::value>; });
+    }
 #endif
-            static const int grid_tune = mpreid_tune("gemm_grid", 0);   // experiment: persistent workgroups on fewer CUs (same bits)
-            if (grid_tune > 0 && grid_tune < big_cus) big_cus = grid_tune;
-            const dim3 grid(total_tiles < (unsigned)big_cus ? total_tiles : (unsigned)big_cus);
-            if (verbose) {   // (the walk: big_walk_of, the copy of the kernel's rule)
-                const bool sym = (EPI == GE_CAND || EPI == GE_EUCLID) && a.sym;
-                const BigWalk bw = big_walk_of(tiles_m, tiles_n, (int)grid.x, a.walk, sym);
-                char wname[64];
-                if (bw.owned)
-                    snprintf(wname, sizeof wname, "%sowned GR=%d %s", tiles_m % (8 * bw.GR) ? "ragged-" : "", bw.GR,
-                             (a.walk & 7) == 1 ? "column-fastest" : "row-fastest");
-                else
-                    snprintf(wname, sizeof wname, "%s", bw.blocked ? (sym ? "blocked compacted" : "blocked") : "strided");
-                // (the stored-distance epilogue's symmetric instance -- mirrored stores -- says so: the walk name alone does not)
-                snprintf(vline, sizeof vline, "gemm epi %d: persistent 256x256%s, walk %s, %dx%d tiles, grid %u", EPI,
-                         EPI == GE_EUCLID && a.sym ? " (symmetric)" : "", wname, tiles_m, tiles_n, grid.x);
-                gemm_verbose_line(vline);
-            }
-#ifdef MPREID_ABLATION
-            if (dbg == 64 && gemm_epi_is_split(EPI)) {   // operand panels aliased onto two (L2-resident): see set_tile
-                if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, 64>, B_LDS_TOTAL)) return rc;
-                hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, 64>), grid, dim3(512), B_LDS_TOTAL, stream, a, tiles_m, tiles_n);
-            } else if (dbg == 32 && EPI != GE_EUCLID && EPI != GE_BIAS_GELU) {   // per-tile phase stamps for any epilogue (tools/gemm_tile_stamps.py)
-                GemmArgs as = a;
-                const char *sp = getenv("MPREID_GEMM_STAMPS");
-                as.stamps = sp ? reinterpret_cast<unsigned long long *>(strtoull(sp, nullptr, 16)) : nullptr;
-                if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, 32>, B_LDS_TOTAL)) return rc;
-                hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, 32>), grid, dim3(512), B_LDS_TOTAL, stream, as, tiles_m, tiles_n);
-            } else
-#endif
-            if constexpr (EPI == GE_BIAS_F16) {
-#define MPREID_DBG_CASE(D)                                                                                  \
-    case D: {                                                                                               \
-        if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, D>, B_LDS_TOTAL)) return rc;                 \
-        hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, D>), grid, dim3(512), B_LDS_TOTAL, stream, a, tiles_m, tiles_n); \
-        break;                                                                                              \
-    }
-                switch (dbg) {
-                    MPREID_DBG_CASE(1) MPREID_DBG_CASE(2) MPREID_DBG_CASE(3) MPREID_DBG_CASE(4) MPREID_DBG_CASE(5)
-                    MPREID_DBG_CASE(7) MPREID_DBG_CASE(8) MPREID_DBG_CASE(9) MPREID_DBG_CASE(15) MPREID_DBG_CASE(16)
-                    MPREID_DBG_CASE(24)
-                default:
-                    hipLaunchKernelGGL(gemm_f16_big_kernel<EPI>, grid, dim3(512), B_LDS_TOTAL, stream, a, tiles_m, tiles_n);
-                }
-#undef MPREID_DBG_CASE
-            } else if constexpr (EPI == GE_EUCLID || EPI == GE_BIAS_GELU) {
-                if (dbg == 800) {   // stamps + raw stores
-                    GemmArgs as = a;
-                    const char *sp = getenv("MPREID_GEMM_STAMPS");
-                    as.stamps = sp ? reinterpret_cast<unsigned long long *>(strtoull(sp, nullptr, 16)) : nullptr;
-                    if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, 800>, B_LDS_TOTAL)) return rc;
-                    hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, 800>), grid, dim3(512), B_LDS_TOTAL, stream, as, tiles_m, tiles_n);
-                } else if (dbg == 32) {   // (ablation builds) per-tile phase stamps; MPREID_GEMM_STAMPS = device pointer (hex)
-                    GemmArgs as = a;
-                    const char *sp = getenv("MPREID_GEMM_STAMPS");
-                    as.stamps = sp ? reinterpret_cast<unsigned long long *>(strtoull(sp, nullptr, 16)) : nullptr;
-                    if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, 32>, B_LDS_TOTAL)) return rc;
-                    hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, 32>), grid, dim3(512), B_LDS_TOTAL, stream, as, tiles_m, tiles_n);
-                } else if (dbg >= 128 && dbg <= 6 * 128 && dbg % 128 == 0) {   // (ablation builds) store cache policies
-#define MPREID_FLAV_CASE(F)                                                                                         \
-    case F * 128:                                                                                                    \
-        if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, F * 128>, B_LDS_TOTAL)) return rc;                    \
-        hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, F * 128>), grid, dim3(512), B_LDS_TOTAL, stream, a, tiles_m, tiles_n); \
-        break;
-                    switch (dbg) { MPREID_FLAV_CASE(1) MPREID_FLAV_CASE(2) MPREID_FLAV_CASE(3) MPREID_FLAV_CASE(4) MPREID_FLAV_CASE(5) MPREID_FLAV_CASE(6) }
-#undef MPREID_FLAV_CASE
-                } else if (dbg == 16) {   // (ablation builds) the unpaired DMA schedule
-                    if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, 16>, B_LDS_TOTAL)) return rc;
-                    hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, 16>), grid, dim3(512), B_LDS_TOTAL, stream, a, tiles_m, tiles_n);
-                } else if (EPI == GE_EUCLID && a.sym) {   // symmetric problem: the instance with the mirrored stores
-                    if constexpr (EPI == GE_EUCLID) {
-                        if (const int rc = mpreid_dyn_lds(gemm_f16_big_kernel<EPI, 0, true>, B_LDS_TOTAL)) return rc;
-                        hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, 0, true>), grid, dim3(512), B_LDS_TOTAL, stream, a, tiles_m, tiles_n);
-                    }
-                } else {
-                    hipLaunchKernelGGL(gemm_f16_big_kernel<EPI>, grid, dim3(512), B_LDS_TOTAL, stream, a, tiles_m, tiles_n);
-                }
-            } else {
-                hipLaunchKernelGGL(gemm_f16_big_kernel<EPI>, grid, dim3(512), B_LDS_TOTAL, stream, a, tiles_m, tiles_n);
-            }
-        }
-    } else {
-        if (verbose) {
-            snprintf(vline, sizeof vline, "gemm epi %d: 128x128, %dx%d tiles, grid %u", EPI, tiles_m, tiles_n,
-                     (unsigned)tiles_m * (unsigned)tiles_n);
-            gemm_verbose_line(vline);
-        }
-        hipLaunchKernelGGL(gemm_f16_kernel<EPI>, dim3((unsigned)tiles_m * (unsigned)tiles_n), dim3(256), G_LDS_BYTES,
-                               stream, a, tiles_m, tiles_n);
-    }
-    LAUNCH_CHECK();
-    if (e0) {
-        HIP_TRY(hipEventRecord(e1, stream));
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        ProfClass &pc = g_prof[std::make_tuple(EPI, a.M, a.N, a.K)];
-        pc.ev.emplace_back(e0, e1);
-        pc.m = std::max<int64_t>(pc.m, a.M);
-        // split mode: three products per logical multiply-add are EXECUTED on the matrix cores
-        pc.flops_total += 2.0 * (double)a.M * (double)a.N * (gemm_epi_is_split(EPI) ? 3.0 * (double)a.kseg : (double)a.K);
-    }
-    return MPREID_OK;
+    if (t.verbose) gemm_verbose_line(p.text);
+    a.walk = p.walk;
+    a.stagger = p.stagger;
+    a.stagger_mode = p.stagger_mode;
+    // split mode: three products per logical multiply-add are EXECUTED on the matrix cores
+    const double work = 2.0 * (double)a.M * (double)a.N * (gemm_epi_is_split(EPI) ? 3.0 * (double)a.kseg : (double)a.K);
+    if constexpr (EPI == GE_EUCLID)
+        if (is_p2) return launch_profiled(k5, p, stream, EPI, work, a, p.tiles_m, p.tiles_n, p.naps, p.strip);
+    return launch_profiled(k3, p, stream, EPI, work, a, p.tiles_m, p.tiles_n);
 }
 
 int launch_gemm_f16(const GemmArgs &a, int epi, hipStream_t stream) {

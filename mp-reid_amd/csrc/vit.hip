@@ -1573,7 +1573,7 @@ static int launch_attention(const _Float16 *qkv, int B, int L, int W, int heads,
     });
     if (rc) return rc;
     if (!blocks_per_cu) blocks_per_cu = occ_dev[dev];   // queried by an earlier call on this device
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    if ((rc = mpreid_device_cus(&cus))) return rc;
     const int total = B * heads;
     int grid = cus * blocks_per_cu;
     if (grid > total) grid = total;
@@ -1600,7 +1600,7 @@ static int launch_attention_split(const float *qkv, int B, int L, int W, int hea
         return MPREID_OK;
     });
     if (rc) return rc;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    if ((rc = mpreid_device_cus(&cus))) return rc;
     const int total = B * heads;
     // persistent: as many workgroups as the LDS lets a CU hold (one for L = 129; the small test shapes fit several)
     int per_cu = (int)((160 * 1024) / lds);

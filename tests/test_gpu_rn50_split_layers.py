@@ -98,7 +98,7 @@ CASES = [
 
 
 # ---- 1x1 on the PERSISTENT 256x256 kernel (gemm_f16_big_kernel), in the launcher's production dispatch ----
-# launch_one (csrc/gemm_f16.hip) takes that kernel when Mp % 256 == 0, npad % 256 == 0 and there are at least 128 tiles of
+# launch_one (csrc/gemm_f16.hip; its plan: csrc/gemm_plan.h) takes that kernel when Mp % 256 == 0, npad % 256 == 0 and there are at least 128 tiles of
 # 256x256; its grid is min(tiles, CU count).  kseg = 64 / 128 give the 6- and 12-stage pipelines of RN50's layer1 / layer2.
 # `walk`: what the kernel's rule gives on 256 CUs (owned: the grid is a multiple of 8 and the tile rows divide into 8 XCDs x
 # groups of 8, or -- ragged -- there are at least 24 groups; blocked: a full grid of a multiple of 64 workgroups; else strided).
@@ -488,7 +488,7 @@ def test_split_layer_argument_checks():
 
 # ---- the persistent 256x256 kernel -----------------------------------------------------------------------------------------
 def _assert_production_dispatch_takes_the_big_kernel(c):
-    """launch_one (csrc/gemm_f16.hip): use_big = M % 256 == 0 && N % 256 == 0 && (M / 256) * (N / 256) >= 128, with gemm_big at
+    """plan_gemm (csrc/gemm_plan.h, launch_one's plan): use_big = M % 256 == 0 && N % 256 == 0 && (M / 256) * (N / 256) >= 128, with gemm_big at
     its default -- M = Mp, N = npad here (conv_split, csrc/rn50_f32.hip)"""
     npad = (c.cout + 127) // 128 * 128
     assert "gemm_big" not in os.environ.get("MPREID_TUNE", ""), "these cases test the default dispatch"
