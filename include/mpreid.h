@@ -624,6 +624,44 @@ int mpreid_text_forward(const mpreid_text_cfg *cfg, const mpreid_text_weights *w
 int mpreid_text_attention(const void *qkv_dev, int batch, int tokens, int width, int heads, void *out_dev,
                           mpreid_stream_t stream);
 
+/* ---- The text tower's gradient with respect to the prompts (prompt learning: every tower weight stays frozen) ----
+ * grad_prompts = d loss / d prompts given grad_out = d loss / d (the output of mpreid_text_forward).  No weight gradient, no
+ * optimizer, no loss.  The call is stateless: it re-runs the forward's own split-precision blocks, keeping each block's input,
+ * then walks the layers back.  Per layer it recomputes q | k | v, the block's mid-point and the fp32 FC1 pre-activation with the
+ * forward's launchers, so the gradient is taken at the activations the forward really produces.  Every gradient GEMM
+ * (dX = dY . W) is the exact fp32 GEMM over mpreid_text_weights_t: fp32 TRANSPOSED copies [in][out] of the frozen matrices
+ * (gradients of a prompt-learning loss sit far below fp16's range, so they never pass through fp16 pair operands).  Causal
+ * attention, LayerNorm and QuickGELU are differentiated by fp32 kernels without atomics: the same bits from run to run.
+ * Properties: prompt b's gradient does not depend on the batch it is computed in; rows behind eot[b] are exactly 0.0; the
+ * result is exactly homogeneous in grad_out under power-of-two scaling (short of underflow); every element of grad_prompts
+ * is written.  Limits and errors as for mpreid_text_forward (all before anything is launched); prompts_dev, grad_prompts_dev
+ * and the transposed matrices 16-byte aligned, the workspace 256; the contents of eot_dev are validated by the caller. */
+typedef struct {                       /* device pointers, fp32, [in][out] = the transpose of the checkpoint's [out][in] */
+    const float *in_proj_t;            /* [width][3 * width] */
+    const float *out_proj_t;           /* [width][width] */
+    const float *fc_t;                 /* [width][4 * width] */
+    const float *proj_t;               /* [4 * width][width] */
+} mpreid_text_layer_t;
+typedef struct {
+    const float *proj_t;               /* text_projection transposed, [out_dim][width] */
+    const mpreid_text_layer_t *layers; /* HOST array of cfg.layers entries */
+} mpreid_text_weights_t;
+size_t mpreid_text_backward_workspace_bytes(const mpreid_text_cfg *cfg, int batch);   /* needs no device; 0 for a bad request */
+int mpreid_text_backward(const mpreid_text_cfg *cfg, const mpreid_text_weights *w, const mpreid_text_weights_t *wt,
+                         const float *prompts_dev, const int32_t *eot_dev, const float *grad_out_dev /* [B][out_dim] */,
+                         int batch, float *grad_prompts_dev /* [B][tokens][width], every element written */,
+                         void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
+/* The causal attention backward kernel alone, for unit tests and tools: qkv_dev fp32 [batch * tokens][3 * width] as for
+ * mpreid_text_attention, d_o_dev fp32 [batch * tokens][width] -> d_qkv_dev fp32 [batch * tokens][3 * width] = dq | dk | dv; all
+ * 16-byte aligned.  Every element of d_qkv_dev is written and no other byte. */
+int mpreid_text_attention_backward(const float *qkv_dev, const float *d_o_dev, int batch, int tokens, int width, int heads,
+                                   float *d_qkv_dev, mpreid_stream_t stream);
+/* LayerNorm's input gradient (biased variance, eps 1e-5, statistics recomputed from x_dev): rows of `width` fp32 values,
+ * dx = (gamma o dy - mean(gamma o dy) - xhat * mean(gamma o dy o xhat)) / sigma; accumulate != 0 adds it to what dx_dev holds.
+ * dx_dev must not overlap the inputs. */
+int mpreid_layernorm_backward_f32(const float *x_dev, const float *dy_dev, const float *gamma_dev, int64_t rows, int width,
+                                  int accumulate, float *dx_dev, mpreid_stream_t stream);
+
 /* processor/processor_uniprompt_stage2.py:636-640: out[rows][dim] = mean over the views of
  * feats[n_views][rows][dim] (sequential sum in view order, true division), then F.normalize(p=2, dim=1,
  * eps=1e-12) when normalize != 0. */

@@ -21,6 +21,7 @@
 
 #include "gemm_f16.h"
 #include "moe.h"
+#include "text_tower.h"
 
 // ---------------------------------------------------------------------------------------------
 // im2col: img [B][3][H][W] fp32 -> patches [MPpad][3*p*p] fp16; rows >= B*P are zero
@@ -1785,8 +1786,11 @@ static int block_attention_part(const BlockCtx &c, const mpreid_vit_layer &ly, c
 // xr += out_proj(ar); xr += mlp(ln_2(xr)) over `rows` rows (rows_pad: the GEMMs' row count; hr: the MLP's hidden buffer).
 // Blocks l < moe->moe_layers of an MoE tower (moe != nullptr; vm places its workspace share behind base) run router and
 // dispatch (l == 0 only), grouped FC1 / FC2 and combine (csrc/moe.hip) in place of FC1 and FC2
+// fc1_f32 (the text tower's backward sweep, text_block_recompute): FC1 leaves its pre-activation there in fp32 [rows_pad][4W]
+// and the part ends before FC2, with xr = the block's mid-point
 static int block_mlp_part(const BlockCtx &c, const mpreid_vit_layer &ly, float *xr, _Float16 *ar, _Float16 *hr, int rows,
-                          int rows_pad, const mpreid_vit_moe *moe, int l, const VitMoeLayout *vm, char *base) {
+                          int rows_pad, const mpreid_vit_moe *moe, int l, const VitMoeLayout *vm, char *base,
+                          float *fc1_f32 = nullptr) {
     const int W = c.W;
     int rc;
     GemmArgs g{};
@@ -1809,7 +1813,13 @@ static int block_mlp_part(const BlockCtx &c, const mpreid_vit_layer &ly, float *
     }
     g = GemmArgs{};
     g.A = ar; g.W = (const _Float16 *)ly.fc_w; g.M = rows_pad; g.N = 4 * W;
-    g.out = hr; g.ldo = c.pr * 4 * W; g.bias = ly.fc_b;
+    g.bias = ly.fc_b;
+    if (fc1_f32) {
+        ARG_CHECK(c.split);   // there is no fp32 epilogue among the fp16 mode's
+        g.out = fc1_f32; g.ldo = 4 * W;
+        return linear(c, g, W, ly.fc_s, GE_BIAS_F16, GE_S_BIAS_F32);
+    }
+    g.out = hr; g.ldo = c.pr * 4 * W;
     if ((rc = linear(c, g, W, ly.fc_s, GE_BIAS_GELU, GE_S_BIAS_GELU))) return rc;
     g = GemmArgs{};
     g.A = hr; g.W = (const _Float16 *)ly.proj_w; g.M = rows_pad; g.N = W;
@@ -2442,7 +2452,7 @@ static int attention_causal_dispatch(const float *qkv, int B, int L, int W, int 
     return launch_attention_causal<8>(qkv, B, L, W, heads, out, stream);
 }
 
-static int text_check_shape(int tokens, int width, int heads) {
+int text_check_shape(int tokens, int width, int heads) {
     if (check_width_heads(width, heads) != SHAPE_OK) {
         mpreid_set_error("text tower: head dim must be 64 and the width a multiple of 128 up to 1024 (width %d, heads %d)", width, heads);
         return MPREID_ERR_UNSUPPORTED;
@@ -2538,12 +2548,7 @@ __global__ __launch_bounds__(256) void text_proj_kernel(const float *__restrict_
         if (b0 + i < B) out[(int64_t)(b0 + i) * out_dim + o] = acc[i];
 }
 
-struct TextLayout {
-    int64_t M, Mpad;
-    size_t x, a, qkv, hbuf, y, total;
-};
-
-static TextLayout text_layout(const mpreid_text_cfg *c, int B) {
+TextLayout text_layout(const mpreid_text_cfg *c, int B) {
     TextLayout v{};
     v.M = (int64_t)B * c->tokens;
     v.Mpad = (int64_t)align_up((size_t)v.M, 256);   // 256-row tiles of the big GEMM kernel
@@ -2558,10 +2563,32 @@ static TextLayout text_layout(const mpreid_text_cfg *c, int B) {
     return v;
 }
 
-static int text_check_cfg(const mpreid_text_cfg *c) {
+int text_check_cfg(const mpreid_text_cfg *c) {
     ARG_CHECK(c != nullptr);
     ARG_CHECK(c->layers >= 0 && c->out_dim > 0);
     return text_check_shape(c->tokens, c->width, c->heads);
+}
+
+int text_embed(const float *prompts, const float *pos, int64_t M, int L, int W, float *x, hipStream_t stream) {
+    const int64_t n4 = M * (W / 4);
+    hipLaunchKernelGGL(text_add_pos_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, prompts, pos, M, L, W, x);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
+// the split mode's blocks (mpreid_vit_forward), causal
+int text_block(const mpreid_text_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *qkv, _Float16 *hbuf,
+               int M, int Mpad, hipStream_t stream) {
+    const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, cfg->tokens};
+    const int rc = block_attention_part(ctx, ly, x, a, qkv, M, Mpad, ATTN_CAUSAL);
+    return rc ? rc : block_mlp_part(ctx, ly, x, a, hbuf, M, Mpad, nullptr, 0, nullptr, nullptr);
+}
+
+int text_block_recompute(const mpreid_text_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *qkv,
+                         float *u, int M, int Mpad, hipStream_t stream) {
+    const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, cfg->tokens};
+    const int rc = block_attention_part(ctx, ly, x, a, qkv, M, Mpad, ATTN_CAUSAL);
+    return rc ? rc : block_mlp_part(ctx, ly, x, a, nullptr, M, Mpad, nullptr, 0, nullptr, nullptr, u);
 }
 
 extern "C" size_t mpreid_text_workspace_bytes(const mpreid_text_cfg *cfg, int batch) {
@@ -2592,18 +2619,9 @@ extern "C" int mpreid_text_forward(const mpreid_text_cfg *cfg, const mpreid_text
     float *qkv = (float *)(base + v.qkv);
     _Float16 *hbuf = (_Float16 *)(base + v.hbuf);
     float *y = (float *)(base + v.y);
-    const BlockCtx ctx{stream, true, 2, W, cfg->heads, B, L};   // the split mode's blocks (mpreid_vit_forward), causal
-    {
-        const int64_t n4 = v.M * (W / 4);
-        hipLaunchKernelGGL(text_add_pos_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, prompts, w->pos_emb, v.M, L,
-                           W, x);
-        LAUNCH_CHECK();
-    }
-    for (int l = 0; l < cfg->layers; ++l) {
-        const mpreid_vit_layer &ly = w->layers[l];
-        if ((rc = block_attention_part(ctx, ly, x, a, qkv, (int)v.M, (int)v.Mpad, ATTN_CAUSAL))) return rc;
-        if ((rc = block_mlp_part(ctx, ly, x, a, hbuf, (int)v.M, (int)v.Mpad, nullptr, l, nullptr, nullptr))) return rc;
-    }
+    if ((rc = text_embed(prompts, w->pos_emb, v.M, L, W, x, stream))) return rc;
+    for (int l = 0; l < cfg->layers; ++l)
+        if ((rc = text_block(cfg, B, w->layers[l], x, a, qkv, hbuf, (int)v.M, (int)v.Mpad, stream))) return rc;
     // ln_final on the end-of-text row alone (LayerNorm is per row: the same values as normalising every row first), @ proj
     hipLaunchKernelGGL(text_eot_ln_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, stream, x, eot, B, L, W, w->ln_final_g,
                        w->ln_final_b, y);

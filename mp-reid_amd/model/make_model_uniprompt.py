@@ -22,8 +22,17 @@ live in a holder that is built at the first ``get_text`` call -- from the checkp
 complete set (``text_encoder.*`` and ``prompt_learner.{ctx_generic, ctx_modality, ctx_platform, token_prefix,
 token_suffix}``), else from the seeded initialisation (``MODEL.INIT_SEED``), as the image tower does with an empty
 ``TEST.WEIGHT``.  ``get_text`` / ``get_raw_text`` without ``label``, the MLP feature fusion (``get_image_update``), the
-multi-token variant (``get_more_image``) and training mode raise NotImplementedError; test-time prompt tuning (a
-backward pass through the text tower) is out of scope.  ``load_param`` skips the checkpoint keys of modules this build
+multi-token variant (``get_more_image``) and training mode raise NotImplementedError.
+
+Prompt learning (reference processor/processor_uniprompt_stage1.py:44-100): ``enable_stage1a_training()`` /
+``enable_stage1b_training()`` (:138-157) mark ``ctx_generic``, or ``ctx_modality`` and ``ctx_platform``, as leaves that
+require grad.  While grad mode is on and the assembled prompts require grad, ``get_text`` runs
+``TextEncoder.forward_grad``: the same features, as a node of torch's autograd graph whose backward is the library's
+prompt gradient (mpreid_text_backward; the tower's weights stay frozen), and autograd carries it through the prompt
+assembly to the context tensors.  ``prompt_learner.parameters()`` hands them to a ``torch.optim`` optimizer,
+``text_state_dict()`` gives the tower and prompt tensors under the reference's checkpoint keys.  The model stays in
+``.eval()`` throughout (neither branch has a mode-dependent layer).  Otherwise -- no stage enabled, or under
+``torch.no_grad()`` -- the call is the evaluation call, bit for bit.  ``load_param`` skips the checkpoint keys of modules this build
 does not have (``prompt_learner.visual_enhanced_net.*``, ``image_fusion_net.*``, unknown keys under those prefixes), and
 an INCOMPLETE set of text-tower tensors as a whole.
 
@@ -80,6 +89,10 @@ class PromptLearner:
 
     def set_training_stage(self, stage):
         self.training_stage = stage
+
+    def parameters(self):
+        """the three context tensors (what the reference's nn.Module registers as parameters), for torch.optim.*"""
+        return iter([self.ctx_generic, self.ctx_modality, self.ctx_platform])
 
     def set_tensors(self, tensors, device=None):
         for k in PROMPT_KEYS:
@@ -163,6 +176,7 @@ class build_transformer(_base.build_transformer):
         self.prompt_learner = PromptLearner()
         self._text_source = None    # (text state dict, prompt tensors) of the last checkpoint that carried a complete set
         self._text_encoder = None
+        self._text_sd = None        # the state dict self._text_encoder was built from (text_state_dict)
 
     def _invalidate(self):
         super()._invalidate()
@@ -179,7 +193,40 @@ class build_transformer(_base.build_transformer):
             enc = _ops.TextEncoder(TEXT_CFG, sd, ws_tag="text")
             self.prompt_learner.set_tensors(prompt, enc.device)
             self._text_encoder = enc
+            self._text_sd = sd
         return self._text_encoder
+
+    def _enable_stage(self, stage, trained):
+        self.text_tower()
+        pl = self.prompt_learner
+        pl.set_training_stage(stage)
+        for p in pl.parameters():
+            p.requires_grad_(False)
+            p.grad = None
+        for name in trained:
+            getattr(pl, name).requires_grad_(True)
+
+    def enable_stage1a_training(self):
+        """Stage 1a (reference :138-146): only the generic context vectors are trained"""
+        print("Enabling Stage 1a Training: Generic Context only.")
+        self._enable_stage('1a', ("ctx_generic",))
+
+    def enable_stage1b_training(self):
+        """Stage 1b (reference :148-157): only the modality and platform context vectors are trained"""
+        print("Enabling Stage 1b Training: Domain-Specific Context only.")
+        self._enable_stage('1b', ("ctx_modality", "ctx_platform"))
+
+    def text_state_dict(self):
+        """the text tower and the prompt tensors (as they stand, tuned or not) under the reference's checkpoint key names,
+        on the host: torch.save(model.text_state_dict(), path), then load_param(path)"""
+        self.text_tower()
+
+        def host(v):
+            return (torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach()).float().cpu().clone()
+        out = {"text_encoder." + k: host(self._text_sd[k]) for k in text_shapes()}
+        for k in PROMPT_KEYS:
+            out["prompt_learner." + k] = getattr(self.prompt_learner, k).detach().cpu().clone()
+        return out
 
     def _eot_rows(self, b):
         tok = self.prompt_learner.tokenized_prompts
@@ -193,6 +240,8 @@ class build_transformer(_base.build_transformer):
     def _text_features(self, label, view):
         enc = self.text_tower()
         prompts = self.prompt_learner(label, view=view)
+        if torch.is_grad_enabled() and prompts.requires_grad:   # prompt learning: see the module docstring
+            return enc.forward_grad(prompts, self._eot_rows(prompts.shape[0]))
         return enc.forward(prompts, self._eot_rows(prompts.shape[0]))
 
     def _raw_features(self, x, view):

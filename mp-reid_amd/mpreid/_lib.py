@@ -75,6 +75,16 @@ class TextWeights(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("pos_emb", "ln_final_g", "ln_final_b", "proj")] + [("layers", C.POINTER(VitLayer))]
 
 
+class TextLayerT(C.Structure):
+    """mpreid_text_layer_t: fp32 [in][out] copies of a block's four frozen matrices (the gradient GEMMs' operands)"""
+    _fields_ = [(k, C.c_void_p) for k in ("in_proj_t", "out_proj_t", "fc_t", "proj_t")]
+
+
+class TextWeightsT(C.Structure):
+    """mpreid_text_weights_t"""
+    _fields_ = [("proj_t", C.c_void_p), ("layers", C.POINTER(TextLayerT))]
+
+
 class ImageIn(C.Structure):
     """mpreid_image_in: the image batch of every encoder forward; exactly one of the two pointers is non-NULL"""
     _fields_ = [("f32_dev", C.c_void_p), ("u8_hwc_dev", C.c_void_p), ("mean", C.c_float * 3), ("std", C.c_float * 3),
@@ -210,6 +220,12 @@ PROTOTYPES = {
     "mpreid_text_workspace_bytes": (sz, [P(TextCfg), i32]),
     "mpreid_text_forward": (i32, [P(TextCfg), P(TextWeights), vp, vp, i32, vp, vp, sz, vp]),
     "mpreid_text_attention": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    # its gradient with respect to the prompts: (cfg, weights, transposed fp32 weights, prompts, eot rows, grad_out, B,
+    # grad_prompts, workspace, workspace bytes, stream)
+    "mpreid_text_backward_workspace_bytes": (sz, [P(TextCfg), i32]),
+    "mpreid_text_backward": (i32, [P(TextCfg), P(TextWeights), P(TextWeightsT), vp, vp, vp, i32, vp, vp, sz, vp]),
+    "mpreid_text_attention_backward": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+    "mpreid_layernorm_backward_f32": (i32, [vp, vp, vp, i64, i32, i32, vp, vp]),
     "mpreid_tta_mean_f32": (i32, [vp, i32, i64, i32, i32, vp, vp]),
     "mpreid_resize_workspace_bytes": (sz, [i32, i32, i32]),
     "mpreid_resize_bilinear_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),

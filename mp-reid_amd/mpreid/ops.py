@@ -1197,6 +1197,41 @@ def text_attention(qkv: torch.Tensor, batch: int, tokens: int, heads: int, out: 
     return out
 
 
+def text_attention_backward(qkv: torch.Tensor, d_o: torch.Tensor, batch: int, tokens: int, heads: int,
+                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the causal attention backward kernel alone (mpreid_text_attention_backward).  qkv: fp32 [batch * tokens, 3 * width] as
+    for text_attention, d_o: fp32 [batch * tokens, width] -> dq | dk | dv, fp32 [batch * tokens, 3 * width]; `out` may be a
+    view into a larger buffer (the tests put guard rows around it)."""
+    _lib.require_gpu()
+    width = 64 * heads
+    assert qkv.is_cuda and qkv.is_contiguous() and tuple(qkv.shape) == (batch * tokens, 3 * width)
+    assert d_o.is_cuda and d_o.is_contiguous() and tuple(d_o.shape) == (batch * tokens, width)
+    if qkv.dtype != torch.float32 or d_o.dtype != torch.float32:
+        _text_unsupported("mpreid_text_attention_backward")
+    if out is None:
+        out = torch.empty((batch * tokens, 3 * width), dtype=torch.float32, device=qkv.device)
+    assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (batch * tokens, 3 * width)
+    _lib.check(_lib.load().mpreid_text_attention_backward(_ptr(qkv), _ptr(d_o), int(batch), int(tokens), width, int(heads),
+                                                          _ptr(out), _lib.stream_ptr()), "mpreid_text_attention_backward")
+    return out
+
+
+def layernorm_backward(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LayerNorm's input gradient (mpreid_layernorm_backward_f32: biased variance, eps 1e-5, statistics recomputed from x).
+    x, dy: fp32 [rows, width], gamma [width] -> dx [rows, width]; with `out` given the gradient is ADDED to it (the form of the
+    residual joins) and `out` is returned."""
+    dev = _lib.require_gpu()
+    x, dy, gamma = _dev_f32(x, dev), _dev_f32(dy, dev), _dev_f32(gamma, dev)
+    assert x.dim() == 2 and dy.shape == x.shape and tuple(gamma.shape) == (x.shape[1],)
+    acc = out is not None
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and out.shape == x.shape
+    _lib.check(_lib.load().mpreid_layernorm_backward_f32(_ptr(x), _ptr(dy), _ptr(gamma), x.shape[0], x.shape[1], int(acc),
+                                                         _ptr(out), _lib.stream_ptr()), "mpreid_layernorm_backward_f32")
+    return out
+
+
 def check_eot(eot, batch: int, tokens: int) -> np.ndarray:
     """the read-out rows of a prompt batch as int32 [batch], validated on the host (the library does not look at them):
     integers with 0 <= eot < tokens, else ValueError"""
@@ -1227,6 +1262,8 @@ class TextEncoder:
         self.ws_tag = ws_tag
         self.cfg = {k: int(cfg[k]) for k in ("tokens", "width", "layers", "heads", "out_dim")}
         get = _state_getter(state_dict, "text_encoder.")
+        self._get = get      # backward() builds its transposed fp32 weights from the same tensors, at its first call
+        self.c_wt = None
 
         def f32(name, shape):
             t = get(name).to(device=dev, dtype=torch.float32).contiguous()
@@ -1278,6 +1315,57 @@ class TextEncoder:
 
     __call__ = forward
 
+    def _transposed_weights(self):
+        """mpreid_text_weights_t: fp32 [in][out] copies of the frozen matrices (~150 MB at CLIP's size), made once"""
+        if self.c_wt is None:
+            def tr(name):
+                return self._get(name).to(device=self.device, dtype=torch.float32).t().contiguous()
+            nl = self.cfg["layers"]
+            layers = (_lib.TextLayerT * max(nl, 1))()
+            keep = []
+            for i in range(nl):
+                b = f"transformer.resblocks.{i}."
+                for field, key in (("in_proj_t", "attn.in_proj_weight"), ("out_proj_t", "attn.out_proj.weight"),
+                                   ("fc_t", "mlp.c_fc.weight"), ("proj_t", "mlp.c_proj.weight")):
+                    keep.append(tr(b + key))
+                    setattr(layers[i], field, keep[-1].data_ptr())
+            keep.append(tr("text_projection"))
+            wt = _lib.TextWeightsT()
+            wt.proj_t = keep[-1].data_ptr()
+            wt.layers = C.cast(layers, C.POINTER(_lib.TextLayerT))
+            self._keep_t = (keep, layers)
+            self.c_wt = wt
+        return self.c_wt
+
+    @torch.no_grad()
+    def backward(self, prompts: torch.Tensor, eot, grad_out: torch.Tensor) -> torch.Tensor:
+        """d loss / d prompts, fp32 [B, tokens, width], given grad_out = d loss / d forward(prompts, eot) [B, out_dim]; the
+        tower's weights are frozen (mpreid_text_backward: it re-runs the forward itself, so no earlier forward call is needed).
+        At most CHUNK prompts per library call, through one workspace (tag ws_tag + "_grad")."""
+        L = _lib.load()
+        n_tok, w, od = self.cfg["tokens"], self.cfg["width"], self.cfg["out_dim"]
+        if prompts.dim() != 3 or tuple(prompts.shape[1:]) != (n_tok, w):
+            raise ValueError(f"prompts: expected [B, {n_tok}, {w}], got {tuple(prompts.shape)}")
+        B = prompts.shape[0]
+        if tuple(grad_out.shape) != (B, od):
+            raise ValueError(f"grad_out: expected [{B}, {od}], got {tuple(grad_out.shape)}")
+        e = torch.from_numpy(check_eot(eot, B, n_tok)).to(self.device)
+        x, g = _dev_f32(prompts, self.device), _dev_f32(grad_out, self.device)
+        wt = self._transposed_weights()
+        out = torch.empty((B, n_tok, w), dtype=torch.float32, device=self.device)
+        for s in range(0, B, self.CHUNK):
+            n = min(B, s + self.CHUNK) - s
+            ws = _workspace(self.ws_tag + "_grad", L.mpreid_text_backward_workspace_bytes(C.byref(self.c_cfg), n), self.device)
+            _lib.check(L.mpreid_text_backward(C.byref(self.c_cfg), C.byref(self.c_w), C.byref(wt), _ptr(x[s:]), _ptr(e[s:]),
+                                              _ptr(g[s:]), n, _ptr(out[s:]), _ptr(ws), ws.numel(), _lib.stream_ptr()),
+                       "mpreid_text_backward")
+        return out
+
+    def forward_grad(self, prompts: torch.Tensor, eot) -> torch.Tensor:
+        """forward(prompts, eot) as a node of torch's autograd graph, differentiable with respect to `prompts` only: its
+        backward is backward(prompts, eot, the incoming gradient)"""
+        return _TextForwardGrad.apply(prompts, self, check_eot(eot, prompts.shape[0], self.cfg["tokens"]))
+
     def encode_tokens(self, token_ids: torch.Tensor) -> torch.Tensor:
         """model/clip/model.py:609-619: forward(token_embedding[token_ids], token_ids.argmax(-1)); the embedding gather is
         torch indexing on the device"""
@@ -1289,6 +1377,22 @@ class TextEncoder:
         if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.token_embedding.shape[0]):
             raise ValueError(f"token_ids outside the embedding table of {self.token_embedding.shape[0]} rows")
         return self.forward(self.token_embedding[ids], ids.argmax(dim=-1))
+
+
+class _TextForwardGrad(torch.autograd.Function):
+    """TextEncoder.forward_grad"""
+
+    @staticmethod
+    def forward(ctx, prompts, enc, eot):
+        ctx.enc, ctx.eot = enc, eot
+        ctx.save_for_backward(prompts)
+        return enc.forward(prompts, eot)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (prompts,) = ctx.saved_tensors
+        grad = ctx.enc.backward(prompts, ctx.eot, grad_out)
+        return grad.to(device=prompts.device, dtype=prompts.dtype), None, None
 
 
 def _np_getter(state_dict):

@@ -11,7 +11,9 @@ patch-gather kernel (no transformed image tensors) and the average + normalise i
 BEFORE it (:594), so a batch straddling num_query is augmented as a whole; TEST.FEAT_NORM is a truthy string.
 
 ``do_inference_ttpt_clipstyle`` (option B) matches images against text features of the prompt learner and
-optimises prompts at test time: text tower, out of scope -> NotImplementedError.
+optimises prompts at test time.  The text tower and its prompt gradient exist (model(label=..., get_text=True) after
+model.enable_stage1a_training()), but the reference's branch reads prompt_learner.cls_ctx and num_class, which its own
+PromptLearner does not have: there is no reference behaviour to reproduce -> NotImplementedError.
 """
 import logging
 import time
@@ -63,9 +65,11 @@ def do_inference(cfg, model, val_loader, num_query):
 
 
 def do_inference_ttpt_clipstyle(cfg, model, val_loader, num_query):
-    raise NotImplementedError("TTA + TTPT with CLIP-style image-text matching (option B) tunes cls_ctx by backpropagation through "
-                              "the text tower: its forward pass exists (model(label=..., get_text=True)), the prompt-tuning "
-                              "backward pass does not; only option A (image features) is on the accelerated path")
+    raise NotImplementedError("TTA + TTPT with CLIP-style image-text matching (option B) tunes prompt_learner.cls_ctx over num_class "
+                              "prompts, which the reference's own PromptLearner does not have: there is no reference behaviour to "
+                              "reproduce.  The pieces exist (model(label=..., get_text=True) is differentiable with respect to the "
+                              "context vectors after model.enable_stage1a_training()); only option A (image features) is on the "
+                              "accelerated path")
 
 
 def do_inference_ttpt_option_a(cfg, model, val_loader, num_query):

@@ -103,6 +103,11 @@ def main():
     readelf = os.environ.get("LLVM_READELF", "/opt/rocm/lib/llvm/bin/llvm-readelf")
     work = args.keep or tempfile.mkdtemp(prefix="device_code_diff_")
     sources = [s for s in b.SOURCES if s.endswith(".hip")]
+    # a source the old tree does not have yet is a NEW file: named, not compared (its kernels cannot change an old one)
+    new_files = [s for s in sources if not os.path.exists(os.path.join(args.old_csrc, s))]
+    sources = [s for s in sources if s not in new_files]
+    for s in new_files:
+        print("%-16s only in the new tree: not compared" % s, flush=True)
     jobs = []
     for tag, csrc in (("old", args.old_csrc), ("new", args.new_csrc)):
         os.makedirs(os.path.join(work, tag), exist_ok=True)
