@@ -515,7 +515,8 @@ int mpreid_vit_forward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, c
  *   MPREID_VIT_F16     [batch * tokens][width]        softmax(q k^T / 8) v
  *   MPREID_VIT_SPLIT   [batch * tokens][2 * width]    [hi(width) | lo(width)], hi = fp16(o), lo = fp16(o - hi)
  * q_tiles 0: every token row of every image is written; q_tiles n > 0: the first min(16 n, tokens) rows of every image
- * (the forward's last block asks for 1: the CLS row's tile) and no other byte of out_dev.  width = 64 * heads,
+ * (the forward's last block asks for 1: the CLS row's tile) and no other byte of out_dev; the rows a partial call writes carry
+ * the bits of the same rows of a q_tiles = 0 call, in every kernel form (tests/test_gpu_attention_direct_forms.py).  width = 64 * heads,
  * 2 <= tokens <= MPREID_VIT_MAX_TOKENS; anything else is MPREID_ERR_ARG before a launch. */
 int mpreid_vit_attention(const void *qkv_dev, int precision, int batch, int tokens, int width, int heads, int q_tiles,
                          void *out_dev, mpreid_stream_t stream);
@@ -528,6 +529,13 @@ size_t mpreid_vit_workspace_bytes_f32(const mpreid_vit_cfg *cfg, int batch);
 int mpreid_vit_forward_f32(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w_f32, const mpreid_image_in *img, int batch,
                            const float *cv_emb_dev, float *out_dev, void *ws_dev, size_t ws_bytes,
                            mpreid_stream_t stream);
+/* The attention step of the all-fp32 mode alone, for unit tests and tools: the host rule mpreid_vit_forward_f32 runs in every
+ * block (K / V resident in LDS up to tokens = 320, streamed in 128-key chunks above), on the caller's buffers.  qkv_dev fp32
+ * [batch * tokens][3 * width] in the column layout of mpreid_vit_attention, out_dev fp32 [batch * tokens][width] =
+ * softmax(q k^T / 8) v, both 16-byte aligned.  Every row is written and no other byte of out_dev.  width = 64 * heads,
+ * 2 <= tokens <= MPREID_VIT_MAX_TOKENS; anything else is MPREID_ERR_ARG before a launch. */
+int mpreid_vit_attention_f32(const float *qkv_dev, int batch, int tokens, int width, int heads,
+                             float *out_dev /* [batch * tokens][width] */, mpreid_stream_t stream);
 /* ---- MoE image encoder: model/clip/model.py:163-258 (MoEResidualAttentionBlock), 283-330 (MoETransformer) -------------
  * With MODEL.MOE.ENABLED the first moe_layers blocks of the image tower replace their MLP by num_experts expert MLPs behind a
  * softmax gate, every token goes to its top_k experts, and the routing is decided ONCE, in block 0, and reused by every

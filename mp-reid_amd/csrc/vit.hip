@@ -2113,6 +2113,29 @@ __global__ __launch_bounds__(256) void attention_f32_chunked_kernel(const float 
     for (int c = 0; c < 64; ++c) o[c] = __fdiv_rn(acc[c], l);
 }
 
+// The all-fp32 attention step: K / V of a head resident in LDS where they fit (L * 512 B <= 160 KB, L <= 320), streamed in
+// chunks above that.  The one place that takes the choice: the forward's blocks and the unit seam both come through here.
+static int attention_f32_dispatch(const float *qkv, int B, int L, int W, int heads, float *out, hipStream_t stream) {
+    const bool chunked = (size_t)L * 64 * 4 * 2 > 160 * 1024;
+    const size_t lds = chunked ? (size_t)ATF_CHUNK * 64 * 4 * 2 : (size_t)L * 64 * 4 * 2;
+    const int rc = chunked ? mpreid_dyn_lds(attention_f32_chunked_kernel, lds) : mpreid_dyn_lds(attention_f32_kernel, lds);
+    if (rc) return rc;
+    if (chunked)
+        hipLaunchKernelGGL(attention_f32_chunked_kernel, dim3((unsigned)(B * heads), (unsigned)((L + 255) / 256)), dim3(256), lds,
+                           stream, qkv, L, W, heads, out);
+    else
+        hipLaunchKernelGGL(attention_f32_kernel, dim3((unsigned)(B * heads)), dim3(256), lds, stream, qkv, L, W, heads, out);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
+extern "C" int mpreid_vit_attention_f32(const float *qkv, int B, int L, int W, int heads, float *out, mpreid_stream_t stream) {
+    ARG_CHECK(qkv && out && B > 0 && heads > 0);
+    ARG_CHECK(W == 64 * heads && L >= 2 && L <= MPREID_VIT_MAX_TOKENS);
+    ARG_CHECK(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 15) == 0);
+    return attention_f32_dispatch(qkv, B, L, W, heads, out, (hipStream_t)stream);
+}
+
 struct VitLayoutF32 {
     int L, P, M, Kp;
     size_t patches, x, a, qkv, hbuf, y_cls, total;
@@ -2173,11 +2196,6 @@ extern "C" int mpreid_vit_forward_f32(const mpreid_vit_cfg *cfg, const mpreid_vi
                            w->ln_pre_g, w->ln_pre_b, (void *)x, (int64_t)W);
         LAUNCH_CHECK();
     }
-    // K / V of a head resident in LDS where they fit (L <= 320), streamed in chunks above that
-    const bool att_chunked = (size_t)L * 64 * 4 * 2 > 160 * 1024;
-    const size_t att_lds = att_chunked ? (size_t)ATF_CHUNK * 64 * 4 * 2 : (size_t)L * 64 * 4 * 2;
-    if ((rc = att_chunked ? mpreid_dyn_lds(attention_f32_chunked_kernel, att_lds) : mpreid_dyn_lds(attention_f32_kernel, att_lds)))
-        return rc;
     for (int l = 0; l < cfg->layers; ++l) {
         const mpreid_vit_layer &ly = w->layers[l];
         hipLaunchKernelGGL(layernorm_kernel<0>, dim3((unsigned)((v.M + 3) / 4)), dim3(256), 0, stream, x, (int64_t)v.M, W,
@@ -2185,13 +2203,7 @@ extern "C" int mpreid_vit_forward_f32(const mpreid_vit_cfg *cfg, const mpreid_vi
         LAUNCH_CHECK();
         if ((rc = mpreid_gemm_f32_linear(a, (const float *)ly.in_proj_w, v.M, 3 * W, W, ly.in_proj_b, qkv, 3 * W, F32_LIN, stream)))
             return rc;
-        if (att_chunked)
-            hipLaunchKernelGGL(attention_f32_chunked_kernel, dim3((unsigned)(B * cfg->heads), (unsigned)((L + 255) / 256)), dim3(256),
-                               att_lds, stream, qkv, L, W, cfg->heads, a);
-        else
-            hipLaunchKernelGGL(attention_f32_kernel, dim3((unsigned)(B * cfg->heads)), dim3(256), att_lds, stream, qkv, L, W,
-                               cfg->heads, a);
-        LAUNCH_CHECK();
+        if ((rc = attention_f32_dispatch(qkv, B, L, W, cfg->heads, a, stream))) return rc;
         if ((rc = mpreid_gemm_f32_linear(a, (const float *)ly.out_proj_w, v.M, W, W, ly.out_proj_b, x, W, F32_LIN_RES, stream)))
             return rc;
         hipLaunchKernelGGL(layernorm_kernel<0>, dim3((unsigned)((v.M + 3) / 4)), dim3(256), 0, stream, x, (int64_t)v.M, W,

@@ -210,6 +210,7 @@ PROTOTYPES = {
     "mpreid_vit_attention": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "mpreid_vit_workspace_bytes_f32": (sz, [P(VitCfg), i32]),
     "mpreid_vit_forward_f32": (i32, [P(VitCfg), P(VitWeights), P(ImageIn), i32, vp, vp, vp, sz, vp]),
+    "mpreid_vit_attention_f32": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     # the MoE image encoder: the forward takes the MoE description behind the weights; then the unit seams
     "mpreid_vit_workspace_bytes_moe": (sz, [P(VitCfg), P(VitMoe), i32]),
     "mpreid_vit_forward_moe": (i32, [P(VitCfg), P(VitWeights), P(VitMoe), P(ImageIn), i32, vp, vp, vp, sz, vp]),

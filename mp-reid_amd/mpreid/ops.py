@@ -1082,6 +1082,21 @@ def vit_attention(qkv: torch.Tensor, batch: int, tokens: int, heads: int, q_tile
     return out
 
 
+def vit_attention_f32(qkv: torch.Tensor, batch: int, tokens: int, heads: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the attention step of the all-fp32 encoder mode alone (mpreid_vit_attention_f32): the resident / chunked rule of
+    mpreid_vit_forward_f32.  qkv: fp32 [batch * tokens, 3 * 64 * heads] in the column layout of vit_attention; out: fp32
+    [batch * tokens, width], allocated (uninitialised) when not passed; may be a view into a larger buffer."""
+    _lib.require_gpu()
+    width = 64 * heads
+    assert qkv.is_cuda and qkv.is_contiguous() and qkv.dtype == torch.float32 and tuple(qkv.shape) == (batch * tokens, 3 * width)
+    if out is None:
+        out = torch.empty((batch * tokens, width), dtype=torch.float32, device=qkv.device)
+    assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (batch * tokens, width)
+    _lib.check(_lib.load().mpreid_vit_attention_f32(_ptr(qkv), int(batch), int(tokens), width, int(heads), _ptr(out),
+                                                    _lib.stream_ptr()), "mpreid_vit_attention_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 # MoE unit seams (include/mpreid.h: mpreid_moe_route, mpreid_moe_mlp_split)
 # ----------------------------------------------------------------------------------------------

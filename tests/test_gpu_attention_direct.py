@@ -10,7 +10,8 @@ before the GPU is touched.
 
 Checks, per case: hi + lo of every written row against float64 softmax(q k^T / 8) v of the same fp32 inputs; `out` pre-filled with a
 NaN pattern, every row finite afterwards (q_tiles 1: rows 0 .. 15 finite, every other row untouched); guard rows before and after
-`out` untouched; the rows of image i equal, bit for bit, a B = 1 call on that image's slab.
+`out` untouched; a second identical call gives the same bits; the rows of image i equal, bit for bit, a B = 1 call on that image's
+slab (attention_direct_cases.checked_call, shared with test_gpu_attention_direct_forms.py).
 
 Bound: PARENT_MAX_ERR below is the largest slab-relative error (attention_direct_cases.error_figure) of the kernel as it stood
 before its LDS / addressing rework, per data kind, over all the shapes here, measured on an MI355X and recorded in
@@ -19,7 +20,6 @@ operations reproduces the bits, the factor only keeps the test from encoding one
 import ctypes as C
 
 import pytest
-import torch
 
 import attention_direct_cases as adc
 
@@ -33,8 +33,6 @@ PARENT_MAX_ERR = {
     "spike0": 8.007095706326771e-07,
     "magnitude": 7.38512629973661e-07,
 }
-GUARD_ROWS = 8
-NAN_BITS = 0x7E01   # an fp16 NaN
 
 
 def persistent_grid():
@@ -56,23 +54,8 @@ def batch_of(which, heads):
     return -(-(grid * 12 // 10) // heads)
 
 
-def _call(qkv, batch, heads, q_tiles):
-    """one launch into a NaN-filled buffer with guard rows -> fp16 [batch * L, 2 * width] (a view); the guards are checked"""
-    from mpreid import ops
-    width = 64 * heads
-    rows = batch * adc.L
-    buf = torch.empty((rows + 2 * GUARD_ROWS, 2 * width), dtype=torch.float16, device=qkv.device)
-    buf.view(torch.int16).fill_(NAN_BITS)
-    out = buf[GUARD_ROWS:GUARD_ROWS + rows]
-    ops.vit_attention(qkv, batch, adc.L, heads, q_tiles=q_tiles, out=out)
-    torch.cuda.synchronize()
-    bits = buf.view(torch.int16)
-    assert bool((bits[:GUARD_ROWS] == NAN_BITS).all()) and bool((bits[GUARD_ROWS + rows:] == NAN_BITS).all()), "guard rows written"
-    return out
-
-
 def measure(width, heads, batch, kind):
-    """every check of one case but the error bound -> {q_tiles: error figure}"""
+    """every check of one case but the error bound (attention_direct_cases.checked_call) -> {q_tiles: error figure}"""
     host = adc.make_qkv(width, heads, batch, kind)
     prem = adc.check_premises(host[:3 * adc.L], min(batch, 3), heads, kind)
     want = adc.attention_f64(host, batch, heads)
@@ -80,21 +63,8 @@ def measure(width, heads, batch, kind):
     qkv = host.cuda()
     errs = {}
     for q_tiles in (0, 1):
-        out = _call(qkv, batch, heads, q_tiles)
-        o3 = out.view(batch, adc.L, 2 * width)
-        written = adc.L if q_tiles == 0 else 16
-        assert bool(torch.isfinite(o3[:, :written]).all()), (kind, q_tiles, "a written row is not finite")
-        if q_tiles:
-            assert bool((o3[:, written:].view(torch.int16) == NAN_BITS).all()), (kind, q_tiles, "a row beyond the tile was written")
-        got = (o3[..., :width].double() + o3[..., width:].double()).cpu().view(batch, adc.L, heads, 64)
-        errs[q_tiles] = adc.error_figure(got, want, scale, rows=written)
-        # image i of the large call against a B = 1 call on its slab, bit for bit
-        if batch > 1:
-            single = torch.empty_like(o3)
-            for i in range(batch):
-                single[i] = _call(qkv[i * adc.L:(i + 1) * adc.L], 1, heads, q_tiles)
-            same = (single.view(torch.int16)[:, :written] == o3.view(torch.int16)[:, :written]).all(-1).all(-1)
-            assert bool(same.all()), (kind, q_tiles, "images that differ from their B = 1 call", (~same).nonzero()[:8].flatten().tolist())
+        got, _ = adc.checked_call(qkv, batch, adc.L, heads, q_tiles, tag=kind)
+        errs[q_tiles] = adc.error_figure(got, want, scale, rows=adc.written_rows(adc.L, q_tiles))
     print("ATTDIRECT width=%d heads=%d B=%d kind=%s err q_tiles0=%.3e q_tiles1=%.3e premises %s"
           % (width, heads, batch, kind, errs[0], errs[1], prem))
     return errs
