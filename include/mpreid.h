@@ -670,6 +670,55 @@ int mpreid_text_attention_backward(const float *qkv_dev, const float *d_o_dev, i
 int mpreid_layernorm_backward_f32(const float *x_dev, const float *dy_dev, const float *gamma_dev, int64_t rows, int width,
                                   int accumulate, float *dx_dev, mpreid_stream_t stream);
 
+/* ---- Stage-1 prompt learning (processor/processor_uniprompt_stage1.py:66-100): loss, context gradients, Adam ----
+ * Three small fp32 entry points around mpreid_text_forward / mpreid_text_backward.  No atomics and a fixed summation order: the
+ * same bits from run to run.  Every output element is written and no other byte; every argument error is found before anything
+ * is launched; stream-ordered, no host synchronisation.  Float buffers 4-byte aligned, labels / indices 8, the workspace 256.
+ *
+ * The symmetric supervised contrastive loss (loss/supcontrast.py at temperature 1, called twice, :90-93) and its gradients.
+ * S = img . txt^T [batch][batch], M_ab = (labels[a] == labels[b]), n_a = sum_b M_ab, P = softmax over the rows of S, Q = softmax
+ * over its columns:
+ *   loss[0] = loss_i2t = -(1/B) sum_a (1/n_a) sum_b M_ab log P_ab        loss[1] = loss_t2i = -(1/B) sum_b (1/n_b) sum_a M_ab log Q_ab
+ *   G_ab = -(1/B) ((M_ab / n_a - P_ab) + (M_ab / n_b - Q_ab))            d_txt = G^T . img        d_img = G . txt
+ * (d_txt, d_img: the gradients of loss[0] + loss[1]; either may be NULL and is then not computed -- the other outputs keep
+ * their bits.)  Stabilised with the row and the column maxima: log P_ab = (S_ab - max_a) - log sum_b exp(S_ab - max_a).
+ * Summation order: S_ab is ONE fmaf chain over the features, ascending.  A row's (column's) exp sum and its masked log-probability
+ * sum: lane l of one wave adds the entries l, l + 64, ... in ascending order, then the butterfly 32, 16, 8, 4, 2, 1.  A loss: thread
+ * t of 256 adds the row terms t, t + 256, ... ascending, butterfly per wave, then the four wave sums in order; divided by B last.
+ * A gradient element is one fmaf chain over the other side's rows, ascending.  batch == 1 gives losses and gradients of 0.0.
+ * Limits: 1 <= batch <= MPREID_SUPCON_MAX_BATCH (the two [B][B] logit matrices live in the workspace; above: MPREID_ERR_UNSUPPORTED),
+ * dim >= 1.  The labels are only compared with each other: any int64 values. */
+#define MPREID_SUPCON_MAX_BATCH 1024
+size_t mpreid_supcon_workspace_bytes(int batch, int dim);   /* needs no device; 0 for a bad request */
+int mpreid_supcon_pair_f32(const float *img_dev, const float *txt_dev /* both [batch][dim] */, const int64_t *labels_dev,
+                           int batch, int dim, float *loss_dev /* [2] */, float *d_txt_dev, float *d_img_dev /* [batch][dim] or NULL */,
+                           void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
+/* The same call with the gradients of ONE of the two losses, what a single SupConLoss call differentiates (the drop-in
+ * loss/supcontrast.py): directions = 1 keeps the row-softmax term of G (d loss[0]), 2 the column-softmax term (d loss[1]), 3 is
+ * mpreid_supcon_pair_f32 bit for bit.  Both losses are written whatever the directions. */
+int mpreid_supcon_f32(const float *img_dev, const float *txt_dev, const int64_t *labels_dev, int batch, int dim, int directions,
+                      float *loss_dev, float *d_txt_dev, float *d_img_dev, void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
+/* The gradient of a context tensor from the prompt gradient (what autograd's index backward does for ctx[idx]):
+ *   out[s][t][e] = sum over b ascending with idx[b] == s of src[b][tok0 + t][e],   s < n_seg, t < n_tok, e < width
+ * a sequential fp32 sum in batch order starting from 0.0; segments without a member are exactly 0.0.  src_dev [batch][tokens][width]
+ * (what mpreid_text_backward writes), idx_dev int64 [batch], out_dev [n_seg][n_tok][width].  0 <= tok0, tok0 + n_tok <= tokens;
+ * n_tok * width < 2^24.  LIMIT: the CONTENTS of idx_dev are device data and are NOT checked here: the caller validates them
+ * (mpreid.ops.rows_segment_sum does); a value outside 0 .. n_seg - 1 belongs to no segment and is never used as an address. */
+int mpreid_rows_segment_sum_f32(const float *src_dev, const int64_t *idx_dev, int batch, int tokens, int width, int tok0,
+                                int n_tok, int n_seg, float *out_dev, mpreid_stream_t stream);
+/* One step of torch.optim.Adam (decoupled == 0: L2 weight decay added to the gradient) or torch.optim.AdamW (decoupled != 0) on
+ * n fp32 elements, in place; step >= 1 is the number of this step, 0 <= beta < 1, eps > 0, lr and weight_decay >= 0 and finite.
+ * The host computes in double, from the float arguments, and rounds once to fp32: w1 = 1 - beta1, w2 = 1 - beta2,
+ * a = lr / (1 - beta1^step), r = sqrt(1 - beta2^step), lw = lr * weight_decay.  Per element, each line rounded once:
+ *   decoupled == 0: g = fmaf(weight_decay, p, grad)          decoupled != 0: p = fmaf(-lw, p, p), g = grad
+ *   m = fmaf(w1, g - m, m)        v = fmaf(w2, g * g, beta2 * v)        p = fmaf(-a, m / (sqrtf(v) / r + eps), p)
+ * (IEEE division and square root).  Groups of four elements go through 16-byte accesses when all four buffers are 16-byte
+ * aligned, the n % 4 elements behind them (all of them otherwise) one by one: the same arithmetic, the same bits.  grad_dev must
+ * not overlap the other three. */
+int mpreid_adam_step_f32(float *param_dev, const float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev, int64_t n, int step,
+                         float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled,
+                         mpreid_stream_t stream);
+
 /* processor/processor_uniprompt_stage2.py:636-640: out[rows][dim] = mean over the views of
  * feats[n_views][rows][dim] (sequential sum in view order, true division), then F.normalize(p=2, dim=1,
  * eps=1e-12) when normalize != 0. */

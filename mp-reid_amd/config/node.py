@@ -68,8 +68,20 @@ class CfgNode(dict):
             node[parts[-1]] = val
 
 
+def _stage1_defaults():
+    """SOLVER.STAGE1 / STAGE1A / STAGE1B of the reference (config/defaults.py:123-210: the three sections carry the same keys
+    and values).  The stage-1 loop reads IMS_PER_BATCH, MAX_EPOCHS, CHECKPOINT_PERIOD and LOG_PERIOD from STAGE1, the optimizer
+    and the schedule OPTIMIZER_NAME, BASE_LR, WEIGHT_DECAY, MOMENTUM, MAX_EPOCHS, LR_MIN, WARMUP_LR_INIT and WARMUP_EPOCHS from the
+    section of their stage; the other keys are accepted and unused, as in the reference."""
+    return {"IMS_PER_BATCH": 64, "OPTIMIZER_NAME": "Adam", "MAX_EPOCHS": 100, "BASE_LR": 3e-4, "MOMENTUM": 0.9,
+            "WEIGHT_DECAY": 0.0005, "WEIGHT_DECAY_BIAS": 0.0005, "WARMUP_FACTOR": 0.01, "WARMUP_EPOCHS": 5,
+            "WARMUP_LR_INIT": 0.01, "LR_MIN": 0.000016, "WARMUP_ITERS": 500, "WARMUP_METHOD": "linear", "COSINE_MARGIN": 0.5,
+            "COSINE_SCALE": 30, "CHECKPOINT_PERIOD": 10, "LOG_PERIOD": 100, "EVAL_PERIOD": 10}
+
+
 def make_defaults():
     return CfgNode({
+        "SOLVER": {"STAGE1": _stage1_defaults(), "STAGE1A": _stage1_defaults(), "STAGE1B": _stage1_defaults()},
         "MODEL": {"NAME": "ViT-B-16", "DEVICE": "cuda", "DEVICE_ID": "0", "STRIDE_SIZE": [16, 16],
                   "SIE_CAMERA": False, "SIE_VIEW": False, "SIE_COE": 3.0, "NECK": "bnneck", "COS_LAYER": False,
                   "DIST_TRAIN": False, "INIT_SEED": 7, "ENCODER_PRECISION": "split",

@@ -29,7 +29,10 @@ Prompt learning (reference processor/processor_uniprompt_stage1.py:44-100): ``en
 require grad.  While grad mode is on and the assembled prompts require grad, ``get_text`` runs
 ``TextEncoder.forward_grad``: the same features, as a node of torch's autograd graph whose backward is the library's
 prompt gradient (mpreid_text_backward; the tower's weights stay frozen), and autograd carries it through the prompt
-assembly to the context tensors.  ``prompt_learner.parameters()`` hands them to a ``torch.optim`` optimizer,
+assembly to the context tensors.  The stage-1 loop itself is ``processor/processor_uniprompt_stage1.py::do_train_stage1``
+with ``loss/supcontrast.py``, ``solver/make_optimizer_prompt.py`` and ``solver/scheduler_factory.py``; with their Adam / AdamW
+optimizer a step is one fused ``mpreid.ops.PromptTrainer.step`` (loss, context gradients and the update in HIP kernels, no
+autograd graph), and it writes the context tensors in place, so the next ``get_text`` call sees the new values.
 ``text_state_dict()`` gives the tower and prompt tensors under the reference's checkpoint keys.  The model stays in
 ``.eval()`` throughout (neither branch has a mode-dependent layer).  Otherwise -- no stage enabled, or under
 ``torch.no_grad()`` -- the call is the evaluation call, bit for bit.  ``load_param`` skips the checkpoint keys of modules this build
@@ -98,23 +101,35 @@ class PromptLearner:
         for k in PROMPT_KEYS:
             setattr(self, k, tensors[k].detach().to(device=device, dtype=torch.float32).contiguous())
 
-    def forward(self, label, view=None):
+    @staticmethod
+    def platform_index(view):
+        """0-5 cctv_rgb, 6-11 cctv_ir, 12 uav_rgb, 13 uav_ir: platform 1 iff view >= 12"""
+        return (view >= 12).long()
+
+    @staticmethod
+    def modality_index(view):
+        """modality 1 iff 6 <= view < 12 or view == 13"""
+        return (((view >= 6) & (view < 12)) | (view == 13)).long()
+
+    def forward(self, label, view=None, validate=True):
+        """validate=False skips the range check of `label` (it reads the labels back from the device): for a caller that has
+        checked them already (mpreid.ops.PromptTrainer, whose step must not wait for the device)"""
         dev = self.ctx_generic.device
         label = torch.as_tensor(label).to(dev).long()
         b = label.shape[0]
-        if b and (int(label.min()) < 0 or int(label.max()) >= self.ctx_generic.shape[0]):
+        if validate and b and (int(label.min()) < 0 or int(label.max()) >= self.ctx_generic.shape[0]):
             raise ValueError(f"label outside 0 .. {self.ctx_generic.shape[0] - 1}")
         generic_ctx = self.ctx_generic[label]
         if self.training_stage == '1a':
-            modal_ctx = torch.zeros(b, N_MODAL_CTX, CTX_DIM, device=dev, dtype=generic_ctx.dtype)
-            plat_ctx = torch.zeros(b, N_PLAT_CTX, CTX_DIM, device=dev, dtype=generic_ctx.dtype)
+            # (the context tensors' own shapes: [.., 4, 512] in the model, narrower in a reduced tower)
+            modal_ctx = torch.zeros(b, *self.ctx_modality.shape[1:], device=dev, dtype=generic_ctx.dtype)
+            plat_ctx = torch.zeros(b, *self.ctx_platform.shape[1:], device=dev, dtype=generic_ctx.dtype)
         elif view is not None:
-            # 0-5 cctv_rgb, 6-11 cctv_ir, 12 uav_rgb, 13 uav_ir: platform 1 iff view >= 12, modality 1 iff 6 <= view < 12 or 13
             view = torch.as_tensor(view).to(dev).long()
             if view.shape != label.shape:
                 raise ValueError(f"view: expected shape {tuple(label.shape)}, got {tuple(view.shape)}")
-            plat_ctx = self.ctx_platform[(view >= 12).long()]
-            modal_ctx = self.ctx_modality[(((view >= 6) & (view < 12)) | (view == 13)).long()]
+            plat_ctx = self.ctx_platform[self.platform_index(view)]
+            modal_ctx = self.ctx_modality[self.modality_index(view)]
         else:
             modal_ctx = self.ctx_modality.mean(dim=0, keepdim=True).expand(b, -1, -1)
             plat_ctx = self.ctx_platform.mean(dim=0, keepdim=True).expand(b, -1, -1)

@@ -64,6 +64,7 @@ class VitMoe(C.Structure):
 
 
 TEXT_MAX_TOKENS = 128   # MPREID_TEXT_MAX_TOKENS
+SUPCON_MAX_BATCH = 1024   # MPREID_SUPCON_MAX_BATCH
 
 
 class TextCfg(C.Structure):
@@ -227,6 +228,12 @@ PROTOTYPES = {
     "mpreid_text_backward": (i32, [P(TextCfg), P(TextWeights), P(TextWeightsT), vp, vp, vp, i32, vp, vp, sz, vp]),
     "mpreid_text_attention_backward": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "mpreid_layernorm_backward_f32": (i32, [vp, vp, vp, i64, i32, i32, vp, vp]),
+    # stage-1 prompt learning: the contrastive loss pair with its gradients, the context gradient, the Adam / AdamW step
+    "mpreid_supcon_workspace_bytes": (sz, [i32, i32]),
+    "mpreid_supcon_pair_f32": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "mpreid_supcon_f32": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "mpreid_rows_segment_sum_f32": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "mpreid_adam_step_f32": (i32, [vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, f32, i32, vp]),
     "mpreid_tta_mean_f32": (i32, [vp, i32, i64, i32, i32, vp, vp]),
     "mpreid_resize_workspace_bytes": (sz, [i32, i32, i32]),
     "mpreid_resize_bilinear_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),

@@ -1311,7 +1311,7 @@ class TextEncoder:
     def forward(self, prompts: torch.Tensor, eot, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """prompts [B, tokens, width] (the embedded prompts, positional embedding NOT added), eot [B] integer rows ->
         fp32 [B, out_dim] on the device; at most CHUNK prompts per library call, through one workspace"""
-        L = _lib.load()
+        _lib.load()
         n_tok, w, od = self.cfg["tokens"], self.cfg["width"], self.cfg["out_dim"]
         if prompts.dim() != 3 or tuple(prompts.shape[1:]) != (n_tok, w):
             raise ValueError(f"prompts: expected [B, {n_tok}, {w}], got {tuple(prompts.shape)}")
@@ -1321,14 +1321,21 @@ class TextEncoder:
         if out is None:
             out = torch.empty((B, od), dtype=torch.float32, device=self.device)
         assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, od)
+        return self._forward_into(x, e, out)
+
+    __call__ = forward
+
+    def _forward_into(self, x: torch.Tensor, e: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """forward's library calls on checked device tensors (x fp32 [B, tokens, width], e int32 [B], out fp32 [B, out_dim], all
+        contiguous): nothing is allocated beyond the cached workspace and nothing is copied from the host"""
+        L = _lib.load()
+        B = x.shape[0]
         for s in range(0, B, self.CHUNK):
             n = min(B, s + self.CHUNK) - s
             ws = _workspace(self.ws_tag, L.mpreid_text_workspace_bytes(C.byref(self.c_cfg), n), self.device)
             _lib.check(L.mpreid_text_forward(C.byref(self.c_cfg), C.byref(self.c_w), _ptr(x[s:]), _ptr(e[s:]), n, _ptr(out[s:]),
                                              _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_text_forward")
         return out
-
-    __call__ = forward
 
     def _transposed_weights(self):
         """mpreid_text_weights_t: fp32 [in][out] copies of the frozen matrices (~150 MB at CLIP's size), made once"""
@@ -1357,7 +1364,7 @@ class TextEncoder:
         """d loss / d prompts, fp32 [B, tokens, width], given grad_out = d loss / d forward(prompts, eot) [B, out_dim]; the
         tower's weights are frozen (mpreid_text_backward: it re-runs the forward itself, so no earlier forward call is needed).
         At most CHUNK prompts per library call, through one workspace (tag ws_tag + "_grad")."""
-        L = _lib.load()
+        _lib.load()
         n_tok, w, od = self.cfg["tokens"], self.cfg["width"], self.cfg["out_dim"]
         if prompts.dim() != 3 or tuple(prompts.shape[1:]) != (n_tok, w):
             raise ValueError(f"prompts: expected [B, {n_tok}, {w}], got {tuple(prompts.shape)}")
@@ -1366,8 +1373,13 @@ class TextEncoder:
             raise ValueError(f"grad_out: expected [{B}, {od}], got {tuple(grad_out.shape)}")
         e = torch.from_numpy(check_eot(eot, B, n_tok)).to(self.device)
         x, g = _dev_f32(prompts, self.device), _dev_f32(grad_out, self.device)
+        return self._backward_into(x, e, g, torch.empty((B, n_tok, w), dtype=torch.float32, device=self.device))
+
+    def _backward_into(self, x: torch.Tensor, e: torch.Tensor, g: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """backward's library calls on checked device tensors (as _forward_into; g fp32 [B, out_dim], out fp32 [B, tokens, width])"""
+        L = _lib.load()
+        B = x.shape[0]
         wt = self._transposed_weights()
-        out = torch.empty((B, n_tok, w), dtype=torch.float32, device=self.device)
         for s in range(0, B, self.CHUNK):
             n = min(B, s + self.CHUNK) - s
             ws = _workspace(self.ws_tag + "_grad", L.mpreid_text_backward_workspace_bytes(C.byref(self.c_cfg), n), self.device)
@@ -1408,6 +1420,230 @@ class _TextForwardGrad(torch.autograd.Function):
         (prompts,) = ctx.saved_tensors
         grad = ctx.enc.backward(prompts, ctx.eot, grad_out)
         return grad.to(device=prompts.device, dtype=prompts.dtype), None, None
+
+
+# ----------------------------------------------------------------------------------------------
+# Stage-1 prompt learning (include/mpreid.h: mpreid_supcon_pair_f32, mpreid_rows_segment_sum_f32, mpreid_adam_step_f32)
+# ----------------------------------------------------------------------------------------------
+def _f32_buffer(t: Optional[torch.Tensor], shape, device, what: str) -> torch.Tensor:
+    """an output buffer: allocated (uninitialised) when not passed, else checked; it may be a view into a larger buffer"""
+    if t is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), what
+    return t
+
+
+def supcon_pair(img: torch.Tensor, txt: torch.Tensor, labels: torch.Tensor, need_d_img: bool = False, directions: int = 3,
+                loss: Optional[torch.Tensor] = None, d_txt: Optional[torch.Tensor] = None, d_img: Optional[torch.Tensor] = None):
+    """The symmetric supervised contrastive loss of stage 1 and its gradients (mpreid_supcon_pair_f32): img, txt fp32
+    [B, dim], labels int64 [B] -> (loss [2] = loss_i2t, loss_t2i; d_txt [B, dim][; d_img [B, dim] with need_d_img]), the gradients
+    of loss_i2t + loss_t2i, all on the device, nothing synchronised.  directions = 1 / 2: the gradients of loss_i2t / loss_t2i
+    alone (mpreid_supcon_f32).  1 <= B <= SUPCON_MAX_BATCH.  The output buffers may be passed (the trainer's persistent ones)."""
+    dev = _lib.require_gpu()
+    L = _lib.load()
+    img, txt = _dev_f32(img, dev), _dev_f32(txt, dev)
+    if img.dim() != 2 or txt.shape != img.shape:
+        raise ValueError(f"supcon_pair: img and txt must be [B, dim] of one shape, got {tuple(img.shape)} and {tuple(txt.shape)}")
+    B, D = img.shape
+    labels = _dev_i64(labels, dev)
+    if tuple(labels.shape) != (B,):
+        raise ValueError(f"supcon_pair: labels must be [{B}], got {tuple(labels.shape)}")
+    if B < 1 or D < 1:
+        raise ValueError("supcon_pair: an empty batch has no loss")
+    loss = _f32_buffer(loss, (2,), dev, "loss")
+    d_txt = _f32_buffer(d_txt, (B, D), dev, "d_txt")
+    d_img = _f32_buffer(d_img, (B, D), dev, "d_img") if need_d_img else None
+    ws = _workspace("supcon", L.mpreid_supcon_workspace_bytes(B, D), dev)
+    _lib.check(L.mpreid_supcon_f32(_ptr(img), _ptr(txt), _ptr(labels), B, D, int(directions), _ptr(loss), _ptr(d_txt), _ptr(d_img),
+                                   _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_supcon_pair_f32")
+    return (loss, d_txt, d_img) if need_d_img else (loss, d_txt)
+
+
+def check_segment_index(idx, batch: int, n_seg: int) -> None:
+    """host-side validation of a segment index (the library does not look at its contents): integers in 0 .. n_seg - 1"""
+    i = idx.detach().cpu().numpy() if torch.is_tensor(idx) else np.asarray(idx)
+    if i.shape != (batch,) or i.dtype == np.bool_ or not np.issubdtype(i.dtype, np.integer):
+        raise ValueError(f"idx: expected {batch} integers, got shape {i.shape} of {i.dtype}")
+    if batch and (int(i.min()) < 0 or int(i.max()) >= n_seg):
+        raise ValueError(f"idx: values must lie in 0 .. {n_seg - 1}, got {int(i.min())} .. {int(i.max())}")
+
+
+def rows_segment_sum(src: torch.Tensor, idx: torch.Tensor, tok0: int, n_tok: int, n_seg: int,
+                     out: Optional[torch.Tensor] = None, validate: bool = True) -> torch.Tensor:
+    """out[s, t, e] = sum over b ascending with idx[b] == s of src[b, tok0 + t, e] (mpreid_rows_segment_sum_f32): the gradient of
+    a context tensor ctx[idx] that fills the rows tok0 .. tok0 + n_tok - 1 of the prompts, from the prompt gradient src fp32
+    [B, tokens, width]; a sequential fp32 sum in batch order, bit-reproducible.  idx int64 [B] -> fp32 [n_seg, n_tok, width].
+    validate=False skips the host-side range check of idx (it reads the indices back from the device)."""
+    dev = _lib.require_gpu()
+    assert src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 3
+    B, tokens, width = src.shape
+    if validate:
+        check_segment_index(idx, B, n_seg)
+    idx = _dev_i64(idx, dev)
+    if not (0 <= tok0 and 1 <= n_tok and tok0 + n_tok <= tokens):
+        raise ValueError(f"rows_segment_sum: the window {tok0} .. {tok0 + n_tok - 1} does not lie in 0 .. {tokens - 1}")
+    out = _f32_buffer(out, (n_seg, n_tok, width), dev, "out")
+    _lib.check(_lib.load().mpreid_rows_segment_sum_f32(_ptr(src), _ptr(idx), B, tokens, width, int(tok0), int(n_tok), int(n_seg),
+                                                       _ptr(out), _lib.stream_ptr()), "mpreid_rows_segment_sum_f32")
+    return out
+
+
+def adam_step(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: int, lr: float,
+              betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, decoupled: bool = False) -> None:
+    """one step of torch.optim.Adam (decoupled False: weight decay added to the gradient) or AdamW (True) on fp32 device
+    tensors of one size, in place (mpreid_adam_step_f32: the arithmetic order is in include/mpreid.h); step >= 1"""
+    _lib.require_gpu()
+    n = param.numel()
+    for t in (param, grad, exp_avg, exp_avg_sq):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    _lib.check(_lib.load().mpreid_adam_step_f32(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), n, int(step), float(lr),
+                                                float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(bool(decoupled)),
+                                                _lib.stream_ptr()), "mpreid_adam_step_f32")
+
+
+class PromptAdam:
+    """torch.optim.Adam / AdamW over fp32 device tensors whose step is adam_step: zero_grad, step, param_groups and state_dict as
+    torch's optimizers have them (one group per entry of `params`: a tensor, or a dict with "params" and its own lr /
+    weight_decay, the form solver/make_optimizer_prompt.py builds).  step() updates every parameter that has a .grad (the
+    autograd path); update(p, grad) is the same step on a gradient held elsewhere (PromptTrainer's buffers).  No amsgrad."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 decoupled: bool = False):
+        self.decoupled = bool(decoupled)
+        self.defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+        self.param_groups = []
+        for g in params:
+            g = dict(g) if isinstance(g, dict) else {"params": [g]}
+            g["params"] = [g["params"]] if torch.is_tensor(g["params"]) else list(g["params"])
+            for k, v in self.defaults.items():
+                g.setdefault(k, v)
+            self.param_groups.append(g)
+        for p in self._params():
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                raise ValueError("PromptAdam: parameters are contiguous fp32 tensors on the device")
+        self.state = {}
+
+    def _params(self):
+        return [p for g in self.param_groups for p in g["params"]]
+
+    def _group_of(self, p):
+        for g in self.param_groups:
+            if any(q is p for q in g["params"]):
+                return g
+        raise KeyError("PromptAdam: not a parameter of this optimizer")
+
+    def zero_grad(self, set_to_none: bool = True):
+        for p in self._params():
+            if p.grad is not None:
+                if set_to_none:
+                    p.grad = None
+                else:
+                    p.grad.zero_()
+
+    @torch.no_grad()
+    def update(self, p: torch.Tensor, grad: torch.Tensor, lr: Optional[float] = None):
+        g = self._group_of(p)
+        st = self.state.get(id(p))
+        if st is None:
+            st = self.state[id(p)] = {"step": 0, "exp_avg": torch.zeros_like(p), "exp_avg_sq": torch.zeros_like(p)}
+        st["step"] += 1
+        adam_step(p.detach(), grad, st["exp_avg"], st["exp_avg_sq"], st["step"], g["lr"] if lr is None else lr, g["betas"], g["eps"],
+                  g["weight_decay"], self.decoupled)
+
+    def step(self):
+        for p in self._params():
+            if p.grad is not None:
+                self.update(p, _dev_f32(p.grad, p.device))
+
+    def state_dict(self):
+        order = {id(p): i for i, p in enumerate(self._params())}
+        groups = [dict({k: v for k, v in g.items() if k != "params"}, params=[order[id(p)] for p in g["params"]])
+                  for g in self.param_groups]
+        return {"state": {order[k]: {"step": v["step"], "exp_avg": v["exp_avg"].clone(), "exp_avg_sq": v["exp_avg_sq"].clone()}
+                          for k, v in self.state.items()}, "param_groups": groups, "decoupled": self.decoupled}
+
+
+class PromptTrainer:
+    """One fused stage-1 step on the device (reference processor/processor_uniprompt_stage1.py:74-98 without autograd): assemble
+    the prompts (PromptLearner.forward), TextEncoder forward, supcon_pair against the fixed image features, TextEncoder backward,
+    rows_segment_sum into a persistent gradient buffer per trained context tensor, adam_step on those tensors in place -- the
+    next get_text call of the model sees the new values.  stage '1a' trains ctx_generic, '1b' ctx_modality and ctx_platform (it
+    needs the views: the index of each prompt's context rows).  `optimizer`: a PromptAdam over the trained tensors (made from
+    the keyword settings when not given); its param_groups carry the learning rate a scheduler sets.  `eot`: the read-out row of
+    the prompts, an integer or a function batch -> rows.  Not reproduced from the reference: autocast and GradScaler -- the
+    text features and their gradient are fp32-grade and the backward never passes through fp16, so there is nothing to scale.
+    After the first step of a batch size nothing is allocated but what torch's prompt assembly takes from its cached blocks."""
+
+    WINDOWS = {"ctx_generic": (1, 8), "ctx_modality": (9, 4), "ctx_platform": (13, 4)}   # first prompt row, rows
+
+    def __init__(self, text_encoder: "TextEncoder", prompt_learner, stage: str, optimizer: Optional[PromptAdam] = None, eot=19,
+                 lr: float = 3e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 5e-4, decoupled: bool = False):
+        if stage not in ("1a", "1b"):
+            raise ValueError(f"PromptTrainer: stage must be '1a' or '1b', got {stage!r}")
+        self.enc, self.pl, self.stage, self.eot = text_encoder, prompt_learner, stage, eot
+        self.names = ("ctx_generic",) if stage == "1a" else ("ctx_modality", "ctx_platform")
+        n_tok, w = self.enc.cfg["tokens"], self.enc.cfg["width"]
+        for name in ("ctx_generic", "ctx_modality", "ctx_platform"):
+            t, (tok0, rows) = getattr(prompt_learner, name), self.WINDOWS[name]
+            if t.dim() != 3 or tuple(t.shape[1:]) != (rows, w) or tok0 + rows > n_tok:
+                raise ValueError(f"PromptTrainer: {name} {tuple(t.shape)} does not fill rows {tok0} .. {tok0 + rows - 1} of "
+                                 f"[{n_tok}, {w}] prompts")
+        trained = [getattr(prompt_learner, k) for k in self.names]
+        self.optimizer = optimizer or PromptAdam(trained, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled=decoupled)
+        for t in trained:
+            self.optimizer._group_of(t)
+        self.grads = {k: torch.zeros_like(getattr(prompt_learner, k).detach()) for k in self.names}
+        self._bufs = {}
+
+    def _buffers(self, B: int):
+        b = self._bufs.get(B)
+        if b is None:
+            dev, c = self.enc.device, self.enc.cfg
+            rows = self.eot(B) if callable(self.eot) else np.full(B, int(self.eot), dtype=np.int64)
+            b = self._bufs[B] = dict(
+                eot=torch.from_numpy(check_eot(rows, B, c["tokens"])).to(dev),
+                feats=torch.empty((B, c["out_dim"]), dtype=torch.float32, device=dev),
+                d_txt=torch.empty((B, c["out_dim"]), dtype=torch.float32, device=dev),
+                d_prompts=torch.empty((B, c["tokens"], c["width"]), dtype=torch.float32, device=dev),
+                loss=torch.empty(2, dtype=torch.float32, device=dev))
+        return b
+
+    @torch.no_grad()
+    def step(self, img_feat: torch.Tensor, labels: torch.Tensor, views: Optional[torch.Tensor] = None, lr: Optional[float] = None,
+             validate: bool = False) -> torch.Tensor:
+        """img_feat fp32 [B, out_dim], labels int64 [B] (and views [B] in stage 1b), all on the device -> the two losses of the
+        batch BEFORE the update, a device tensor [2] that the next step of this batch size overwrites.  Nothing is synchronised.
+        The labels index ctx_generic on the device: validate=True checks them (and the views) on the host first, which waits
+        for the device; do_train_stage1 checks its whole label set once instead."""
+        dev = self.enc.device
+        if not (torch.is_tensor(img_feat) and img_feat.is_cuda and torch.is_tensor(labels) and labels.is_cuda):
+            raise ValueError("PromptTrainer.step: img_feat and labels are device tensors")
+        B = labels.shape[0]
+        if self.pl.training_stage != self.stage:
+            raise ValueError(f"PromptTrainer.step: the prompt learner assembles stage {self.pl.training_stage!r} prompts, the "
+                             f"trainer was built for stage {self.stage!r}")
+        if self.stage == "1b" and views is None:
+            raise ValueError("PromptTrainer.step: stage 1b needs the views (the rows of ctx_modality / ctx_platform per prompt)")
+        if tuple(img_feat.shape) != (B, self.enc.cfg["out_dim"]):
+            raise ValueError(f"img_feat: expected [{B}, {self.enc.cfg['out_dim']}], got {tuple(img_feat.shape)}")
+        labels = _dev_i64(labels, dev)
+        prompts = self.pl.forward(labels, view=views if self.stage == "1b" else None, validate=validate)
+        prompts = prompts.detach().to(dtype=torch.float32).contiguous()
+        b = self._buffers(B)
+        self.enc._forward_into(prompts, b["eot"], b["feats"])
+        supcon_pair(img_feat, b["feats"], labels, loss=b["loss"], d_txt=b["d_txt"])
+        self.enc._backward_into(prompts, b["eot"], b["d_txt"], b["d_prompts"])
+        if self.stage == "1a":
+            index = {"ctx_generic": labels}
+        else:
+            v = _dev_i64(views, dev)
+            index = {"ctx_modality": self.pl.modality_index(v), "ctx_platform": self.pl.platform_index(v)}
+        for name in self.names:
+            p = getattr(self.pl, name)
+            tok0, rows = self.WINDOWS[name]
+            rows_segment_sum(b["d_prompts"], index[name], tok0, rows, p.shape[0], out=self.grads[name], validate=False)
+            self.optimizer.update(p, self.grads[name], lr=lr)
+        return b["loss"]
 
 
 def _np_getter(state_dict):
