@@ -16,6 +16,7 @@
 #include "common.h"
 #include "conv_f16.h"
 #include "gemm_f16.h"
+#include "image_in.h"
 
 namespace {
 
@@ -25,10 +26,9 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 // one thread per output pixel: 27 inputs (coalesced along the image row), all cout <= 32 channels from weights in
 // LDS (broadcast float4 reads), 128 contiguous bytes out (channels cout..63 are the zero padding of the storage)
 template <bool U8>
-__global__ __launch_bounds__(256) void rn50_stem1_kernel(const float *__restrict__ img, const unsigned char *__restrict__ img8,
-                                                         float m0, float m1, float m2, float s0, float s1, float s2,
-                                                         const float *__restrict__ w, const float *__restrict__ bias,
-                                                         int cout, int B, int H, int W, _Float16 *__restrict__ out) {
+__global__ __launch_bounds__(256) void rn50_stem1_kernel(const mpreid_image_in in, const float *__restrict__ w,
+                                                         const float *__restrict__ bias, int cout, int B, int H, int W,
+                                                         _Float16 *__restrict__ out) {
     __shared__ __attribute__((aligned(16))) float sw[27 * 32 + 32]; // [k = c*9 + kh*3 + kw][n], then bias[n]
     for (int i = threadIdx.x; i < 27 * 32; i += 256) {
         const int k = i >> 5, n = i & 31;
@@ -48,16 +48,8 @@ __global__ __launch_bounds__(256) void rn50_stem1_kernel(const float *__restrict
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
                 const int iy = oy * 2 + kh - 1, ix = ox * 2 + kw - 1;
-                float v = 0.f;
-                if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
-                    if (U8) {
-                        const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
-                        v = __fdiv_rn(__fdiv_rn((float)img8[(((int64_t)b * H + iy) * W + ix) * 3 + c], 255.0f) - mean, sd);
-                    } else {
-                        v = img[(((int64_t)b * 3 + c) * H + iy) * W + ix];
-                    }
-                }
-                x[c * 9 + kh * 3 + kw] = v;
+                const bool inside = iy >= 0 && iy < H && ix >= 0 && ix < W;
+                x[c * 9 + kh * 3 + kw] = inside ? image_px_raw<U8 ? IMAGE_SRC_U8 : IMAGE_SRC_F32>(in, b, c, iy, ix, H, W) : 0.f;
             }
     _Float16 *o = out + pix * 64;
 #pragma unroll
@@ -501,10 +493,9 @@ extern "C" int mpreid_rn50_forward(const mpreid_rn50_cfg *cfg, const mpreid_rn50
     {
         const int64_t threads = (int64_t)B * H * W;   // one per output pixel
         const dim3 grid((unsigned)((threads + 255) / 256));
-#define MPREID_STEM1(U8)   /* (`in` holds NULL for the absent form and mean 0 / std 1 with fp32 input) */                 \
-        hipLaunchKernelGGL(rn50_stem1_kernel<U8>, grid, dim3(256), 0, stream, in.f32_dev, in.u8_hwc_dev, in.mean[0],       \
-                           in.mean[1], in.mean[2], in.std[0], in.std[1], in.std[2], w->stem1_w, w->stem1_b, cfg->width / 2, \
-                           B, cfg->img_h, cfg->img_w, buf[0])
+#define MPREID_STEM1(U8)                                                                                                  \
+        hipLaunchKernelGGL(rn50_stem1_kernel<U8>, grid, dim3(256), 0, stream, in, w->stem1_w, w->stem1_b, cfg->width / 2, B, \
+                           cfg->img_h, cfg->img_w, buf[0])
         if (in.u8_hwc_dev) MPREID_STEM1(true);
         else MPREID_STEM1(false);
 #undef MPREID_STEM1

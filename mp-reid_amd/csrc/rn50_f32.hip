@@ -15,27 +15,13 @@
 #include "common.h"
 #include "conv_f16.h"   // ... and its 3x3 convolutions as implicit GEMMs over fp16 pairs
 #include "gemm_f16.h"   // the split-precision tower (below) runs its layer1-4 convolutions on the fp16 matrix cores
+#include "image_in.h"   // the stems read the image batch through it: ToTensor + Normalize of uint8 input, the views
 
 int mpreid_gemm_f32_linear(const float *A, const float *Wt, int64_t M, int64_t N, int K, const float *bias, float *C,
                            int64_t ldc, int epi, hipStream_t stream);
 enum { F32_LIN = 2, F32_LIN_RES = 4, F32_LIN_RELU = 5, F32_LIN_RES_RELU = 6 };   // distance.hip: EPI_LIN*
 
 namespace {
-
-// The stem's input is the image batch of include/mpreid.h (mpreid_image_in, as mpreid_check_image_in returns it): ToTensor +
-// Normalize of uint8 input and the test-time-augmentation view are applied while the pixels are read.
-__device__ __forceinline__ float stem_px_raw(const mpreid_image_in &in, int b, int c, int iy, int ix, int H, int W) {
-    if (in.u8_hwc_dev)
-        return __fdiv_rn(__fdiv_rn((float)in.u8_hwc_dev[(((int64_t)b * H + iy) * W + ix) * 3 + c], 255.0f) - in.mean[c], in.std[c]);
-    return in.f32_dev[(((int64_t)b * 3 + c) * H + iy) * W + ix];
-}
-__device__ __forceinline__ float stem_px(const mpreid_image_in &in, int b, int c, int iy, int ix, int H, int W) {
-    if (in.view == 0) return stem_px_raw(in, b, c, iy, ix, H, W);
-    const int x = in.view == 1 ? W - 1 - ix : ix;
-    if (in.view == 2)
-        return __fdiv_rn((stem_px_raw(in, b, 0, iy, x, H, W) + stem_px_raw(in, b, 1, iy, x, H, W)) + stem_px_raw(in, b, 2, iy, x, H, W), 3.0f);
-    return stem_px_raw(in, b, in.view == 3 ? 0 : c, iy, x, H, W);
-}
 
 // stem conv1 + bn1 + relu: [B][3][H][W] fp32 -> [B][H/2][W/2][cout] fp32 (stride 2, pad 1); w [cout][c][kh][kw] folded
 __global__ __launch_bounds__(256) void stem1_f32_kernel(const mpreid_image_in img, const float *__restrict__ w,
@@ -52,7 +38,7 @@ __global__ __launch_bounds__(256) void stem1_f32_kernel(const mpreid_image_in im
         for (int kh = 0; kh < 3; ++kh)
             for (int kw = 0; kw < 3; ++kw) {
                 const int iy = oy * 2 + kh - 1, ix = ox * 2 + kw - 1;
-                const float x = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? stem_px(img, b, c, iy, ix, H, W) : 0.0f;
+                const float x = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? image_px(img, img.view, b, c, iy, ix, H, W) : 0.0f;
                 acc = fmaf(x, w[n * 27 + c * 9 + kh * 3 + kw], acc);
             }
     const float v = acc + bias[n];
@@ -90,7 +76,7 @@ __global__ __launch_bounds__(256) void stem1_px_kernel(const mpreid_image_in img
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
                 const int iy = oy * 2 + kh - 1, ix = ox * 2 + kw - 1;
-                xin[c * 9 + kh * 3 + kw] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? stem_px(img, b, c, iy, ix, H, W) : 0.0f;
+                xin[c * 9 + kh * 3 + kw] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? image_px(img, img.view, b, c, iy, ix, H, W) : 0.0f;
             }
 #pragma unroll
     for (int t = 0; t < 27; ++t) {   // t = c * 9 + kh * 3 + kw: the accumulation order of the reference chain

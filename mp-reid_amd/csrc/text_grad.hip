@@ -1,9 +1,9 @@
 // text_grad.hip — mpreid_text_backward: the gradient of the text features with respect to the prompts, every tower weight
-// frozen (include/mpreid.h).  The call re-runs the forward's own blocks (csrc/vit.hip through text_tower.h), keeps each
+// frozen (include/mpreid.h).  The call re-runs the forward's own blocks (csrc/vit.hip through towers.h), keeps each
 // block's input, and walks the layers back: per layer it recomputes q | k | v, the block's mid-point and the FC1
 // pre-activation with the forward's launchers, and propagates the gradient with the exact fp32 GEMM over transposed fp32
 // weights (dX = dY . W) and the fp32 kernels below.  No weight gradient, no atomics: the same bits from run to run.
-#include "text_tower.h"
+#include "towers.h"
 
 namespace {
 
@@ -210,7 +210,7 @@ __device__ __forceinline__ float block_sum(float v, float *red) {
 
 // The head, backwards, for prompt b = blockIdx.x: dy = grad_out[b] @ text_projection^T (proj_t: [out_dim][W]), ln_final's
 // input gradient at the read-out row, written to row eot[b] of dx; every other row of the prompt is set to zero.  The row
-// index is clamped into the prompt as in the forward (text_eot_ln_kernel).
+// index is clamped into the prompt as in the forward (head_ln_kernel, csrc/vit.hip).
 __global__ __launch_bounds__(256) void text_head_backward_kernel(const float *__restrict__ x, const int32_t *__restrict__ eot,
                                                                  const float *__restrict__ grad_out, int L, int W, int out_dim,
                                                                  const float *__restrict__ proj_t, const float *__restrict__ g,
@@ -374,18 +374,18 @@ extern "C" int mpreid_text_backward(const mpreid_text_cfg *cfg, const mpreid_tex
         HIP_TRY(hipMemcpyAsync(x, xl, xbytes, hipMemcpyDeviceToDevice, stream));
         if ((rc = text_block_recompute(cfg, B, ly, x, a, qkv, u, M, Mpad, stream))) return rc;   // x = x_mid from here on
         // x_{l+1} = x_mid + c_proj(quickgelu(c_fc(ln_2(x_mid))))
-        if ((rc = mpreid_gemm_f32_linear(dx, lt.proj_t, M, 4 * W, W, nullptr, dh, 4 * W, TEXT_F32_LIN, stream))) return rc;
+        if ((rc = mpreid_gemm_f32_linear(dx, lt.proj_t, M, 4 * W, W, nullptr, dh, 4 * W, F32_LIN, stream))) return rc;
         {
             const int64_t n4 = (int64_t)M * W;   // M * 4W / 4
             hipLaunchKernelGGL(quickgelu_backward_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, u, dh, n4);
             LAUNCH_CHECK();
         }
-        if ((rc = mpreid_gemm_f32_linear(dh, lt.fc_t, M, W, 4 * W, nullptr, t, W, TEXT_F32_LIN, stream))) return rc;
+        if ((rc = mpreid_gemm_f32_linear(dh, lt.fc_t, M, W, 4 * W, nullptr, t, W, F32_LIN, stream))) return rc;
         if ((rc = launch_layernorm_backward(x, t, ly.ln2_g, M, W, true, dx, stream))) return rc;   // dx = d/dx_mid
         // x_mid = x_l + out_proj(attention(in_proj(ln_1(x_l))))
-        if ((rc = mpreid_gemm_f32_linear(dx, lt.out_proj_t, M, W, W, nullptr, t, W, TEXT_F32_LIN, stream))) return rc;
+        if ((rc = mpreid_gemm_f32_linear(dx, lt.out_proj_t, M, W, W, nullptr, t, W, F32_LIN, stream))) return rc;
         if ((rc = launch_attention_backward(qkv, t, B, L, W, cfg->heads, dqkv, stream))) return rc;
-        if ((rc = mpreid_gemm_f32_linear(dqkv, lt.in_proj_t, M, W, 3 * W, nullptr, t, W, TEXT_F32_LIN, stream))) return rc;
+        if ((rc = mpreid_gemm_f32_linear(dqkv, lt.in_proj_t, M, W, 3 * W, nullptr, t, W, F32_LIN, stream))) return rc;
         if ((rc = launch_layernorm_backward(xl, t, ly.ln1_g, M, W, true, dx, stream))) return rc;   // dx = d/dx_l
     }
     // the positional embedding is an added constant: d/dprompts = d/dx_0

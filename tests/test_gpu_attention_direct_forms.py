@@ -1,6 +1,6 @@
 """Every attention kernel form called directly through its seam, every written row against float64.
 
-csrc/vit.hip holds fifteen attention kernels behind three dispatchers (the table of test_gpu_attention_forms.py): six fp16 forms
+csrc/attention.hip holds fifteen attention kernels behind three dispatchers (the table of test_gpu_attention_forms.py): six fp16 forms
 and five split forms with K / V resident in LDS, the streaming kernel above 256 tokens in both operand types, and the two all-fp32
 kernels (resident up to 320 tokens, 128-key chunks above).  test_gpu_attention_direct.py does this for one of them,
 attention_split_kernel<8,4,XKEY> at L = 129; here are all of them, through ops.vit_attention (fp16 input: the fp16 mode, fp32

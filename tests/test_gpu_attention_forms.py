@@ -1,5 +1,5 @@
 """GPU tests of every attention kernel form below 257 tokens.  The encoder picks its attention kernel from the token count L
-(attention_dispatch / attention_split_dispatch in csrc/vit.hip), keyed on kt = ceil(L / 16):
+(attention_dispatch / attention_split_dispatch in csrc/attention.hip), keyed on kt = ceil(L / 16):
 
     fp16   attention_kernel<2,2,EXACT> L 2..32 | <10,4,MASKALL> 33..128 | <10,4,EXACT> 129..160 | <14,8,MASKALL> 161..192 |
            <14,8,EXACT> 193..224 | <16,8,EXACT> 225..256

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-device A/B of the headline step (processor.do_inference over the Market-1501 shape): the product library against
 # another build of it (default: tools/ablation_lib/libmpreid_hip_base.so = the current tree with the previous round's
-# vit.hip / gemm_f16.hip / common.h, built by
+# vit.hip / attention.hip / gemm_f16.hip / common.h, built by
 #   MPREID_CSRC=<scratch csrc> MPREID_BUILD_TAG=base python mp-reid_amd/mpreid/build.py),
 # alternating processes on ONE device in ONE job: devices of the pool differ by 2-3 % in the clock they hold.
 #   bash tools/ab_encoder.sh [other.so] [rounds] [steps]

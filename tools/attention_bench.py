@@ -6,7 +6,7 @@ attention_split_kernel<8,4,XKEY>), alone: mpreid_vit_attention on a seeded q | k
     python tools/attention_bench.py [tag]
 
 With a timing-ablation build (MPREID_ABLATION=1 python mp-reid_amd/mpreid/build.py; MPREID_LIB=tools/ablation_lib/...
-MPREID_ALLOW_ABLATION=1) MPREID_ATT_DBG selects what the kernel leaves out (csrc/vit.hip); the switch is latched per process, so
+MPREID_ALLOW_ABLATION=1) MPREID_ATT_DBG selects what the kernel leaves out (csrc/attention.hip); the switch is latched per process, so
 one process per value.  profiles/attention_split_ablation.log holds such a table."""
 import os
 import sys

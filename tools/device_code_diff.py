@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Prove that a host-only change left the device code alone -- no GPU needed.
 
-    python tools/device_code_diff.py OLD_CSRC NEW_CSRC [--jobs N] [--keep DIR]
+    python tools/device_code_diff.py OLD_CSRC NEW_CSRC [--pool] [--jobs N] [--keep DIR]
 
 Every .hip of build.py's SOURCES is compiled for the device only from both source trees, with build.py's own FLAGS and
 EXTRA_FLAGS (imported, so MPREID_ABLATION=1 in the environment selects the ablation flag set exactly as it does for the
@@ -10,6 +10,8 @@ build).  Compared, keyed by symbol name:
   * each kernel's entry in the AMDGPU metadata note: register counts, LDS, scratch, kernarg size, workgroup size.
 Whole files are NOT compared: two device objects of identical kernels differ in their hashes (the source path is in
 there), and moving a launch into a helper may reorder implicit template instantiations -- reported, not an error.
+Files are compared one by one; --pool compares one table per tree instead, the union of all its files, for a change that
+moves kernels between files (each move is listed; a kernel that left one file for another is neither removed nor added).
 
 Each CSRC directory must sit where its `../../include` resolves (a checkout of the parent commit, e.g. from
 `git worktree add DIR HEAD`, gives DIR/mp-reid_amd/csrc).  Exit status 1 if a symbol was added, removed or differs.
@@ -97,21 +99,30 @@ def main():
     ap.add_argument("new_csrc")
     ap.add_argument("--jobs", type=int, default=4)
     ap.add_argument("--keep", help="keep the device objects in this directory")
+    ap.add_argument("--pool", action="store_true",
+                    help="compare by symbol over ALL files of each tree (a kernel that moved to another file is compared there)")
     args = ap.parse_args()
     b = load_build()
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     readelf = os.environ.get("LLVM_READELF", "/opt/rocm/lib/llvm/bin/llvm-readelf")
     work = args.keep or tempfile.mkdtemp(prefix="device_code_diff_")
-    sources = [s for s in b.SOURCES if s.endswith(".hip")]
-    # a source the old tree does not have yet is a NEW file: named, not compared (its kernels cannot change an old one)
-    new_files = [s for s in sources if not os.path.exists(os.path.join(args.old_csrc, s))]
-    sources = [s for s in sources if s not in new_files]
-    for s in new_files:
-        print("%-16s only in the new tree: not compared" % s, flush=True)
+    hips = [s for s in b.SOURCES if s.endswith(".hip")]
+    new_files = [s for s in hips if not os.path.exists(os.path.join(args.old_csrc, s))]
+    if args.pool:
+        # every file of each tree: a kernel is compared wherever it lives now
+        sources = {"old": [s for s in hips if s not in new_files], "new": hips}
+        for s in new_files:
+            print("%-16s only in the new tree: pooled" % s, flush=True)
+    else:
+        # a source the old tree does not have yet is a NEW file: named, not compared (its kernels cannot change an old one)
+        sources = {"old": [s for s in hips if s not in new_files]}
+        sources["new"] = sources["old"]
+        for s in new_files:
+            print("%-16s only in the new tree: not compared" % s, flush=True)
     jobs = []
     for tag, csrc in (("old", args.old_csrc), ("new", args.new_csrc)):
         os.makedirs(os.path.join(work, tag), exist_ok=True)
-        for src in sources:
+        for src in sources[tag]:
             obj = os.path.join(work, tag, src[:-4] + ".o")
             jobs.append([hipcc] + b.FLAGS + b.EXTRA_FLAGS.get(src, []) +
                         ["--cuda-device-only", "--no-gpu-bundle-output", "-c", os.path.join(csrc, src), "-o", obj])
@@ -119,13 +130,38 @@ def main():
     with ThreadPoolExecutor(max_workers=max(1, args.jobs)) as ex:
         list(ex.map(run, jobs))
 
+    def pooled(tag, srcs):
+        """functions and metadata of all files of one tree in one table each, keyed by symbol (a symbol that two files
+        of a tree define -- one template instance used in both -- is keyed 'symbol [file]' in the later one)"""
+        f_all, m_all, home = {}, {}, {}
+        for src in srcs:
+            obj = os.path.join(work, tag, src[:-4] + ".o")
+            f, _ = functions(readelf, obj)
+            for table, part in ((f_all, f), (m_all, kernel_metadata(readelf, obj))):
+                for k, v in part.items():
+                    table[k + " [" + src + "]" if k in table else k] = v
+            for k in f:
+                home.setdefault(k, src)
+        return f_all, m_all, home
+
     bad = 0
     tot_funcs = tot_kernels = 0
-    for src in sources:
-        o, n = (os.path.join(work, t, src[:-4] + ".o") for t in ("old", "new"))
-        fo, order_o = functions(readelf, o)
-        fn, order_n = functions(readelf, n)
-        mo, mn = kernel_metadata(readelf, o), kernel_metadata(readelf, n)
+    if args.pool:
+        pool_o, pool_n = pooled("old", sources["old"]), pooled("new", sources["new"])
+        moved = {}
+        for k in set(pool_o[2]) & set(pool_n[2]):
+            if pool_o[2][k] != pool_n[2][k]:
+                moved.setdefault((pool_o[2][k], pool_n[2][k]), []).append(k)
+        for (src_o, src_n), names in sorted(moved.items()):
+            print("moved %s -> %s: %d functions" % (src_o, src_n, len(names)))
+        units = [("all files", pool_o[0], [], pool_n[0], [], pool_o[1], pool_n[1])]
+    else:
+        units = []
+        for src in sources["new"]:
+            o, n = (os.path.join(work, t, src[:-4] + ".o") for t in ("old", "new"))
+            units.append((src,) + functions(readelf, o) + functions(readelf, n) +
+                         (kernel_metadata(readelf, o), kernel_metadata(readelf, n)))
+    for src, fo, order_o, fn, order_n, mo, mn in units:
         removed = sorted((set(fo) - set(fn)) | (set(mo) - set(mn)))
         added = sorted((set(fn) - set(fo)) | (set(mn) - set(mo)))
         code_diff = sorted(k for k in set(fo) & set(fn) if fo[k] != fn[k])
@@ -148,7 +184,7 @@ def main():
             print("    metadata differs: %s\n        old %r\n        new %r" % (k, mo[k], mn[k]))
         bad += not ok
     print("%d files, %d functions, %d kernels: %s" % (
-        len(sources), tot_funcs, tot_kernels,
+        len(sources["new"]), tot_funcs, tot_kernels,
         "no kernel added, removed or different" if not bad else "%d file(s) DIFFER" % bad))
     return 1 if bad else 0
 
