@@ -719,6 +719,80 @@ int mpreid_adam_step_f32(float *param_dev, const float *grad_dev, float *exp_avg
                          float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled,
                          mpreid_stream_t stream);
 
+/* ---- Stage-2 head (processor/processor_uniprompt_stage2.py:114-119, loss/make_loss.py): BNNeck in training mode, the bias-free
+ * classifiers, the label-smoothed identity loss, the batch-hard triplet loss, and their gradients ----
+ * Small fp32 entry points between the tower's output features and the scalar loss.  No atomics and a fixed summation order: the
+ * same bits from run to run.  Every output element is written and no other byte; every argument error is found before anything
+ * is launched; stream-ordered, no host synchronisation; a NULL optional output is not computed and leaves the other outputs'
+ * bits unchanged.  Float and int32 buffers 4-byte aligned, labels 8, the workspace 256.  Inputs are taken to be finite.
+ *
+ * Row cross-entropy with label smoothing (loss/softmax_loss.py:24-35; epsilon = 0: F.cross_entropy with mean reduction).
+ * K = classes, t_ac = (1 - epsilon) [c == y_a] + epsilon / K, logp_ac = (x_ac - max_a) - log sum_c exp(x_ac - max_a):
+ *   row_loss[a] = -sum_c t_ac logp_ac = (1 - epsilon) (lse_a - (x_ay - max_a)) + (epsilon / K) (K lse_a - sum_c (x_ac - max_a))
+ *   loss = (scale / rows) sum_a row_loss[a]          d_logits_ac = (scale / rows) (p_ac - t_ac)          argmax[a] = lowest index of max_a
+ * (the target of the label's class is computed as 1 - epsilon (K - 1) / K: exactly 1 at K = 1, where loss and gradient are 0.0;
+ * the exp sum leaves out the maximum's own term, exactly 1, and lse_a = log1p of the rest; at the maximum's class p - t is formed
+ * from q = rest / (1 + rest) = 1 - p, so a row whose label holds nearly all the probability keeps its digits).
+ * One workgroup of 256 threads per row, looping over the classes: any classes >= 1.  Summation order: thread t adds the entries
+ * t, t + 256, ... ascending, butterfly 32, 16, 8, 4, 2, 1 per wave, then the four wave sums in order; the loss the same over the rows.
+ * logits_dev [rows][classes] with leading dimension ld >= classes; d_logits_dev [rows][classes] dense, argmax_dev int32 [rows]: both
+ * optional.  row_loss_dev [rows] is an output.  LIMIT: the CONTENTS of labels_dev are device data and are NOT checked here (the
+ * caller does: mpreid.ops.xent_rows); a label outside 0 .. classes - 1 belongs to no class -- its one-hot term is absent from
+ * loss and gradient -- and is never used as an address. */
+int mpreid_xent_rows_f32(const float *logits_dev, int64_t ld, const int64_t *labels_dev, int rows, int classes, float epsilon,
+                         float scale, float *loss_dev /* [1] */, float *row_loss_dev, float *d_logits_dev, int32_t *argmax_dev,
+                         mpreid_stream_t stream);
+/* Batch-hard triplet loss (loss/triplet_loss.py:51-134 with its default arguments, normalize_feature = False).
+ *   d_ab = sqrt(max(sum_e (x_ae - x_be)^2, 1e-12)), ONE fmaf chain over the features, ascending
+ * DIFFERENCE from the reference: its euclidean_dist forms |x_a|^2 + |x_b|^2 - 2 x_a . x_b, which in fp32 loses the digits of close
+ * pairs (on the diagonal it gives noise of the order of 1e-3 where the exact value is the clamp, 1e-6); this is the
+ * exact-arithmetic value of that expression.
+ * Per anchor a: p = the largest d_ab among the rows with the anchor's label (the anchor included, as in the reference), n = the
+ * smallest among the others, ties to the lowest index (lane l of one wave scans b = l, l + 64, ... ascending, then the butterfly);
+ * ap = d_ap (1 + hard_factor), an = d_an (1 - hard_factor), these are dist_ap / dist_an;
+ *   soft_margin == 0: term = max(0, ap - an + margin), w = [ap - an + margin > 0]
+ *   soft_margin != 0: term = log(1 + exp(ap - an)) = max(z, 0) + log1p(exp(-|z|)), w = sigmoid(ap - an)       (margin unused)
+ *   loss = (scale / B) sum_a term_a  (summed as above: thread t of 256, butterfly, four waves)
+ *   d_feat = sum_a (scale / B) w_a ((1 + hard_factor) (x_a - x_p) / d_ap  [rows a: +, p: -]  -  (1 - hard_factor) (x_a - x_n) / d_an  [a: +, n: -])
+ * a pair whose squared distance is below 1e-12 contributes nothing (the clamp).  d_feat row r is written by one workgroup that
+ * walks the anchors in ascending order and adds, one fmaf each, what r receives as that anchor (positive term, negative term),
+ * as its positive, as its negative.  An anchor without any negative: n_idx = -1, dist_an = +inf, no loss and no gradient.
+ * Unequal group sizes are answered (the reference's view(N, -1) raises there).
+ * Limits: 1 <= batch <= MPREID_TRIPLET_MAX_BATCH (the [B][B] matrix lives in the workspace; above: MPREID_ERR_UNSUPPORTED),
+ * dim >= 1.  The labels are only compared with each other: any int64 values.  d_feat_dev [batch][dim] is optional. */
+#define MPREID_TRIPLET_MAX_BATCH 1024
+size_t mpreid_triplet_workspace_bytes(int batch, int dim);   /* needs no device; 0 for a bad request */
+int mpreid_triplet_hard_f32(const float *feat_dev /* [batch][dim] */, const int64_t *labels_dev, int batch, int dim, float margin,
+                            int soft_margin, float hard_factor, float scale, float *loss_dev /* [1] */, float *dist_ap_dev,
+                            float *dist_an_dev /* [batch] */, int32_t *p_idx_dev, int32_t *n_idx_dev /* [batch] */,
+                            float *d_feat_dev, void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
+/* nn.BatchNorm1d in training mode on x_dev [batch][dim], one thread per column, rows ascending:
+ *   mean = (sum_b x) / B (sequential), var = (sum_b (x - mean)^2) / B (two-pass, one fmaf chain), invstd = 1 / sqrt(var + eps),
+ *   y = fmaf((x - mean) * invstd, gamma, beta); mean_dev and invstd_dev [dim] are saved for the backward pass.
+ * running_mean_dev / running_var_dev (both or neither) are updated in place: r += momentum (mean - r), with the unbiased
+ * variance (sum_b (x - mean)^2) / (B - 1).  batch == 1 is refused (MPREID_ERR_ARG), as torch refuses it in training. */
+int mpreid_bn1d_train_forward_f32(const float *x_dev, const float *gamma_dev, const float *beta_dev, int batch, int dim, float eps,
+                                  float momentum, float *y_dev, float *mean_dev, float *invstd_dev, float *running_mean_dev,
+                                  float *running_var_dev, mpreid_stream_t stream);
+/* Its backward pass, xhat = (x - mean) * invstd recomputed: dgamma = sum_b dy xhat (one fmaf chain), dbeta = sum_b dy (optional),
+ *   dx = (gamma invstd / B) ((B dy - sum dy) - xhat sum(dy xhat)) [+ dx_add, when given: another gradient of x, [batch][dim]]
+ * dx_dev may not overlap any input. */
+int mpreid_bn1d_train_backward_f32(const float *x_dev, const float *dy_dev, const float *gamma_dev, const float *mean_dev,
+                                   const float *invstd_dev, const float *dx_add_dev, int batch, int dim, float *dx_dev,
+                                   float *dgamma_dev, float *dbeta_dev, mpreid_stream_t stream);
+/* The small fp32 matrix product behind a bias-free nn.Linear, on the vector units (not the matrix cores: bit-defined):
+ *   C[m][n] = sum_k A(m, k) B(n, k),   A(m, k) = a_dev[m a_rs + k a_cs],   B(n, k) = b_dev[n b_rs + k b_cs],   C dense rows of ldc
+ * each element ONE fmaf chain over k ascending from 0.0; c_add_dev (optional, laid out as C) is added to it last.  With f [B][D], W [C][D], dS [B][C]:
+ *   S = f W^T: (f, D, 1, W, D, 1, B, C, D)      d_f = dS W: (dS, C, 1, W, 1, D, B, D, C)      dW = dS^T f: (dS, 1, C, f, 1, D, C, D, B)
+ * Strides >= 1 in elements; c_dev may not overlap the inputs. */
+int mpreid_matmul_f32(const float *a_dev, int64_t a_rs, int64_t a_cs, const float *b_dev, int64_t b_rs, int64_t b_cs, int m, int n,
+                      int k, const float *c_add_dev, float *c_dev, int64_t ldc, mpreid_stream_t stream);
+/* The total of a head step from its loss terms (each already carries its weight): terms_dev holds n_id identity terms, then
+ * n_tri triplet terms, then n_i2t image-to-text terms (at most 64 in all), each group added in order from 0.0:
+ *   out[1] = identity part, out[2] = triplet part, out[3] = image-to-text part, out[0] = out[3] + (out[1] + out[2]) */
+int mpreid_stage2_total_f32(const float *terms_dev, int n_id, int n_tri, int n_i2t, float *out_dev /* [4] */,
+                            mpreid_stream_t stream);
+
 /* processor/processor_uniprompt_stage2.py:636-640: out[rows][dim] = mean over the views of
  * feats[n_views][rows][dim] (sequential sum in view order, true division), then F.normalize(p=2, dim=1,
  * eps=1e-12) when normalize != 0. */

@@ -81,8 +81,12 @@ def _stage1_defaults():
 
 def make_defaults():
     return CfgNode({
-        "SOLVER": {"STAGE1": _stage1_defaults(), "STAGE1A": _stage1_defaults(), "STAGE1B": _stage1_defaults()},
+        "SOLVER": {"STAGE1": _stage1_defaults(), "STAGE1A": _stage1_defaults(), "STAGE1B": _stage1_defaults(),
+                   "MARGIN": 0.3},   # the triplet loss's margin (loss/make_loss.py)
         "MODEL": {"NAME": "ViT-B-16", "DEVICE": "cuda", "DEVICE_ID": "0", "STRIDE_SIZE": [16, 16],
+                  # what loss/make_loss.py reads (reference config/defaults.py:39-49)
+                  "ID_LOSS_WEIGHT": 1.0, "TRIPLET_LOSS_WEIGHT": 1.0, "I2T_LOSS_WEIGHT": 1.0, "METRIC_LOSS_TYPE": "triplet",
+                  "NO_MARGIN": False, "IF_LABELSMOOTH": "on",
                   "SIE_CAMERA": False, "SIE_VIEW": False, "SIE_COE": 3.0, "NECK": "bnneck", "COS_LAYER": False,
                   "DIST_TRAIN": False, "INIT_SEED": 7, "ENCODER_PRECISION": "split",
                   # not a reference key: the row of the Uni-Prompt prompt that get_text reads out.  The reference takes it
@@ -107,7 +111,7 @@ def make_defaults():
                      # gallery and all the others are queries (datasets/make_dataloader.py:vehicleid_trial_splits, drawn
                      # from TRIAL_SEED).  '' = the single query-then-gallery evaluation
                      "PROTOCOL": "", "TRIAL_SEED": 0},
-        "DATALOADER": {"NUM_WORKERS": 0},
+        "DATALOADER": {"NUM_WORKERS": 0, "SAMPLER": "softmax", "NUM_INSTANCE": 16},
         "TEST": {"IMS_PER_BATCH": 64, "RE_RANKING": False, "WEIGHT": "", "NECK_FEAT": "before", "FEAT_NORM": "yes",
                  "DIST_MAT": "dist_mat.npy", "EVAL": False,
                  "DISTANCE_MODE": "exact", "RERANK_ALGO": "exact",   # not reference keys: see processor.do_inference

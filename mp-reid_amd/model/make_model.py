@@ -11,7 +11,8 @@ does, even at test time, model/make_model.py:137-139); weights are seeded random
 ``load_param`` is called.  MODEL.NAME 'RN50' selects the CLIP ModifiedResNet tower (2048 + 1024 = 3072-d feature,
 model/make_model.py:40-42, 82-86).  MODEL.MOE.ENABLED (ViT-B-16 only) creates the MoE parameters of the reference's
 MoETransformer under ``image_encoder.`` (experts.{e}.c_fc / c_proj, gate.weight) and runs the MoE tower.
-Training-mode forward and the text tower are out of scope.
+Training-mode forward and the text tower are out of scope; ``stage2_head(cfg)`` gives the stage-2 head
+(BNNeck in training mode, classifiers, make_loss and their gradients) as one fused step over the module's own parameters.
 """
 import numpy as np
 import torch
@@ -186,6 +187,16 @@ class build_transformer(nn.Module):
         if view == 0 and x.dtype != torch.uint8:
             return enc(x, cv_embed)
         return enc.forward_view(x, view, cv_embed, self.pixel_mean, self.pixel_std)
+
+    def stage2_head(self, cfg):
+        """The stage-2 head of this model as one fused step on the device (mpreid.ops.Stage2Head): bound to the module's own
+        classifier and bottleneck parameters and running statistics, which a step changes IN PLACE (the module must be on the
+        device), with the loss settings make_loss reads from cfg.  A step drops the folded encoder: the eval forward with
+        TEST.NECK_FEAT 'after' folds the running statistics of the bottlenecks."""
+        return _ops.Stage2Head(self.classifier.weight, self.classifier_proj.weight, self.bottleneck, self.bottleneck_proj,
+                               id_weight=cfg.MODEL.ID_LOSS_WEIGHT, triplet_weight=cfg.MODEL.TRIPLET_LOSS_WEIGHT,
+                               i2t_weight=cfg.MODEL.I2T_LOSS_WEIGHT, epsilon=0.1 if cfg.MODEL.IF_LABELSMOOTH == 'on' else None,
+                               margin=None if cfg.MODEL.NO_MARGIN else cfg.SOLVER.MARGIN, on_update=self._invalidate)
 
     def load_param(self, trained_path):
         param_dict = torch.load(trained_path, map_location="cpu")

@@ -65,6 +65,7 @@ class VitMoe(C.Structure):
 
 TEXT_MAX_TOKENS = 128   # MPREID_TEXT_MAX_TOKENS
 SUPCON_MAX_BATCH = 1024   # MPREID_SUPCON_MAX_BATCH
+TRIPLET_MAX_BATCH = 1024  # MPREID_TRIPLET_MAX_BATCH
 
 
 class TextCfg(C.Structure):
@@ -234,6 +235,14 @@ PROTOTYPES = {
     "mpreid_supcon_f32": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "mpreid_rows_segment_sum_f32": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "mpreid_adam_step_f32": (i32, [vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, f32, i32, vp]),
+    # the stage-2 head: row cross-entropy, batch-hard triplet loss, BatchNorm1d in training mode, the linear products, the total
+    "mpreid_xent_rows_f32": (i32, [vp, i64, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp]),
+    "mpreid_triplet_workspace_bytes": (sz, [i32, i32]),
+    "mpreid_triplet_hard_f32": (i32, [vp, vp, i32, i32, f32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "mpreid_bn1d_train_forward_f32": (i32, [vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp]),
+    "mpreid_bn1d_train_backward_f32": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "mpreid_matmul_f32": (i32, [vp, i64, i64, vp, i64, i64, i32, i32, i32, vp, vp, i64, vp]),
+    "mpreid_stage2_total_f32": (i32, [vp, i32, i32, i32, vp, vp]),
     "mpreid_tta_mean_f32": (i32, [vp, i32, i64, i32, i32, vp, vp]),
     "mpreid_resize_workspace_bytes": (sz, [i32, i32, i32]),
     "mpreid_resize_bilinear_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),

@@ -1646,6 +1646,373 @@ class PromptTrainer:
         return b["loss"]
 
 
+# ----------------------------------------------------------------------------------------------
+# Stage-2 head (include/mpreid.h: mpreid_xent_rows_f32, mpreid_triplet_hard_f32, mpreid_bn1d_train_*_f32, mpreid_matmul_f32)
+# ----------------------------------------------------------------------------------------------
+def _i32_buffer(t: Optional[torch.Tensor], shape, device, what: str) -> torch.Tensor:
+    if t is None:
+        return torch.empty(shape, dtype=torch.int32, device=device)
+    assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), what
+    return t
+
+
+def check_class_labels(labels, rows: int, classes: int) -> None:
+    """host-side validation of class labels (the library does not look at their contents): integers in 0 .. classes - 1"""
+    i = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    if i.shape != (rows,) or i.dtype == np.bool_ or not np.issubdtype(i.dtype, np.integer):
+        raise ValueError(f"labels: expected {rows} integers, got shape {i.shape} of {i.dtype}")
+    if rows and (int(i.min()) < 0 or int(i.max()) >= classes):
+        raise ValueError(f"labels: values must lie in 0 .. {classes - 1}, got {int(i.min())} .. {int(i.max())}")
+
+
+def _rows_f32(t, device, what: str) -> torch.Tensor:
+    """a 2-D fp32 device tensor with unit column stride (a column slice of a wider matrix is fine), copied only when it is not"""
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(t)
+    if t.dim() != 2:
+        raise ValueError(f"{what}: expected a matrix, got {tuple(t.shape)}")
+    t = t.detach().to(device=device, dtype=torch.float32)
+    if t.shape[1] > 1 and t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        t = t.contiguous()
+    return t
+
+
+def xent_rows(logits: torch.Tensor, labels: torch.Tensor, epsilon: float = 0.0, scale: float = 1.0, need_grad: bool = True,
+              need_argmax: bool = False, validate: bool = True, loss: Optional[torch.Tensor] = None,
+              row_loss: Optional[torch.Tensor] = None, d_logits: Optional[torch.Tensor] = None,
+              argmax: Optional[torch.Tensor] = None):
+    """Row cross-entropy with label smoothing and its gradient (mpreid_xent_rows_f32): logits fp32 [rows, classes], labels int64
+    [rows] -> (loss [1] = -(scale / rows) sum_a sum_c t_ac log_softmax(logits)_ac with t_ac = (1 - epsilon) [c == y_a] +
+    epsilon / classes; d_logits [rows, classes] or None; argmax int32 [rows] (lowest index of the row maximum) or None), all on the
+    device, nothing synchronised.  validate=False skips the host-side range check of the labels (it reads them back)."""
+    dev = _lib.require_gpu()
+    logits = _rows_f32(logits, dev, "xent_rows: logits")
+    rows, classes = logits.shape
+    if rows < 1 or classes < 1:
+        raise ValueError("xent_rows: an empty matrix has no loss")
+    if validate:
+        check_class_labels(labels, rows, classes)
+    labels = _dev_i64(labels, dev)
+    if tuple(labels.shape) != (rows,):
+        raise ValueError(f"xent_rows: labels must be [{rows}], got {tuple(labels.shape)}")
+    loss = _f32_buffer(loss, (1,), dev, "loss")
+    row_loss = _f32_buffer(row_loss, (rows,), dev, "row_loss")
+    d_logits = _f32_buffer(d_logits, (rows, classes), dev, "d_logits") if need_grad else None
+    argmax = _i32_buffer(argmax, (rows,), dev, "argmax") if need_argmax else None
+    _lib.check(_lib.load().mpreid_xent_rows_f32(_ptr(logits), logits.stride(0) if rows > 1 else classes, _ptr(labels), rows, classes,
+                                                float(epsilon), float(scale), _ptr(loss), _ptr(row_loss), _ptr(d_logits), _ptr(argmax),
+                                                _lib.stream_ptr()), "mpreid_xent_rows_f32")
+    return loss, d_logits, argmax
+
+
+def triplet_hard(feat: torch.Tensor, labels: torch.Tensor, margin: Optional[float] = None, hard_factor: float = 0.0,
+                 scale: float = 1.0, need_grad: bool = True, loss: Optional[torch.Tensor] = None,
+                 d_feat: Optional[torch.Tensor] = None):
+    """The batch-hard triplet loss and its gradient (mpreid_triplet_hard_f32): feat fp32 [B, dim], labels int64 [B] (only compared
+    with each other); margin None is the soft-margin form.  -> (loss [1], dist_ap [B], dist_an [B], p_idx int32 [B], n_idx int32
+    [B], d_feat [B, dim] or None), on the device, nothing synchronised.  1 <= B <= TRIPLET_MAX_BATCH."""
+    dev = _lib.require_gpu()
+    L = _lib.load()
+    feat = _dev_f32(feat, dev)
+    if feat.dim() != 2 or feat.shape[0] < 1 or feat.shape[1] < 1:
+        raise ValueError(f"triplet_hard: feat must be [B, dim], got {tuple(feat.shape)}")
+    B, D = feat.shape
+    if B > _lib.TRIPLET_MAX_BATCH:
+        raise ValueError(f"triplet_hard: batch {B} above TRIPLET_MAX_BATCH = {_lib.TRIPLET_MAX_BATCH}")
+    labels = _dev_i64(labels, dev)
+    if tuple(labels.shape) != (B,):
+        raise ValueError(f"triplet_hard: labels must be [{B}], got {tuple(labels.shape)}")
+    loss = _f32_buffer(loss, (1,), dev, "loss")
+    d_feat = _f32_buffer(d_feat, (B, D), dev, "d_feat") if need_grad else None
+    stats = torch.empty((2, B), dtype=torch.float32, device=dev)
+    idx = torch.empty((2, B), dtype=torch.int32, device=dev)
+    ws = _workspace("triplet", L.mpreid_triplet_workspace_bytes(B, D), dev)
+    _lib.check(L.mpreid_triplet_hard_f32(_ptr(feat), _ptr(labels), B, D, float(margin or 0.0), int(margin is None), float(hard_factor),
+                                         float(scale), _ptr(loss), _ptr(stats[0]), _ptr(stats[1]), _ptr(idx[0]), _ptr(idx[1]),
+                                         _ptr(d_feat), _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_triplet_hard_f32")
+    return loss, stats[0], stats[1], idx[0], idx[1], d_feat
+
+
+def _vec_f32(t, n: int, what: str) -> torch.Tensor:
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n,)):
+        raise ValueError(f"{what}: expected a contiguous fp32 device tensor [{n}]")
+    return t.detach()
+
+
+def bn1d_train(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, running_mean: Optional[torch.Tensor] = None,
+               running_var: Optional[torch.Tensor] = None, momentum: float = 0.1, eps: float = 1e-5,
+               y: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None, invstd: Optional[torch.Tensor] = None):
+    """nn.BatchNorm1d in training mode (mpreid_bn1d_train_forward_f32): x fp32 [B, dim], B >= 2 -> (y [B, dim], the batch mean
+    [dim], 1 / sqrt(biased variance + eps) [dim]); running_mean / running_var (both or neither, device tensors) are updated IN
+    PLACE with the momentum and the unbiased variance"""
+    dev = _lib.require_gpu()
+    x = _dev_f32(x, dev)
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError(f"bn1d_train: x must be [B, dim], got {tuple(x.shape)}")
+    B, D = x.shape
+    if B < 2:
+        raise ValueError(f"bn1d_train: expected more than 1 value per channel when training, got a batch of {B}")
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("bn1d_train: running_mean and running_var come together")
+    w, b = _vec_f32(weight, D, "weight"), _vec_f32(bias, D, "bias")
+    rm = None if running_mean is None else _vec_f32(running_mean, D, "running_mean")
+    rv = None if running_var is None else _vec_f32(running_var, D, "running_var")
+    y, mean, invstd = _f32_buffer(y, (B, D), dev, "y"), _f32_buffer(mean, (D,), dev, "mean"), _f32_buffer(invstd, (D,), dev, "invstd")
+    _lib.check(_lib.load().mpreid_bn1d_train_forward_f32(_ptr(x), _ptr(w), _ptr(b), B, D, float(eps), float(momentum), _ptr(y), _ptr(mean),
+                                                         _ptr(invstd), _ptr(rm), _ptr(rv), _lib.stream_ptr()),
+               "mpreid_bn1d_train_forward_f32")
+    return y, mean, invstd
+
+
+def bn1d_train_backward(x: torch.Tensor, dy: torch.Tensor, weight: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor,
+                        dx_add: Optional[torch.Tensor] = None, need_dbeta: bool = True, dx: Optional[torch.Tensor] = None,
+                        dweight: Optional[torch.Tensor] = None, dbias: Optional[torch.Tensor] = None):
+    """its backward pass (mpreid_bn1d_train_backward_f32) from the saved statistics -> (dx [B, dim] (+ dx_add: another gradient
+    of x), dweight [dim], dbias [dim] or None)"""
+    dev = _lib.require_gpu()
+    x, dy = _dev_f32(x, dev), _dev_f32(dy, dev)
+    if x.dim() != 2 or x.shape != dy.shape or x.shape[0] < 2:
+        raise ValueError(f"bn1d_train_backward: x and dy must be [B >= 2, dim] of one shape, got {tuple(x.shape)} and {tuple(dy.shape)}")
+    B, D = x.shape
+    w, mean, invstd = _vec_f32(weight, D, "weight"), _vec_f32(mean, D, "mean"), _vec_f32(invstd, D, "invstd")
+    if dx_add is not None:
+        dx_add = _dev_f32(dx_add, dev)
+        assert dx_add.shape == x.shape, "dx_add"
+    dx, dweight = _f32_buffer(dx, (B, D), dev, "dx"), _f32_buffer(dweight, (D,), dev, "dweight")
+    dbias = _f32_buffer(dbias, (D,), dev, "dbias") if need_dbeta else None
+    _lib.check(_lib.load().mpreid_bn1d_train_backward_f32(_ptr(x), _ptr(dy), _ptr(w), _ptr(mean), _ptr(invstd), _ptr(dx_add), B, D,
+                                                          _ptr(dx), _ptr(dweight), _ptr(dbias), _lib.stream_ptr()),
+               "mpreid_bn1d_train_backward_f32")
+    return dx, dweight, dbias
+
+
+def _matmul(a, a_rs, a_cs, b, b_rs, b_cs, m, n, k, out, add=None):
+    _lib.check(_lib.load().mpreid_matmul_f32(_ptr(a), a_rs, a_cs, _ptr(b), b_rs, b_cs, m, n, k, _ptr(add), _ptr(out), n,
+                                             _lib.stream_ptr()), "mpreid_matmul_f32")
+    return out
+
+
+def _linear_operands(x, w, what: str):
+    dev = _lib.require_gpu()
+    x, w = _dev_f32(x, dev), _dev_f32(w, dev)
+    if x.dim() != 2 or w.dim() != 2 or min(x.shape) < 1 or min(w.shape) < 1:
+        raise ValueError(f"{what}: expected two non-empty matrices, got {tuple(x.shape)} and {tuple(w.shape)}")
+    return dev, x, w
+
+
+def linear_forward(f: torch.Tensor, weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """S = f . weight^T of a bias-free nn.Linear (mpreid_matmul_f32): f [B, D], weight [C, D] -> [B, C]; each element one fmaf
+    chain over D, ascending"""
+    dev, f, weight = _linear_operands(f, weight, "linear_forward")
+    if f.shape[1] != weight.shape[1]:
+        raise ValueError(f"linear_forward: f {tuple(f.shape)} and weight {tuple(weight.shape)} differ in width")
+    (B, D), Cn = f.shape, weight.shape[0]
+    return _matmul(f, D, 1, weight, D, 1, B, Cn, D, _f32_buffer(out, (B, Cn), dev, "out"))
+
+
+def linear_grad_input(d_scores: torch.Tensor, weight: torch.Tensor, add: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d_f = d_scores . weight (+ add): d_scores [B, C], weight [C, D] -> [B, D]; each element one fmaf chain over C, ascending"""
+    dev, d_scores, weight = _linear_operands(d_scores, weight, "linear_grad_input")
+    if d_scores.shape[1] != weight.shape[0]:
+        raise ValueError(f"linear_grad_input: d_scores {tuple(d_scores.shape)} and weight {tuple(weight.shape)} do not match")
+    (B, Cn), D = d_scores.shape, weight.shape[1]
+    if add is not None:
+        add = _dev_f32(add, dev)
+        assert tuple(add.shape) == (B, D), "add"
+    return _matmul(d_scores, Cn, 1, weight, 1, D, B, D, Cn, _f32_buffer(out, (B, D), dev, "out"), add)
+
+
+def linear_grad_weight(d_scores: torch.Tensor, f: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d_weight = d_scores^T . f: d_scores [B, C], f [B, D] -> [C, D]; each element one fmaf chain over B, ascending"""
+    dev, d_scores, f = _linear_operands(d_scores, f, "linear_grad_weight")
+    if d_scores.shape[0] != f.shape[0]:
+        raise ValueError(f"linear_grad_weight: d_scores {tuple(d_scores.shape)} and f {tuple(f.shape)} differ in batch")
+    (B, Cn), D = d_scores.shape, f.shape[1]
+    return _matmul(d_scores, 1, Cn, f, 1, D, Cn, D, B, _f32_buffer(out, (Cn, D), dev, "out"))
+
+
+class Stage2Step:
+    """what Stage2Head.step returns: device tensors that the next step of the same batch size and form overwrites.  loss [1];
+    id_loss, triplet_loss, i2t_loss: views of the three parts AS THEY ENTER the loss (weights applied); scores (classifier,
+    classifier_proj or None) and i2t_logits (or None); d_f_last, d_f, d_f_proj; grads: parameter name -> gradient;
+    acc: (i2t_logits.max(1)[1] == target).float().mean() as a device scalar, or None without text features."""
+
+    def __init__(self, parts, scores, i2t_logits, argmax, target, d_f_last, d_f, d_f_proj, grads):
+        self.loss, self.id_loss, self.triplet_loss, self.i2t_loss = parts[0:1], parts[1], parts[2], parts[3]
+        self.scores, self.i2t_logits, self.i2t_argmax, self._target = scores, i2t_logits, argmax, target
+        self.d_f_last, self.d_f, self.d_f_proj, self.grads = d_f_last, d_f, d_f_proj, grads
+
+    @property
+    def acc(self):
+        return None if self.i2t_argmax is None else (self.i2t_argmax == self._target).float().mean()
+
+
+class Stage2Head:
+    """The stage-2 head as one fused step on the device, without autograd (reference model/make_model.py:98-112 in training
+    mode, loss/make_loss.py, processor/processor_uniprompt_stage2.py:114-119): BNNeck in training mode, the two bias-free
+    classifiers, the label-smoothed identity loss, the batch-hard triplet loss, the image-to-text loss, and the gradients with
+    respect to the three features and the head's parameters.  The launch counts are in csrc/stage2_head.hip.
+
+    classifier / classifier_proj: the weights [classes, width] / [classes, width_proj]; bottleneck / bottleneck_proj: dicts (or
+    modules) with weight, bias, running_mean, running_var and num_batches_tracked; all fp32 on the device, used IN PLACE.
+    epsilon None: plain cross-entropy (MODEL.IF_LABELSMOOTH off); margin None: the soft-margin triplet loss (MODEL.NO_MARGIN).
+    on_update: called after a step has changed the running statistics (the model invalidates its folded encoder)."""
+
+    FORMS = ("uniprompt", "list")
+    PARAMS = ("classifier.weight", "classifier_proj.weight", "bottleneck.weight", "bottleneck.bias", "bottleneck_proj.weight",
+              "bottleneck_proj.bias")
+
+    def __init__(self, classifier: torch.Tensor, classifier_proj: torch.Tensor, bottleneck, bottleneck_proj,
+                 id_weight: float = 1.0, triplet_weight: float = 1.0, i2t_weight: float = 1.0, epsilon: Optional[float] = 0.1,
+                 margin: Optional[float] = 0.3, momentum: float = 0.1, bn_eps: float = 1e-5, on_update=None):
+        self.device = _lib.require_gpu()
+
+        def get(src, k):
+            return src[k] if isinstance(src, dict) else getattr(src, k)
+        self.C, self.D = classifier.shape
+        self.Dp = classifier_proj.shape[1]
+        if classifier_proj.shape[0] != self.C:
+            raise ValueError("Stage2Head: the two classifiers differ in their number of classes")
+        self.params = {"classifier.weight": classifier, "classifier_proj.weight": classifier_proj}
+        self.bn = {}
+        for name, src, n in (("bottleneck", bottleneck, self.D), ("bottleneck_proj", bottleneck_proj, self.Dp)):
+            self.params[name + ".weight"], self.params[name + ".bias"] = get(src, "weight"), get(src, "bias")
+            self.bn[name] = (get(src, "running_mean"), get(src, "running_var"), get(src, "num_batches_tracked"))
+            for t in (self.params[name + ".weight"], self.params[name + ".bias"]) + self.bn[name][:2]:
+                _vec_f32(t, n, "Stage2Head: " + name)
+        for k in ("classifier.weight", "classifier_proj.weight"):
+            t = self.params[k]
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError(f"Stage2Head: {k} is a contiguous fp32 tensor on the device")
+        self.id_weight, self.triplet_weight, self.i2t_weight = float(id_weight), float(triplet_weight), float(i2t_weight)
+        self.epsilon = 0.0 if epsilon is None else float(epsilon)
+        self.margin, self.momentum, self.bn_eps, self.on_update = margin, float(momentum), float(bn_eps), on_update
+        self._bufs = {}
+
+    def _buffers(self, B: int, T: int, form: str):
+        key = (B, T, form)
+        b = self._bufs.get(key)
+        if b is None:
+            dev = self.device
+
+            def e(*shape):
+                return torch.empty(shape, dtype=torch.float32, device=dev)
+            b = self._bufs[key] = dict(terms=e(8), parts=e(4), row_loss=e(B), tri_stats=e(2, B),
+                                       tri_idx=torch.empty((2, B), dtype=torch.int32, device=dev))
+            branches = (("", self.D),) if form == "uniprompt" else (("", self.D), ("_proj", self.Dp))
+            for s, n in branches:
+                b.update({"y" + s: e(B, n), "mean" + s: e(n), "invstd" + s: e(n), "S" + s: e(B, self.C), "dS" + s: e(B, self.C),
+                          "dy" + s: e(B, n), "d_tri" + s: e(B, n)})
+            # gradients: in the Uni-Prompt form nothing ever writes those of the unused branch -- they stay the exact zeros of here
+            z = torch.zeros
+            b["grads"] = {"classifier.weight": e(self.C, self.D), "bottleneck.weight": e(self.D), "bottleneck.bias": e(self.D)}
+            if form == "uniprompt":
+                b["grads"].update({"classifier_proj.weight": z((self.C, self.Dp), device=dev), "bottleneck_proj.weight": z(self.Dp, device=dev),
+                                   "bottleneck_proj.bias": z(self.Dp, device=dev)})
+                b["d_f_last"] = z((B, self.D), device=dev)
+            else:
+                b["grads"].update({"classifier_proj.weight": e(self.C, self.Dp), "bottleneck_proj.weight": e(self.Dp),
+                                   "bottleneck_proj.bias": e(self.Dp)})
+                b["d_f_last"], b["d_add_proj"] = e(B, self.D), e(B, self.Dp)
+            b["d_f"], b["d_f_proj"] = e(B, self.D), (e(B, self.Dp) if (T or form == "list") else z((B, self.Dp), device=dev))
+            if T:
+                b.update(i2t=e(B, T), d_i2t=e(B, T), argmax=torch.empty(B, dtype=torch.int32, device=dev))
+        return b
+
+    def _triplet(self, b, feat, target, term, d_feat):
+        L = _lib.load()
+        B, D = feat.shape
+        ws = _workspace("triplet", L.mpreid_triplet_workspace_bytes(B, D), self.device)
+        st, ix = b["tri_stats"], b["tri_idx"]
+        _lib.check(L.mpreid_triplet_hard_f32(_ptr(feat), _ptr(target), B, D, float(self.margin or 0.0), int(self.margin is None), 0.0,
+                                             self.triplet_weight, _ptr(term), _ptr(st[0]), _ptr(st[1]), _ptr(ix[0]), _ptr(ix[1]),
+                                             _ptr(d_feat), _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_triplet_hard_f32")
+
+    def _identity(self, b, s, name, f, target, term, dx_add, d_f):
+        """one identity branch: BNNeck, classifier, loss, and back; the feature gradient takes dx_add along"""
+        w, beta = self.params[name + ".weight"].detach(), self.params[name + ".bias"].detach()
+        W = self.params["classifier" + s + ".weight"].detach()
+        rm, rv, nbt = self.bn[name]
+        g = b["grads"]
+        bn1d_train(f, w, beta, rm, rv, self.momentum, self.bn_eps, y=b["y" + s], mean=b["mean" + s], invstd=b["invstd" + s])
+        nbt.add_(1)
+        linear_forward(b["y" + s], W, out=b["S" + s])
+        xent_rows(b["S" + s], target, self.epsilon, self.id_weight, validate=False, loss=term, row_loss=b["row_loss"],
+                  d_logits=b["dS" + s])
+        linear_grad_input(b["dS" + s], W, out=b["dy" + s])
+        linear_grad_weight(b["dS" + s], b["y" + s], out=g["classifier" + s + ".weight"])
+        bn1d_train_backward(f, b["dy" + s], w, b["mean" + s], b["invstd" + s], dx_add=dx_add, dx=d_f, dweight=g[name + ".weight"],
+                            dbias=g[name + ".bias"])
+
+    @torch.no_grad()
+    def step(self, f_last: torch.Tensor, f: torch.Tensor, f_proj: torch.Tensor, target: torch.Tensor,
+             text_features: Optional[torch.Tensor] = None, form: str = "uniprompt", write_grad: bool = False,
+             validate: bool = False) -> Stage2Step:
+        """f_last, f fp32 [B, width], f_proj fp32 [B, width_proj] (the tower's three features: model/make_model.py:98-100),
+        target int64 [B], text_features fp32 [T, width_proj] (held constant), all on the device.
+        form 'uniprompt': identity loss on classifier(bottleneck(f)), triplet loss on f, image-to-text loss on f_proj .
+        text_features^T (it needs them); classifier_proj, bottleneck_proj and f_last receive exact zeros.
+        form 'list': make_loss over [score, score_proj] and [f_last, f, f_proj], plus the image-to-text loss when text_features
+        are given.  write_grad: the parameter gradients also become the parameters' .grad (clones).
+        The labels select a class on the device: validate=True checks them on the host first, which waits for the device."""
+        if form not in self.FORMS:
+            raise ValueError(f"Stage2Head.step: form must be one of {self.FORMS}, got {form!r}")
+        for t, n, what in ((f_last, self.D, "f_last"), (f, self.D, "f"), (f_proj, self.Dp, "f_proj")):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == n
+                    and t.shape[0] == f.shape[0]):
+                raise ValueError(f"Stage2Head.step: {what} is an fp32 device tensor [B, {n}]")
+        B = f.shape[0]
+        if B < 2 or B > _lib.TRIPLET_MAX_BATCH:
+            raise ValueError(f"Stage2Head.step: 2 <= batch <= {_lib.TRIPLET_MAX_BATCH}, got {B}")
+        if form == "uniprompt" and text_features is None:
+            raise ValueError("Stage2Head.step: the Uni-Prompt form needs the text features")
+        T = 0
+        if text_features is not None:
+            text_features = _dev_f32(text_features, self.device)
+            if text_features.dim() != 2 or text_features.shape[1] != self.Dp or text_features.shape[0] < 1:
+                raise ValueError(f"Stage2Head.step: text_features must be [T, {self.Dp}], got {tuple(text_features.shape)}")
+            T = text_features.shape[0]
+        if validate:
+            check_class_labels(target, B, min(self.C, T) if T else self.C)
+        target = _dev_i64(target, self.device)
+        if tuple(target.shape) != (B,):
+            raise ValueError(f"Stage2Head.step: target must be [{B}], got {tuple(target.shape)}")
+        f_last, f, f_proj = (t.detach().contiguous() for t in (f_last, f, f_proj))
+        b = self._buffers(B, T, form)
+        terms = b["terms"]
+        if form == "uniprompt":
+            n_id, n_tri = 1, 1
+            self._triplet(b, f, target, terms[1:2], b["d_tri"])
+            self._identity(b, "", "bottleneck", f, target, terms[0:1], b["d_tri"], b["d_f"])
+            add_proj, scores = None, (b["S"], None)
+        else:
+            n_id, n_tri = 2, 3
+            self._triplet(b, f_last, target, terms[2:3], b["d_f_last"])
+            self._triplet(b, f, target, terms[3:4], b["d_tri"])
+            self._triplet(b, f_proj, target, terms[4:5], b["d_tri_proj"])
+            self._identity(b, "", "bottleneck", f, target, terms[0:1], b["d_tri"], b["d_f"])
+            add_proj, scores = b["d_tri_proj"], (b["S"], b["S_proj"])
+        if T:
+            term = terms[n_id + n_tri:n_id + n_tri + 1]
+            linear_forward(f_proj, text_features, out=b["i2t"])
+            xent_rows(b["i2t"], target, self.epsilon, self.i2t_weight, need_argmax=True, validate=False, loss=term,
+                      row_loss=b["row_loss"], d_logits=b["d_i2t"], argmax=b["argmax"])
+            # d_f_proj in the Uni-Prompt form; in the list form what the BatchNorm backward of the projected branch takes along
+            linear_grad_input(b["d_i2t"], text_features, add=add_proj, out=b["d_f_proj"] if form == "uniprompt" else b["d_add_proj"])
+            add_proj = b.get("d_add_proj")
+        if form == "list":
+            self._identity(b, "_proj", "bottleneck_proj", f_proj, target, terms[1:2], add_proj, b["d_f_proj"])
+        _lib.check(_lib.load().mpreid_stage2_total_f32(_ptr(terms), n_id, n_tri, 1 if T else 0, _ptr(b["parts"]), _lib.stream_ptr()),
+                   "mpreid_stage2_total_f32")
+        if write_grad:
+            for k, g in b["grads"].items():
+                self.params[k].grad = g.clone()
+        if self.on_update is not None:
+            self.on_update()
+        return Stage2Step(b["parts"], scores, b.get("i2t"), b.get("argmax"), target, b["d_f_last"], b["d_f"], b["d_f_proj"], b["grads"])
+
+
 def _np_getter(state_dict):
     """name -> numpy array of a ModifiedResNet state dict (keys optionally prefixed 'image_encoder.', numpy or torch)"""
     def get(name):
