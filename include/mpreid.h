@@ -670,6 +670,107 @@ int mpreid_text_attention_backward(const float *qkv_dev, const float *d_o_dev, i
 int mpreid_layernorm_backward_f32(const float *x_dev, const float *dy_dev, const float *gamma_dev, int64_t rows, int width,
                                   int accumulate, float *dx_dev, mpreid_stream_t stream);
 
+/* ---- The image tower's gradient (stage 2): training forward, attention gradient, the sweep and the parameter gradients ----
+ * The three features stage 2 differentiates, the one backward kernel the image tower cannot borrow from the text tower, and
+ * the sweep over the layers with every parameter gradient.
+ *
+ * mpreid_vit_forward_train: the dense tower in MPREID_VIT_SPLIT precision, the launch sequence of mpreid_vit_forward plus one
+ * copy of batch rows.  Outputs, all fp32, 4-byte aligned, every element written:
+ *   f_last_dev [B][width]     the CLS row of the LAST block's input (model/clip/model.py:458-468; with one layer that is
+ *                             ln_pre's output); no ln_post
+ *   f_dev      [B][width]     ln_post(x_layers)[:, 0]
+ *   f_proj_dev [B][out_dim]   f @ proj
+ * No BatchNorm neck is applied whatever cfg.neck_after says (the stage-2 head owns BNNeck).  f | f_proj carries the bits of
+ * mpreid_vit_forward's out_dev with neck_after = 0, with cls_only_last on and off.  layers < 1 or a precision other than
+ * MPREID_VIT_SPLIT: MPREID_ERR_UNSUPPORTED; the other limits, the workspace (mpreid_vit_workspace_bytes) and the argument
+ * errors are mpreid_vit_forward's; all of them before anything is launched. */
+int mpreid_vit_forward_train(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_image_in *img, int batch,
+                             const float *cv_emb_dev, float *f_last_dev, float *f_dev, float *f_proj_dev, void *ws_dev,
+                             size_t ws_bytes, mpreid_stream_t stream);
+/* The unmasked attention gradient: qkv_dev fp32 [batch * tokens][3 * width] in the column layout of mpreid_vit_attention,
+ * d_o_dev fp32 [batch * tokens][width] -> d_qkv_dev fp32 [batch * tokens][3 * width] = dq | dk | dv; all 16-byte aligned.
+ *   P = softmax(q k^T / 8), dV = P^T dO, dP = dO V^T, dS = P o (dP - rowsum(P o dP)), dQ = dS K / 8, dK = dS^T Q / 8
+ * ONE form for every token count, two kernels of 512 threads over the workspace (16 bytes per (image, head, query row):
+ * the row's score maximum, exponential sum, dP at its strongest key, and rowsum(P o (dP - that))):
+ *   rows pass   a workgroup per (image, head, 8 query rows), a wave per row; K and V stream through LDS in 64-key blocks of
+ *               fp32 [64][68] (68: the 16-byte reads of 16 consecutive rows cover all 64 banks); writes the row statistics and dQ.
+ *               LDS = 39 168 + 64 * (tokens rounded up to 64) bytes: 51 456 at 129 .. 192 tokens (3 workgroups per CU),
+ *               55 552 at 193 .. 256, 59 648 at 257 .. 320, 67 840 at 442, 108 800 at 1025 (1 per CU).
+ *   columns pass  a workgroup per (image, head, 8 keys), a wave per key; Q and dO stream in 64-row blocks; P and dS are rebuilt
+ *               from the stored statistics; writes dK and dV.  LDS = 43 264 bytes at every token count (3 workgroups per CU).
+ * There is no resident form and so no boundary between forms.  No atomics; every sum has one fixed order: a score is one
+ * fmaf chain over the 64 features wherever it is recomputed; a row statistic is summed by lane l over the keys l, l + 64, ...
+ * ascending, then the butterfly 32 .. 1; dQ / dK / dV elements are one fmaf chain over the keys / query rows, ascending.
+ * So: the same bits from run to run, and for an image alone or inside a batch; exactly homogeneous in d_o under
+ * power-of-two scaling (short of underflow); an all-zero d_o gives zeros.  dS is taken about the row's strongest key
+ * (DESIGN section 14), which keeps the digits of saturated rows.  Every element of d_qkv_dev is written and no other byte.
+ * Limits: width == 64 * heads, width % 128 == 0, width <= 1024, 2 <= tokens <= MPREID_VIT_MAX_TOKENS, else
+ * MPREID_ERR_UNSUPPORTED; NULL or misaligned pointers, batch <= 0: MPREID_ERR_ARG; a NULL or short workspace (16-byte
+ * aligned): MPREID_ERR_WORKSPACE -- all before anything is launched. */
+size_t mpreid_vit_attention_backward_workspace_bytes(int batch, int tokens, int heads);   /* needs no device; 0 for a bad request */
+int mpreid_vit_attention_backward(const float *qkv_dev, const float *d_o_dev, int batch, int tokens, int width, int heads,
+                                  float *d_qkv_dev, void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
+
+/* mpreid_vit_backward: the three feature gradients of mpreid_vit_forward_train -> the gradient of every tower parameter, of
+ * cv_emb and of the embedded sequence.  Stateless and stream-ordered, no host synchronisation, as mpreid_text_backward: it
+ * re-runs the forward's own split-precision launches (every block on all rows, whatever cfg.cls_only_last says) keeping the
+ * embedded sequence and each block's input x_l, seeds dx at the CLS rows from d_f_dev and d_f_proj_dev (ln_post and proj are
+ * differentiated there; every other row of dx starts as exact zero), walks the layers back recomputing q | k | v, the
+ * attention output, the block's mid-point and the fp32 FC1 pre-activation with the forward's launchers, adds d_f_last_dev
+ * to the CLS rows once the last block has been swept, and sweeps ln_pre.  Any seed may be NULL (= zero).  No gradient passes
+ * through fp16: dX = dY . W is the exact fp32 GEMM over mpreid_vit_weights_t (fp32 transposed copies [in][out]); a weight
+ * gradient dW[n][k] = sum_m dY[m][n] X[m][k] is the same GEMM over two transposed operands [cols][rows rounded up to 4, pad
+ * zero] written by a transposing kernel, so it is one k-ascending chain over the token rows.  X is what the forward's GEMM
+ * multiplied: the fp16 pair unpacked to hi + lo for LayerNorm-2 outputs, the attention output and the patches, the fp32 value
+ * the pair was split from for LayerNorm-1 outputs and the MLP's hidden layer (they differ by 2^-22 relative).  Bias, beta
+ * and gamma gradients are column sums (mpreid_colsum_f32 below) in a fixed order.  No atomics: the same bits from run to run.
+ *
+ * grads: optional; fp32 device pointers in the checkpoint's layout (matrices [out][in], conv_w [width][3 * patch * patch],
+ * pos_emb [L][width], proj [width][out_dim]) plus cv_emb [batch][width], the gradient of the cv_emb_dev rows as given.
+ * NULL members (or a NULL struct) are skipped, cost nothing and leave the other outputs' bits unchanged.  Gradients are
+ * WRITTEN, not accumulated.  d_tokens_dev: optional [batch][L][width], the gradient of ln_pre's input, 16-byte aligned.
+ * Workspace, bytes per token row of width W (rows rounded up to 256): the forward's regions (mpreid_vit_workspace_bytes),
+ * 4 W the embedded sequence, layers x 4 W the x_l, 4 W dx, 16 W the hidden layer's gradient, 4 W a LayerNorm output's
+ * gradient, 12 W dq | dk | dv, 4 W the transposed attention output, 2 x 4 max(4 W, 3 patch^2, out_dim) the two transposed
+ * operands, 16 bytes per (head, row) attention statistics, and the reductions' partial sums (8 x 4 W bytes per 128 rows)
+ * and row statistics (8 bytes per row).  Errors, all before anything is launched: NULL or misaligned pointers, batch <= 0,
+ * batch * L above 65 535 * 128 rows (the column reduction's grid): MPREID_ERR_ARG; a short workspace (256-byte aligned): MPREID_ERR_WORKSPACE; layers < 1, a precision other than
+ * MPREID_VIT_SPLIT or a shape outside mpreid_vit_forward's: MPREID_ERR_UNSUPPORTED.  (The C entry point has no MoE argument;
+ * mpreid.ops refuses an MoE tower.) */
+typedef struct {                       /* device pointers, fp32, [in][out] = the transpose of the checkpoint's [out][in] */
+    const float *in_proj_t;            /* [width][3 * width] */
+    const float *out_proj_t;           /* [width][width] */
+    const float *fc_t;                 /* [width][4 * width] */
+    const float *proj_t;               /* [4 * width][width] */
+} mpreid_vit_layer_t;
+typedef struct {
+    const mpreid_vit_layer_t *layers;  /* HOST array of cfg.layers entries */
+} mpreid_vit_weights_t;
+typedef struct {                       /* device pointers, fp32, torch layout; NULL = not wanted */
+    float *in_proj_w, *in_proj_b, *out_proj_w, *out_proj_b, *fc_w, *fc_b, *proj_w, *proj_b, *ln1_g, *ln1_b, *ln2_g, *ln2_b;
+} mpreid_vit_layer_grads;
+typedef struct {
+    float *conv_w, *class_emb, *pos_emb, *ln_pre_g, *ln_pre_b, *ln_post_g, *ln_post_b, *proj, *cv_emb;
+    const mpreid_vit_layer_grads *layers;   /* HOST array of cfg.layers entries */
+} mpreid_vit_grads;
+size_t mpreid_vit_backward_workspace_bytes(const mpreid_vit_cfg *cfg, int batch);   /* needs no device; 0 for a bad request */
+int mpreid_vit_backward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_weights_t *wt,
+                        const mpreid_image_in *img, int batch, const float *cv_emb_dev, const float *d_f_last_dev,
+                        const float *d_f_dev, const float *d_f_proj_dev, const mpreid_vit_grads *grads, float *d_tokens_dev,
+                        void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
+/* The two small kernels of the parameter gradients alone, for unit tests and tools.
+ * mpreid_transpose_pad_f32: dst [cols][rows_pad] = src [rows][cols] transposed, columns rows .. rows_pad - 1 zero.
+ * mpreid_colsum_f32: out_sum[c] = sum_m dy[m][c] and out_sumx[c] = sum_m dy[m][c] xhat[m][c], xhat = (x - mean) / sigma per row
+ * of x [rows][cols] (biased variance, eps 1e-5); either output may be NULL (out_sumx needs x).  Fixed order: rows in pieces of
+ * 128, a column's piece added rows ascending, the pieces' sums added ascending; row statistics: lane l of a wave adds the
+ * elements l, l + 64, ... ascending, then the butterfly 32 .. 1.  Every step is one rounded fp32 operation (no fused
+ * multiply-add).  Workspace 256-byte aligned.  Limits, MPREID_ERR_ARG before a launch: rows_pad >= rows, rows_pad < 2^31,
+ * cols <= 65 535 * 32 (transpose); rows <= 65 535 * 128 (column sums); a NULL or short workspace: MPREID_ERR_WORKSPACE. */
+int mpreid_transpose_pad_f32(const float *src_dev, int64_t rows, int cols, float *dst_dev, int64_t rows_pad, mpreid_stream_t stream);
+size_t mpreid_colsum_workspace_bytes(int64_t rows, int cols);   /* needs no device; 0 for a bad request */
+int mpreid_colsum_f32(const float *dy_dev, const float *x_dev, int64_t rows, int cols, float *out_sum_dev, float *out_sumx_dev,
+                      void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
+
 /* ---- Stage-1 prompt learning (processor/processor_uniprompt_stage1.py:66-100): loss, context gradients, Adam ----
  * Three small fp32 entry points around mpreid_text_forward / mpreid_text_backward.  No atomics and a fixed summation order: the
  * same bits from run to run.  Every output element is written and no other byte; every argument error is found before anything

@@ -259,6 +259,9 @@ int launch_attention_backward(const float *qkv, const float *d_o, int B, int L, 
     return MPREID_OK;
 }
 
+}   // namespace
+
+// (towers.h: the image tower's sweep, csrc/vit_grad.hip, launches these two as well)
 int launch_layernorm_backward(const float *x, const float *dy, const float *g, int64_t rows, int W, bool acc, float *out,
                               hipStream_t s) {
     const dim3 grid((unsigned)((rows + 3) / 4));
@@ -269,6 +272,14 @@ int launch_layernorm_backward(const float *x, const float *dy, const float *g, i
     LAUNCH_CHECK();
     return MPREID_OK;
 }
+
+int launch_quickgelu_backward(const float *u, float *d, int64_t n4, hipStream_t s) {
+    hipLaunchKernelGGL(quickgelu_backward_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, u, d, n4);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
+namespace {
 
 // The backward call's workspace: the forward's regions first (f.x doubles as the block mid-point and f.hbuf as the fp32 FC1
 // pre-activation of the sweep: the same 16 W bytes per row), then the kept block inputs and the gradient buffers
@@ -375,11 +386,7 @@ extern "C" int mpreid_text_backward(const mpreid_text_cfg *cfg, const mpreid_tex
         if ((rc = text_block_recompute(cfg, B, ly, x, a, qkv, u, M, Mpad, stream))) return rc;   // x = x_mid from here on
         // x_{l+1} = x_mid + c_proj(quickgelu(c_fc(ln_2(x_mid))))
         if ((rc = mpreid_gemm_f32_linear(dx, lt.proj_t, M, 4 * W, W, nullptr, dh, 4 * W, F32_LIN, stream))) return rc;
-        {
-            const int64_t n4 = (int64_t)M * W;   // M * 4W / 4
-            hipLaunchKernelGGL(quickgelu_backward_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, u, dh, n4);
-            LAUNCH_CHECK();
-        }
+        if ((rc = launch_quickgelu_backward(u, dh, (int64_t)M * W, stream))) return rc;   // M * 4W / 4 float4
         if ((rc = mpreid_gemm_f32_linear(dh, lt.fc_t, M, W, 4 * W, nullptr, t, W, F32_LIN, stream))) return rc;
         if ((rc = launch_layernorm_backward(x, t, ly.ln2_g, M, W, true, dx, stream))) return rc;   // dx = d/dx_mid
         // x_mid = x_l + out_proj(attention(in_proj(ln_1(x_l))))

@@ -42,6 +42,39 @@ int text_block(const mpreid_text_cfg *cfg, int B, const mpreid_vit_layer &ly, fl
 int text_block_recompute(const mpreid_text_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *qkv,
                          float *u, int M, int Mpad, hipStream_t stream);
 
+// the workspace of mpreid_vit_forward (byte offsets; every region 256-byte aligned)
+struct VitLayout {
+    int L, P, M, Mpad, MPpad, Kp, Bpad;
+    size_t patches, x, a, qkv, hbuf, x_cls, a_cls, h_cls, y_cls, total;
+};
+VitLayout vit_layout(const mpreid_vit_cfg *c, int B);
+int vit_check_cfg(const mpreid_vit_cfg *c);   // MPREID_ERR_ARG / MPREID_ERR_UNSUPPORTED with the error text set
+
+// The image tower's embedded sequence in the split precision, what the forward launches in front of ln_pre: the patch
+// gather into `patches` (fp16 pairs [MPpad][hi(Kp) | lo(Kp)]), conv1 + positional embedding, the CLS row (+ cv_emb).
+// x [Mpad][W] fp32 = ln_pre's input.  `in` has passed mpreid_check_image_in.
+int vit_embed_tokens(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_image_in &in, int B, const float *cv_emb,
+                     const VitLayout &v, _Float16 *patches, float *x, hipStream_t stream);
+// out = LayerNorm(x) in fp32 over `rows` rows of W (layernorm_kernel<0>; out may be x)
+int vit_layernorm_f32(const float *x, int64_t rows, int W, const float *g, const float *b, float *out, hipStream_t stream);
+
+// One unmasked split-precision residual block over all M rows of x, in place (what mpreid_vit_forward runs per layer in
+// front of the tail), and its two halves for the backward sweep, as text_block / text_block_recompute are for the causal
+// tower.  vit_block_attention: qkv = q | k | v of ln_1(x) in fp32, a = the attention output as fp16 pairs [hi(W) | lo(W)];
+// x is not written.  vit_block_mlp_recompute: x += out_proj(a) (the block's mid-point), a = ln_2(x) as pairs,
+// u [Mpad][4W] = the FC1 pre-activation in fp32; FC2 is not run.
+int vit_block(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *qkv, _Float16 *hbuf,
+              int M, int Mpad, hipStream_t stream);
+int vit_block_attention(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer &ly, const float *x, _Float16 *a, float *qkv,
+                        int M, int Mpad, hipStream_t stream);
+int vit_block_mlp_recompute(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *u, int M,
+                            int Mpad, hipStream_t stream);
+
+// text_grad.hip: the kernels the image tower's sweep borrows
+int launch_layernorm_backward(const float *x, const float *dy, const float *g, int64_t rows, int W, bool acc, float *out,
+                              hipStream_t s);
+int launch_quickgelu_backward(const float *u, float *d, int64_t n4, hipStream_t s);
+
 // The head of every tower (vit.hip): LayerNorm of ONE row per item, then that row @ proj.
 //   x        fp32, item b at x + b * row_stride; its row is row 0 (row_of == nullptr: the CLS row) or row_of[b], device data
 //            clamped into [0, L-1] (the text tower's end-of-text row).  Rows are W wide.

@@ -264,12 +264,7 @@ __global__ __launch_bounds__(256) void gather_cls_kernel(const float *__restrict
 // ---------------------------------------------------------------------------------------------
 // host driver
 // ---------------------------------------------------------------------------------------------
-struct VitLayout {
-    int L, P, M, Mpad, MPpad, Kp, Bpad;
-    size_t patches, x, a, qkv, hbuf, x_cls, a_cls, h_cls, y_cls, total;
-};
-
-static VitLayout vit_layout(const mpreid_vit_cfg *c, int B) {
+VitLayout vit_layout(const mpreid_vit_cfg *c, int B) {
     VitLayout v{};
     v.P = c->h_res * c->w_res;
     v.L = v.P + 1;
@@ -295,7 +290,7 @@ static VitLayout vit_layout(const mpreid_vit_cfg *c, int B) {
     return v;
 }
 
-static int vit_check_cfg(const mpreid_vit_cfg *c) {
+int vit_check_cfg(const mpreid_vit_cfg *c) {
     ARG_CHECK(c != nullptr);
     ARG_CHECK(c->width > 0 && c->heads > 0 && c->layers >= 0 && c->out_dim > 0);
     if (c->precision == 2) {   // MPREID_VIT_SPLIT_LNFOLD of rounds 3: see include/mpreid.h
@@ -448,15 +443,66 @@ static int block_mlp_part(const BlockCtx &c, const mpreid_vit_layer &ly, float *
     return linear(c, g, 4 * W, ly.proj_s, GE_BIAS_RES, GE_S_BIAS_RES);
 }
 
+// The embedded sequence, ln_pre's input: patch gather, conv1 (no bias) + positional embedding, the CLS row (+ cv_emb)
+static int vit_embed_tokens_impl(const BlockCtx &ctx, const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w,
+                                 const mpreid_image_in &in, int B, const float *cv_emb, const VitLayout &v, _Float16 *patches,
+                                 float *x) {
+    hipStream_t stream = ctx.stream;
+    const bool split = ctx.split;
+    const int W = cfg->width, L = v.L;
+    const int64_t threads = (int64_t)v.MPpad * (v.Kp / 8);
+    const dim3 grid((unsigned)((threads + 255) / 256));
+#define MPREID_IM2COL(V, S, U)                                                                                         \
+    case (V) * 4 + (S) * 2 + (U):                                                                                      \
+        hipLaunchKernelGGL((im2col_kernel<V, S, U>), grid, dim3(256), 0, stream, in, B, cfg->img_h, cfg->img_w,        \
+                           cfg->patch, cfg->stride, cfg->h_res, cfg->w_res, patches, v.MPpad);                         \
+        break;
+#define MPREID_IM2COL_V(V)                                                                                             \
+    MPREID_IM2COL(V, false, false) MPREID_IM2COL(V, false, true) MPREID_IM2COL(V, true, false) MPREID_IM2COL(V, true, true)
+    switch (in.view * 4 + (split ? 2 : 0) + (in.u8_hwc_dev ? 1 : 0)) {   // (in.view is 0..3: mpreid_check_image_in)
+        MPREID_IM2COL_V(0) MPREID_IM2COL_V(1) MPREID_IM2COL_V(2) MPREID_IM2COL_V(3)
+    }
+#undef MPREID_IM2COL_V
+#undef MPREID_IM2COL
+    LAUNCH_CHECK();
+    GemmArgs g{};
+    g.A = patches;
+    g.W = (const _Float16 *)w->conv_w;
+    g.M = v.MPpad;
+    g.N = W;
+    g.out = x;
+    g.ldo = W;
+    g.aux = w->pos_emb;
+    g.m_valid = B * v.P;
+    g.P = v.P;
+    g.L = L;
+    const int rc = linear(ctx, g, v.Kp, w->conv_s, GE_PATCH, GE_S_PATCH);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cls_token_kernel, dim3((unsigned)B), dim3(256), 0, stream, w->class_emb, w->pos_emb, cv_emb, B, L, W, x);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
+// The three features of the training forward (mpreid_vit_forward_train) in place of `out`: no neck, f | f_proj apart
+struct TrainOut {
+    float *f_last, *f, *f_proj;   // [B][W], [B][W], [B][out_dim]
+};
+
 // moe == nullptr: the dense tower (mpreid_vit_forward).  Otherwise blocks l < moe->moe_layers run the routed MLP.
+// tr != nullptr: the training forward -- the same launches, plus one copy of the B CLS rows in front of the last block.
 static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_moe *moe,
                             const mpreid_image_in *img, int B, const float *cv_emb, float *out, void *ws, size_t ws_bytes,
-                            mpreid_stream_t stream_) {
+                            mpreid_stream_t stream_, const TrainOut *tr = nullptr) {
     int rc = vit_check_cfg(cfg);
     if (rc) return rc;
+    if (tr && (cfg->precision != MPREID_VIT_SPLIT || cfg->layers < 1)) {
+        mpreid_set_error("the training forward runs the dense tower in the split precision with at least one layer "
+                         "(precision %d, layers %d)", cfg->precision, cfg->layers);
+        return MPREID_ERR_UNSUPPORTED;
+    }
     mpreid_image_in in;
     if ((rc = mpreid_check_image_in(img, &in))) return rc;
-    ARG_CHECK(w && out && B > 0 && w->layers);
+    ARG_CHECK(w && (out || tr) && B > 0 && w->layers);
     const VitLayout v = vit_layout(cfg, B);
     const int n_moe = moe ? moe->moe_layers : 0;
     VitMoeLayout vm{};
@@ -487,46 +533,18 @@ static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights 
     const BlockCtx ctx{stream, split, split ? 2 : 1, W, cfg->heads, B, L};
 
     // patch embedding (conv1, no bias) + positional embedding; CLS row; ln_pre
-    {
-        const int64_t threads = (int64_t)v.MPpad * (v.Kp / 8);
-        const dim3 grid((unsigned)((threads + 255) / 256));
-#define MPREID_IM2COL(V, S, U)                                                                                         \
-    case (V) * 4 + (S) * 2 + (U):                                                                                      \
-        hipLaunchKernelGGL((im2col_kernel<V, S, U>), grid, dim3(256), 0, stream, in, B, cfg->img_h, cfg->img_w,        \
-                           cfg->patch, cfg->stride, cfg->h_res, cfg->w_res, patches, v.MPpad);                         \
-        break;
-#define MPREID_IM2COL_V(V)                                                                                             \
-    MPREID_IM2COL(V, false, false) MPREID_IM2COL(V, false, true) MPREID_IM2COL(V, true, false) MPREID_IM2COL(V, true, true)
-        switch (in.view * 4 + (split ? 2 : 0) + (in.u8_hwc_dev ? 1 : 0)) {   // (in.view is 0..3: mpreid_check_image_in)
-            MPREID_IM2COL_V(0) MPREID_IM2COL_V(1) MPREID_IM2COL_V(2) MPREID_IM2COL_V(3)
-        }
-#undef MPREID_IM2COL_V
-#undef MPREID_IM2COL
-        LAUNCH_CHECK();
-        GemmArgs g{};
-        g.A = patches;
-        g.W = (const _Float16 *)w->conv_w;
-        g.M = v.MPpad;
-        g.N = W;
-        g.out = x;
-        g.ldo = W;
-        g.aux = w->pos_emb;
-        g.m_valid = B * v.P;
-        g.P = v.P;
-        g.L = L;
-        rc = linear(ctx, g, v.Kp, w->conv_s, GE_PATCH, GE_S_PATCH);
-        if (rc) return rc;
-        hipLaunchKernelGGL(cls_token_kernel, dim3((unsigned)B), dim3(256), 0, stream, w->class_emb, w->pos_emb, cv_emb,
-                           B, L, W, x);
-        hipLaunchKernelGGL(layernorm_kernel<0>, dim3((unsigned)((v.M + 3) / 4)), dim3(256), 0, stream, x,
-                           (int64_t)v.M, W, w->ln_pre_g, w->ln_pre_b, (void *)x, (int64_t)W);
-        LAUNCH_CHECK();
-    }
+    if ((rc = vit_embed_tokens_impl(ctx, cfg, w, in, B, cv_emb, v, patches, x))) return rc;
+    hipLaunchKernelGGL(layernorm_kernel<0>, dim3((unsigned)((v.M + 3) / 4)), dim3(256), 0, stream, x, (int64_t)v.M, W,
+                       w->ln_pre_g, w->ln_pre_b, (void *)x, (int64_t)W);
+    LAUNCH_CHECK();
     for (int l = 0; l < cfg->layers; ++l) {
         const mpreid_vit_layer &ly = w->layers[l];
         // in the last block only the CLS row reaches the output (model/make_model.py:98-100): the
         // attention runs the first query tile only and everything after it runs on the B CLS rows.
         const bool tail = cls_last && (l == cfg->layers - 1);
+        if (tr && l == cfg->layers - 1)   // f_last: the CLS row of the last block's input (model/clip/model.py:458-468)
+            HIP_TRY(hipMemcpy2DAsync(tr->f_last, (size_t)W * 4, x, (size_t)L * W * 4, (size_t)W * 4, (size_t)B,
+                                     hipMemcpyDeviceToDevice, stream));
         if ((rc = block_attention_part(ctx, ly, x, a, qkv, v.M, v.Mpad, tail ? ATTN_CLS_TILE : ATTN_ALL_ROWS))) return rc;
         if (tail) {   // (never an MoE block)
             hipLaunchKernelGGL(gather_cls_kernel, dim3((unsigned)B), dim3(256), 0, stream, x, a, B, L, W, ctx.pr * W, x_cls, a_cls);
@@ -536,7 +554,20 @@ static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights 
                        : block_mlp_part(ctx, ly, x, a, hbuf, v.M, v.Mpad, moe, l, &vm, base)))
             return rc;
     }
+    if (tr)   // the head's own kernels: the normalised rows land in f (the forward's scratch y), the projection in f_proj
+        return tower_head(cls_last ? x_cls : x, cls_last ? (int64_t)W : (int64_t)L * W, nullptr, 1, B, W, cfg->out_dim,
+                          w->ln_post_g, w->ln_post_b, w->proj, nullptr, nullptr, nullptr, nullptr, tr->f, tr->f_proj, cfg->out_dim,
+                          0, false, stream);
     return image_head(cfg, w, cls_last ? x_cls : x, cls_last ? (int64_t)W : (int64_t)L * W, B, y_cls, out, stream);
+}
+
+extern "C" int mpreid_vit_forward_train(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_image_in *img, int B,
+                                        const float *cv_emb, float *f_last, float *f, float *f_proj, void *ws, size_t ws_bytes,
+                                        mpreid_stream_t stream_) {
+    ARG_CHECK(f_last && f && f_proj);
+    ARG_CHECK((((uintptr_t)f_last | (uintptr_t)f | (uintptr_t)f_proj) & 3) == 0);
+    const TrainOut tr{f_last, f, f_proj};
+    return vit_forward_impl(cfg, w, nullptr, img, B, cv_emb, nullptr, ws, ws_bytes, stream_, &tr);
 }
 
 extern "C" int mpreid_vit_forward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_image_in *img, int B,
@@ -706,4 +737,37 @@ int text_block_recompute(const mpreid_text_cfg *cfg, int B, const mpreid_vit_lay
     const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, cfg->tokens};
     const int rc = block_attention_part(ctx, ly, x, a, qkv, M, Mpad, ATTN_CAUSAL);
     return rc ? rc : block_mlp_part(ctx, ly, x, a, nullptr, M, Mpad, nullptr, 0, nullptr, nullptr, u);
+}
+
+// the unmasked tower's entry points for the backward sweep (towers.h; csrc/vit_grad.hip)
+int vit_embed_tokens(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_image_in &in, int B, const float *cv_emb,
+                     const VitLayout &v, _Float16 *patches, float *x, hipStream_t stream) {
+    const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, v.L};
+    return vit_embed_tokens_impl(ctx, cfg, w, in, B, cv_emb, v, patches, x);
+}
+
+int vit_layernorm_f32(const float *x, int64_t rows, int W, const float *g, const float *b, float *out, hipStream_t stream) {
+    hipLaunchKernelGGL(layernorm_kernel<0>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, rows, W, g, b, (void *)out,
+                       (int64_t)W);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
+int vit_block(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *qkv, _Float16 *hbuf,
+              int M, int Mpad, hipStream_t stream) {
+    const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, cfg->h_res * cfg->w_res + 1};
+    const int rc = block_attention_part(ctx, ly, x, a, qkv, M, Mpad, ATTN_ALL_ROWS);
+    return rc ? rc : block_mlp_part(ctx, ly, x, a, hbuf, M, Mpad, nullptr, 0, nullptr, nullptr);
+}
+
+int vit_block_attention(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer &ly, const float *x, _Float16 *a, float *qkv,
+                        int M, int Mpad, hipStream_t stream) {
+    const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, cfg->h_res * cfg->w_res + 1};
+    return block_attention_part(ctx, ly, x, a, qkv, M, Mpad, ATTN_ALL_ROWS);
+}
+
+int vit_block_mlp_recompute(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *u, int M,
+                            int Mpad, hipStream_t stream) {
+    const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, cfg->h_res * cfg->w_res + 1};
+    return block_mlp_part(ctx, ly, x, a, nullptr, M, Mpad, nullptr, 0, nullptr, nullptr, u);
 }

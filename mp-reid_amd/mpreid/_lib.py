@@ -87,6 +87,26 @@ class TextWeightsT(C.Structure):
     _fields_ = [("proj_t", C.c_void_p), ("layers", C.POINTER(TextLayerT))]
 
 
+class VitWeightsT(C.Structure):
+    """mpreid_vit_weights_t: per block the fp32 [in][out] copies of its four matrices (TextLayerT's layout)"""
+    _fields_ = [("layers", C.POINTER(TextLayerT))]
+
+
+VIT_LAYER_GRADS = ("in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "fc_w", "fc_b", "proj_w", "proj_b", "ln1_g", "ln1_b",
+                   "ln2_g", "ln2_b")
+VIT_TOWER_GRADS = ("conv_w", "class_emb", "pos_emb", "ln_pre_g", "ln_pre_b", "ln_post_g", "ln_post_b", "proj", "cv_emb")
+
+
+class VitLayerGrads(C.Structure):
+    """mpreid_vit_layer_grads: fp32 device pointers in torch layout, NULL = not wanted"""
+    _fields_ = [(k, C.c_void_p) for k in VIT_LAYER_GRADS]
+
+
+class VitGrads(C.Structure):
+    """mpreid_vit_grads"""
+    _fields_ = [(k, C.c_void_p) for k in VIT_TOWER_GRADS] + [("layers", C.POINTER(VitLayerGrads))]
+
+
 class ImageIn(C.Structure):
     """mpreid_image_in: the image batch of every encoder forward; exactly one of the two pointers is non-NULL"""
     _fields_ = [("f32_dev", C.c_void_p), ("u8_hwc_dev", C.c_void_p), ("mean", C.c_float * 3), ("std", C.c_float * 3),
@@ -229,6 +249,19 @@ PROTOTYPES = {
     "mpreid_text_backward": (i32, [P(TextCfg), P(TextWeights), P(TextWeightsT), vp, vp, vp, i32, vp, vp, sz, vp]),
     "mpreid_text_attention_backward": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "mpreid_layernorm_backward_f32": (i32, [vp, vp, vp, i64, i32, i32, vp, vp]),
+    # the image tower's gradient: the training forward (cfg, weights, image batch, B, cv_emb, f_last, f, f_proj, workspace,
+    # workspace bytes, stream) and the unmasked attention gradient (qkv, d_o, B, tokens, width, heads, d_qkv, workspace, bytes, stream)
+    "mpreid_vit_forward_train": (i32, [P(VitCfg), P(VitWeights), P(ImageIn), i32, vp, vp, vp, vp, vp, sz, vp]),
+    "mpreid_vit_attention_backward_workspace_bytes": (sz, [i32, i32, i32]),
+    "mpreid_vit_attention_backward": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
+    # the sweep (cfg, weights, transposed weights, image batch, B, cv_emb, d_f_last, d_f, d_f_proj, grads, d_tokens, workspace,
+    # workspace bytes, stream) and its two small kernels alone
+    "mpreid_vit_backward_workspace_bytes": (sz, [P(VitCfg), i32]),
+    "mpreid_vit_backward": (i32, [P(VitCfg), P(VitWeights), P(VitWeightsT), P(ImageIn), i32, vp, vp, vp, vp, P(VitGrads), vp, vp,
+                                  sz, vp]),
+    "mpreid_transpose_pad_f32": (i32, [vp, i64, i32, vp, i64, vp]),
+    "mpreid_colsum_workspace_bytes": (sz, [i64, i32]),
+    "mpreid_colsum_f32": (i32, [vp, vp, i64, i32, vp, vp, vp, sz, vp]),
     # stage-1 prompt learning: the contrastive loss pair with its gradients, the context gradient, the Adam / AdamW step
     "mpreid_supcon_workspace_bytes": (sz, [i32, i32]),
     "mpreid_supcon_pair_f32": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]),

@@ -25,7 +25,7 @@ OBJ = os.path.join(os.path.join(os.path.dirname(HERE), "csrc"), "_obj" + ("_" + 
 _REPO = os.path.dirname(os.path.dirname(HERE))
 LIB = (os.path.join(_REPO, "tools", "ablation_lib", "libmpreid_hip_" + _TAG + ".so") if _TAG
        else os.path.join(HERE, "libmpreid_hip.so"))
-SOURCES = ["api.cpp", "distance.hip", "rerank.hip", "gemm_f16.hip", "vit.hip", "attention.hip", "text.hip", "text_grad.hip", "prompt_train.hip", "stage2_head.hip", "moe.hip", "evalrank.hip", "ranklist.hip", "qexpand.hip", "pairstats.hip", "preprocess.hip", "conv_f16.hip", "rn50.hip", "rn50_f32.hip"]
+SOURCES = ["api.cpp", "distance.hip", "rerank.hip", "gemm_f16.hip", "vit.hip", "attention.hip", "text.hip", "text_grad.hip", "vit_grad.hip", "prompt_train.hip", "stage2_head.hip", "moe.hip", "evalrank.hip", "ranklist.hip", "qexpand.hip", "pairstats.hip", "preprocess.hip", "conv_f16.hip", "rn50.hip", "rn50_f32.hip"]
 # -ffp-contract=off: the rounding sequence of the re-ranking path is part of the contract
 # (include/mpreid_numerics.h); fused multiply-adds are written as explicit fmaf().
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
@@ -38,8 +38,10 @@ if os.environ.get("MPREID_ABLATION"):
 # The transformer towers (vit.hip, and attention.hip / text.hip that were split off it: the three share ONE flag set, or
 # the moved kernels compile differently) are floating-point kernels with a stated tolerance: assuming finite values there
 # removes the NaN-canonicalising v_max before every fmaxf.  (distance.hip / rerank.hip keep strict IEEE semantics.)
+# vit_grad.hip (the image tower's gradient kernels) takes the same set.
 _ENCODER_FLAGS = ["-ffinite-math-only", "-fno-signed-zeros"]
-EXTRA_FLAGS = {"vit.hip": _ENCODER_FLAGS, "attention.hip": _ENCODER_FLAGS, "text.hip": _ENCODER_FLAGS}
+EXTRA_FLAGS = {"vit.hip": _ENCODER_FLAGS, "attention.hip": _ENCODER_FLAGS, "text.hip": _ENCODER_FLAGS,
+               "vit_grad.hip": _ENCODER_FLAGS}
 
 
 def _deps(src):

@@ -643,6 +643,25 @@ _TOWERS = {
 
 
 @torch.no_grad()
+def _stage_images(enc, img, u8: bool, view: int, cv_emb, pixel_mean, pixel_std):
+    """An image batch as every tower entry point takes it -> (img on enc's device, cv_emb on it or None, the ImageIn
+    descriptor pointing at the whole batch): fp32 [B,3,H,W], or, u8, uint8 [B,H,W,3]; cv_emb None or [B, width]"""
+    if u8:
+        img = img.detach().to(device=enc.device, dtype=torch.uint8).contiguous()
+        assert tuple(img.shape[1:]) == enc.img_hw + (3,), img.shape
+    else:
+        img = _dev_f32(img, enc.device)
+        assert tuple(img.shape[1:]) == (3,) + enc.img_hw, img.shape
+    cv = None
+    if cv_emb is not None:
+        cv = _dev_f32(cv_emb, enc.device)
+        assert tuple(cv.shape) == (img.shape[0], enc.cfg["width"]), cv.shape
+    desc = _lib.ImageIn(mean=(C.c_float * 3)(*[float(x) for x in pixel_mean]),
+                        std=(C.c_float * 3)(*[float(x) for x in pixel_std]), view=int(view))
+    desc.f32_dev, desc.u8_hwc_dev = (None, img.data_ptr()) if u8 else (img.data_ptr(), None)
+    return img, cv, desc
+
+
 def _forward_images(enc, img, u8: bool, view: int = 0, cv_emb=None, pixel_mean=(0.5, 0.5, 0.5), pixel_std=(0.5, 0.5, 0.5),
                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The one path from an image batch to a tower: img is fp32 [B,3,H,W] (val_transforms applied) or, u8, uint8 [B,H,W,3]
@@ -650,22 +669,11 @@ def _forward_images(enc, img, u8: bool, view: int = 0, cv_emb=None, pixel_mean=(
     cv_emb: None or [B, width] (ViT only).  Validates, stages on enc's device, runs the tower chunk by chunk into out."""
     L = _lib.load()
     fwd, ws_query, weights, tag, step = _TOWERS[enc.tower, enc.precision]
-    if u8:
-        img = img.detach().to(device=enc.device, dtype=torch.uint8).contiguous()
-        assert tuple(img.shape[1:]) == enc.img_hw + (3,), img.shape
-    else:
-        img = _dev_f32(img, enc.device)
-        assert tuple(img.shape[1:]) == (3,) + enc.img_hw, img.shape
+    img, cv, desc = _stage_images(enc, img, u8, view, cv_emb, pixel_mean, pixel_std)
     B = img.shape[0]
-    cv = None
-    if cv_emb is not None:
-        cv = _dev_f32(cv_emb, enc.device)
-        assert tuple(cv.shape) == (B, enc.cfg["width"]), cv.shape
     if out is None:
         out = torch.empty((B, enc.feat_dim), dtype=torch.float32, device=enc.device)
     assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, enc.feat_dim)
-    desc = _lib.ImageIn(mean=(C.c_float * 3)(*[float(x) for x in pixel_mean]),
-                        std=(C.c_float * 3)(*[float(x) for x in pixel_std]), view=int(view))
     moe_arg = []
     if getattr(enc, "c_moe", None) is not None:   # the MoE image tower: its own entry points, the MoE description behind the weights
         fwd, ws_query, tag, moe_arg = "mpreid_vit_forward_moe", "mpreid_vit_workspace_bytes_moe", "_moe", [C.byref(enc.c_moe)]
@@ -824,7 +832,8 @@ class VitEncoder:
         self.img_hw = tuple(img_hw)
         dev = self.device
 
-        get = _state_getter(state_dict, "image_encoder.")
+        get = self._get = _state_getter(state_dict, "image_encoder.")
+        self.masters = None   # enable_training()
 
         def f32(name, shape=None):   # (shapes are not checked here: the library's own checks and the asserts below)
             return get(name).to(device=dev, dtype=torch.float32).contiguous()
@@ -921,12 +930,177 @@ class VitEncoder:
             self.forward_view(img, v, cv_emb, pixel_mean, pixel_std, out=feats[i])
         return tta_mean(feats, normalize)
 
+    @torch.no_grad()
+    def forward_train(self, img: torch.Tensor, cv_emb: Optional[torch.Tensor] = None, view: int = VIEW_ORIGINAL,
+                      pixel_mean=(0.5, 0.5, 0.5), pixel_std=(0.5, 0.5, 0.5)):
+        """The three features stage 2 differentiates (mpreid_vit_forward_train) -> (f_last [B, width], f [B, width],
+        f_proj [B, out_dim]): the CLS row of the last block's input, ln_post of the CLS row, and that @ proj; no BatchNorm neck
+        (Stage2Head owns BNNeck).  f | f_proj carries the bits of forward() of an encoder without a neck.  img as forward_view
+        takes it: fp32 [B,3,H,W] or uint8 [B,H,W,3], any view -- pixels are data, there is no pixel gradient.  The dense tower
+        in the split precision only."""
+        if self.precision != "split" or self.c_moe is not None:
+            raise NotImplementedError("forward_train: the dense ViT tower in the split precision only (no MoE, fp16 or fp32 tower)")
+        L = _lib.load()
+        img, cv, desc = _stage_images(self, img, img.dtype == torch.uint8, view, cv_emb, pixel_mean, pixel_std)
+        B, w = img.shape[0], self.cfg["width"]
+        f_last, f = (torch.empty((B, w), dtype=torch.float32, device=self.device) for _ in range(2))
+        f_proj = torch.empty((B, self.cfg["out_dim"]), dtype=torch.float32, device=self.device)
+        ws = _workspace(self.ws_tag, L.mpreid_vit_workspace_bytes(C.byref(self.c_cfg), B), self.device)
+        _lib.check(L.mpreid_vit_forward_train(C.byref(self.c_cfg), C.byref(self.c_w), C.byref(desc), B, _ptr(cv), _ptr(f_last),
+                                              _ptr(f), _ptr(f_proj), _ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "mpreid_vit_forward_train")
+        return f_last, f, f_proj
+
+    # ---- training (include/mpreid.h "The image tower's gradient") ----
+    _LAYER_KEYS = dict(in_proj_w="attn.in_proj_weight", in_proj_b="attn.in_proj_bias", out_proj_w="attn.out_proj.weight",
+                       out_proj_b="attn.out_proj.bias", fc_w="mlp.c_fc.weight", fc_b="mlp.c_fc.bias", proj_w="mlp.c_proj.weight",
+                       proj_b="mlp.c_proj.bias", ln1_g="ln_1.weight", ln1_b="ln_1.bias", ln2_g="ln_2.weight", ln2_b="ln_2.bias")
+    _TOWER_KEYS = dict(conv_w="conv1.weight", class_emb="class_embedding", pos_emb="positional_embedding",
+                       ln_pre_g="ln_pre.weight", ln_pre_b="ln_pre.bias", ln_post_g="ln_post.weight", ln_post_b="ln_post.bias",
+                       proj="proj")
+
+    def _param_fields(self):
+        """(reference key name, layer index or None, struct field) of every trained parameter, in a fixed order"""
+        out = [(key, None, field) for field, key in self._TOWER_KEYS.items()]
+        for i in range(self.cfg["layers"]):
+            out += [(f"transformer.resblocks.{i}.{key}", i, field) for field, key in self._LAYER_KEYS.items()]
+        return out
+
+    def _check_trainable(self, what: str):
+        if self.precision != "split" or self.c_moe is not None:
+            raise NotImplementedError(f"{what}: the dense ViT tower in the split precision only (no MoE, fp16 or fp32 tower)")
+        if self.cfg["layers"] < 1:
+            raise NotImplementedError(f"{what}: a tower of at least one layer")
+
+    def enable_training(self):
+        """fp32 master copies of every parameter as device tensors (leaves that require grad) in self.masters, under the
+        reference's checkpoint key names and in its shapes; the split pairs the forward reads and the transposed fp32 copies
+        [in][out] the gradient GEMMs read are rebuilt from them by sync_weights().  Returns self.masters."""
+        self._check_trainable("enable_training")
+        if self.masters is None:
+            self.masters = {key: self._get(key).to(device=self.device, dtype=torch.float32).contiguous().clone().requires_grad_(True)
+                            for key, _, _ in self._param_fields()}
+            self._pairs, self._wt = {}, {}
+            self._layers_t = (_lib.TextLayerT * self.cfg["layers"])()
+            self.c_wt = _lib.VitWeightsT(C.cast(self._layers_t, C.POINTER(_lib.TextLayerT)))
+            self.sync_weights()
+        return self.masters
+
+    @torch.no_grad()
+    def sync_weights(self):
+        """Re-packs the forward's fp16 pairs and the transposed copies from the masters (after an optimizer step on them) and
+        points the library's structs at the masters' vectors.  Reading each matrix's largest entry back for the pair's
+        power-of-two scale synchronises with the device once per matrix."""
+        L = _lib.load()
+        for key, i, field in self._param_fields():
+            m = self.masters[key]
+            assert m.is_contiguous() and m.dtype == torch.float32 and m.device == self.device, key
+            target = self.c_w if i is None else self._layers[i]
+            if field.endswith("_w"):   # a GEMM weight: conv_w and the four matrices of a block
+                m2 = m.detach().reshape(m.shape[0], -1)
+                pair, scale, _ = _split_pack(m2, out=self._pairs.get(key))
+                self._pairs[key] = pair
+                setattr(target, field, pair.data_ptr())
+                setattr(target, field[:-2] + "_s" if i is not None else "conv_s", scale)
+                if i is not None:
+                    n, k = m2.shape
+                    if key not in self._wt:
+                        self._wt[key] = torch.empty((k, n), dtype=torch.float32, device=self.device)
+                    _lib.check(L.mpreid_transpose_pad_f32(_ptr(m2), n, k, _ptr(self._wt[key]), n, _lib.stream_ptr()),
+                               "mpreid_transpose_pad_f32")
+                    setattr(self._layers_t[i], field[:-2] + "_t", self._wt[key].data_ptr())
+            else:
+                setattr(target, field, m.data_ptr())
+        torch.cuda.current_stream().synchronize()
+
+    @torch.no_grad()
+    def backward(self, img: torch.Tensor, cv_emb: Optional[torch.Tensor], d_f_last: Optional[torch.Tensor],
+                 d_f: Optional[torch.Tensor], d_f_proj: Optional[torch.Tensor], want=None, view: int = VIEW_ORIGINAL,
+                 pixel_mean=(0.5, 0.5, 0.5), pixel_std=(0.5, 0.5, 0.5), out: Optional[dict] = None):
+        """The gradients of sum(f_last o d_f_last) + sum(f o d_f) + sum(f_proj o d_f_proj) over forward_train's features
+        (mpreid_vit_backward; a None seed is zero) -> {reference key name: fp32 gradient in the checkpoint's shape}.  want: the
+        names to compute (default: every parameter, and "cv_emb" when cv_emb is given); "cv_emb" [B, width] is the gradient of
+        the cv_emb rows as given, "tokens" [B, L, width] that of the embedded sequence.  Names left out cost nothing.
+        out: optional {name: a contiguous fp32 device tensor of the gradient's shape} to write into (it may be a view into a
+        larger buffer).  The call re-runs the forward itself; img as forward_train takes it (pixels are data: there is no
+        pixel gradient)."""
+        self._check_trainable("backward")
+        if self.masters is None:
+            raise RuntimeError("backward: call enable_training() first")
+        L = _lib.load()
+        img, cv, desc = _stage_images(self, img, img.dtype == torch.uint8, view, cv_emb, pixel_mean, pixel_std)
+        B, w, od = img.shape[0], self.cfg["width"], self.cfg["out_dim"]
+        fields = self._param_fields()
+        if want is None:
+            want = [key for key, _, _ in fields] + (["cv_emb"] if cv is not None else [])
+        want = list(want)
+        known = {key for key, _, _ in fields} | {"cv_emb", "tokens"}
+        for name in want:
+            if name not in known:
+                raise KeyError(f"backward: no gradient named {name!r}")
+        if "cv_emb" in want and cv is None:
+            raise ValueError("backward: the gradient of cv_emb was asked for and no cv_emb given")
+        seeds = []
+        for t, dim, what in ((d_f_last, w, "d_f_last"), (d_f, w, "d_f"), (d_f_proj, od, "d_f_proj")):
+            if t is not None:
+                t = _dev_f32(t, self.device)
+                if tuple(t.shape) != (B, dim):
+                    raise ValueError(f"{what}: expected [{B}, {dim}], got {tuple(t.shape)}")
+            seeds.append(t)
+        given, out = out or {}, {}
+        n_tok = self.cfg["h_res"] * self.cfg["w_res"] + 1
+        shapes = {key: tuple(self.masters[key].shape) for key, _, _ in fields}
+        shapes.update(cv_emb=(B, w), tokens=(B, n_tok, w))
+        for name in want:
+            out[name] = _f32_buffer(given.get(name), shapes[name], self.device, name)
+        lg = (_lib.VitLayerGrads * self.cfg["layers"])()
+        g = _lib.VitGrads()
+        g.layers = C.cast(lg, C.POINTER(_lib.VitLayerGrads))
+        for key, i, field in fields:
+            if key in want:
+                setattr(g if i is None else lg[i], field, out[key].data_ptr())
+        if "cv_emb" in want:
+            g.cv_emb = out["cv_emb"].data_ptr()
+        ws = _workspace(self.ws_tag + "_grad", L.mpreid_vit_backward_workspace_bytes(C.byref(self.c_cfg), B), self.device)
+        _lib.check(L.mpreid_vit_backward(C.byref(self.c_cfg), C.byref(self.c_w), C.byref(self.c_wt), C.byref(desc), B, _ptr(cv),
+                                         _ptr(seeds[0]), _ptr(seeds[1]), _ptr(seeds[2]), C.byref(g), _ptr(out.get("tokens")),
+                                         _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_vit_backward")
+        return out
+
+    def forward_grad(self, img: torch.Tensor, cv_emb: Optional[torch.Tensor] = None, view: int = VIEW_ORIGINAL,
+                     pixel_mean=(0.5, 0.5, 0.5), pixel_std=(0.5, 0.5, 0.5)):
+        """forward_train as a node of torch's autograd graph -> (f_last, f, f_proj), differentiable in self.masters and in
+        cv_emb (not in the pixels): its backward is backward() with the incoming gradients, so torch.optim.* can drive the
+        masters; call sync_weights() after each optimizer step."""
+        self._check_trainable("forward_grad")
+        if self.masters is None:
+            raise RuntimeError("forward_grad: call enable_training() first")
+        keys = [key for key, _, _ in self._param_fields()]
+        return _VitForwardGrad.apply(self, img, (view, pixel_mean, pixel_std), keys, cv_emb, *[self.masters[k] for k in keys])
+
     def clone_for_stream(self, ws_tag: str) -> "VitEncoder":
         """a second handle on the same device weights with its own workspace (for a second HIP stream)"""
         import copy
         other = copy.copy(self)
         other.ws_tag = ws_tag
         return other
+
+
+class _VitForwardGrad(torch.autograd.Function):
+    """VitEncoder.forward_grad"""
+
+    @staticmethod
+    def forward(ctx, enc, img, how, keys, cv_emb, *masters):
+        ctx.enc, ctx.img, ctx.how, ctx.keys = enc, img, how, keys
+        ctx.cv = None if cv_emb is None else cv_emb.detach()
+        return enc.forward_train(img, ctx.cv, *how)
+
+    @staticmethod
+    def backward(ctx, d_f_last, d_f, d_f_proj):
+        need = ctx.needs_input_grad   # (enc, img, how, keys, cv_emb, *masters)
+        want = [k for k, n in zip(ctx.keys, need[5:]) if n] + (["cv_emb"] if need[4] else [])
+        g = ctx.enc.backward(ctx.img, ctx.cv, d_f_last, d_f, d_f_proj, want, *ctx.how)
+        return (None, None, None, None, g.get("cv_emb")) + tuple(g.get(k) for k in ctx.keys)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1094,6 +1268,27 @@ def vit_attention_f32(qkv: torch.Tensor, batch: int, tokens: int, heads: int, ou
     assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (batch * tokens, width)
     _lib.check(_lib.load().mpreid_vit_attention_f32(_ptr(qkv), int(batch), int(tokens), width, int(heads), _ptr(out),
                                                     _lib.stream_ptr()), "mpreid_vit_attention_f32")
+    return out
+
+
+def vit_attention_backward(qkv: torch.Tensor, d_o: torch.Tensor, batch: int, tokens: int, heads: int,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the image tower's unmasked attention gradient alone (mpreid_vit_attention_backward).  qkv: fp32 [batch * tokens, 3 * width]
+    in the column layout of vit_attention, d_o: fp32 [batch * tokens, width] -> dq | dk | dv, fp32 [batch * tokens, 3 * width];
+    `out` may be a view into a larger buffer (the tests put guard rows around it).  2 <= tokens <= MPREID_VIT_MAX_TOKENS."""
+    dev = _lib.require_gpu()
+    width = 64 * heads
+    assert qkv.is_cuda and qkv.is_contiguous() and tuple(qkv.shape) == (batch * tokens, 3 * width)
+    assert d_o.is_cuda and d_o.is_contiguous() and tuple(d_o.shape) == (batch * tokens, width)
+    if qkv.dtype != torch.float32 or d_o.dtype != torch.float32:
+        raise RuntimeError(f"mpreid_vit_attention_backward failed (code {_lib.ERR_UNSUPPORTED}): gradients are fp32 only")
+    if out is None:
+        out = torch.empty((batch * tokens, 3 * width), dtype=torch.float32, device=qkv.device)
+    assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (batch * tokens, 3 * width)
+    L = _lib.load()
+    ws = _workspace("vit_attention_backward", L.mpreid_vit_attention_backward_workspace_bytes(int(batch), int(tokens), int(heads)), dev)
+    _lib.check(L.mpreid_vit_attention_backward(_ptr(qkv), _ptr(d_o), int(batch), int(tokens), width, int(heads), _ptr(out),
+                                               _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_vit_attention_backward")
     return out
 
 

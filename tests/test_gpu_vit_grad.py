@@ -1,0 +1,439 @@
+"""The image tower's gradient work on the GPU: the unmasked attention gradient (mpreid_vit_attention_backward) against
+float64 autograd at every token count of vit_grad_cases, its memory discipline and bits; the training forward
+(mpreid_vit_forward_train) bit for bit against the forward, f_last against float64; the transposing and column-reduction
+kernels bit for bit; the sweep (mpreid_vit_backward) with every parameter gradient against float64 autograd, its bits, NULL
+members, forward_grad under torch.autograd and 20 SGD steps against float64; limits and errors.  Oracles: tests/vit_grad_cases.py."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import text_cases as tc
+import text_grad_cases as tg
+import vit_grad_cases as vg
+from mpreid import _lib, ops
+
+pytestmark = pytest.mark.gpu
+
+ATT_CASES = [(w, h, t, vg.ATT_BATCH) for w, h in vg.ATT_SHAPES for t in vg.ATT_TOKENS] + [vg.ATT_MAX]
+
+
+# ---- 1. the attention gradient against float64 -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("width,heads,tokens,batch", ATT_CASES)
+def test_attention_backward_against_float64(width, heads, tokens, batch):
+    """slab-relative error of dq | dk | dv (text_grad_cases.grad_figure) <= 2e-5; fp32 autograd on the host is printed beside it.
+    At two tokens the slab (image 0, head 0) is saturated (test_vit_grad_cpu.py): the plain form of dS has no digits there.
+    Measured on an MI355X over the 27 cases: largest 2.2e-6 ((768, 12), L = 2), 5.7e-7 .. 1.9e-6 elsewhere; fp32 autograd on the
+    host 2.9e-7 .. 1.5e-6, and 0.95 / 0.98 at L = 2"""
+    qkv, d_o, want = vg.attention_grad_case(width, heads, tokens, batch)
+    got = ops.vit_attention_backward(qkv.cuda(), d_o.cuda(), batch, tokens, heads)
+    assert bool(torch.isfinite(got).all())
+    fig = tg.grad_figure(got, want, batch, heads)
+    host = tg.grad_figure(tg.attention_grad(qkv, d_o, batch, heads, vg.all_keys(tokens), dtype=torch.float32), want, batch, heads)
+    print("vit attention backward (%d, %d) L = %d: %.3e; fp32 autograd on the host %.3e, ratio %.2f"
+          % (width, heads, tokens, fig, host, fig / host if host else float("inf")))
+    assert fig <= vg.BOUND
+
+
+# ---- 2. memory discipline and bits -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tokens", [3, 65, 129, 257])
+def test_attention_backward_writes_d_qkv_and_nothing_else(tokens):
+    """qkv and d_o are followed by NaN guard rows in their allocations, d_qkv lies between sentinel guard rows: finite results,
+    every element of d_qkv written, every guard byte untouched; a second call gives the same bits"""
+    width, heads = 128, 2
+    B, G = vg.ATT_BATCH, 32
+    qkv, d_o, want = vg.attention_grad_case(width, heads, tokens)
+    M = B * tokens
+    buf = torch.full((M + G, 3 * width), float("nan"), dtype=torch.float32, device="cuda")
+    buf[:M] = qkv.cuda()
+    gbuf = torch.full((M + G, width), float("nan"), dtype=torch.float32, device="cuda")
+    gbuf[:M] = d_o.cuda()
+    sentinel = 0x7FC12345   # a NaN pattern
+    obuf = torch.full((G + M + G, 3 * width), sentinel, dtype=torch.int32, device="cuda")
+    out = obuf[G:G + M].view(torch.float32)
+    ops.vit_attention_backward(buf[:M], gbuf[:M], B, tokens, heads, out=out)
+    torch.cuda.synchronize()
+    assert bool((obuf[:G] == sentinel).all()) and bool((obuf[G + M:] == sentinel).all())
+    assert bool(torch.isnan(buf[M:]).all()) and bool(torch.isnan(gbuf[M:]).all())
+    assert bool(torch.isfinite(out).all())
+    assert tg.grad_figure(out, want, B, heads) <= vg.BOUND
+    again = ops.vit_attention_backward(buf[:M], gbuf[:M], B, tokens, heads)
+    assert torch.equal(again.view(torch.int32), out.view(torch.int32))
+
+
+@pytest.mark.parametrize("tokens", [2, 129, 258])
+def test_attention_backward_batch_independence_homogeneity_and_zeros(tokens):
+    """an image alone has the bits it has in the batch of three; d_o scaled by 2^-40 scales the bits; an all-zero d_o gives
+    exact zeros"""
+    width, heads = 128, 2
+    B = vg.ATT_BATCH
+    qkv, d_o, _ = vg.attention_grad_case(width, heads, tokens)
+    q, g = qkv.cuda(), d_o.cuda()
+    full = ops.vit_attention_backward(q, g, B, tokens, heads).clone()
+    for i in range(B):
+        rows = slice(i * tokens, (i + 1) * tokens)
+        alone = ops.vit_attention_backward(q[rows].contiguous(), g[rows].contiguous(), 1, tokens, heads)
+        assert torch.equal(alone.view(torch.int32), full[rows].view(torch.int32)), i
+    s = 2.0 ** -40
+    scaled = ops.vit_attention_backward(q, g * s, B, tokens, heads)
+    assert torch.equal(scaled.view(torch.int32), (full * s).view(torch.int32))
+    zero = ops.vit_attention_backward(q, torch.zeros_like(g), B, tokens, heads)
+    assert bool((zero == 0.0).all())
+
+
+# ---- 3. the training forward -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(vg.TOWER_CASES))
+def test_forward_train_has_the_forward_s_bits_and_f_last_within_the_bound(name):
+    """f | f_proj bit-equal to forward() of an encoder without a neck, with cls_only_last off and on; the three features within
+    2e-5 (relative L2) of the float64 restatement"""
+    cfg, img_hw, sd, imgs, cv, want = vg.tower_case(name)
+    img, cv_d = torch.from_numpy(imgs).cuda(), torch.from_numpy(cv).cuda()
+    last = []
+    for cls_only in (False, True):
+        enc = ops.VitEncoder(cfg, sd, img_hw, cls_only_last=cls_only, ws_tag="vitgrad_%s_%d" % (name, cls_only))
+        for cv_arg in (cv_d, None):
+            out = enc.forward(img, cv_arg).clone()
+            f_last, f, f_proj = enc.forward_train(img, cv_arg)
+            assert torch.equal(torch.cat([f, f_proj], dim=1).view(torch.int32), out.view(torch.int32)), (cls_only, cv_arg is None)
+        for got, ref, what in zip((f_last, f, f_proj), vg.tower(cfg, vg.weights(sd), tc._t64(imgs), None), ("f_last", "f", "f_proj")):
+            fig = tc.rel_l2(got, ref.detach())
+            print("forward_train %s cls_only_last %d: %s rel L2 %.3e against float64" % (name, cls_only, what, fig))
+            assert fig <= vg.BOUND, what
+        last.append(f_last.clone())
+        f_last, f, f_proj = enc.forward_train(img, cv_d)
+        for got, ref, what in zip((f_last, f, f_proj), want, ("f_last", "f", "f_proj")):
+            assert tc.rel_l2(got, ref) <= vg.BOUND, what
+        # uint8 input and a view are accepted as the forward accepts them
+        u8 = ((img.permute(0, 2, 3, 1) * 0.5 + 0.5) * 255).round().clamp(0, 255).to(torch.uint8).contiguous()
+        out = enc.forward_view(u8, ops.VIEW_FLIP, cv_d).clone()
+        _, f, f_proj = enc.forward_train(u8, cv_d, view=ops.VIEW_FLIP)
+        assert torch.equal(torch.cat([f, f_proj], dim=1), out)
+    assert torch.equal(last[0], last[1])   # f_last does not depend on how the tail block is run
+
+
+# ---- 4. limits and errors ---------------------------------------------------------------------------------------------------------
+def test_limits_and_errors_leave_the_next_call_intact():
+    width, heads, tokens = 128, 2, 65
+    qkv, d_o, want = vg.attention_grad_case(width, heads, tokens)
+    q, g = qkv.cuda(), d_o.cuda()
+    B = vg.ATT_BATCH
+
+    def good():
+        assert tg.grad_figure(ops.vit_attention_backward(q, g, B, tokens, heads), want, B, heads) <= vg.BOUND
+
+    good()
+    with pytest.raises(RuntimeError, match="code %d" % _lib.ERR_UNSUPPORTED):
+        ops.vit_attention_backward(q.half(), g, B, tokens, heads)
+    L = _lib.load()
+    out = torch.empty_like(q)
+    need = L.mpreid_vit_attention_backward_workspace_bytes(B, tokens, heads)
+    ws = torch.empty(need + 256, dtype=torch.uint8, device="cuda")
+
+    def call(qkv_ptr=q.data_ptr(), tok=tokens, ws_ptr=ws.data_ptr(), ws_bytes=need, h=heads):
+        return L.mpreid_vit_attention_backward(qkv_ptr, g.data_ptr(), B, tok, width, h, out.data_ptr(), ws_ptr, ws_bytes,
+                                               _lib.stream_ptr())
+    assert call(ws_bytes=need - 1) == _lib.ERR_WORKSPACE
+    good()
+    assert call(qkv_ptr=q.data_ptr() + 4) == _lib.ERR_ARG and call(qkv_ptr=None) == _lib.ERR_ARG
+    assert call(ws_ptr=ws.data_ptr() + 8) == _lib.ERR_ARG
+    assert call(tok=1) == _lib.ERR_UNSUPPORTED and call(tok=1026) == _lib.ERR_UNSUPPORTED and call(h=4) == _lib.ERR_UNSUPPORTED
+    good()
+    assert call() == 0
+    torch.cuda.synchronize()
+    assert tg.grad_figure(out, want, B, heads) <= vg.BOUND
+    # the training forward: an fp16 tower and a tower without a layer are refused, the next call is intact
+    cfg, img_hw, sd, imgs, cv, ref = vg.tower_case("two_layers")
+    img = torch.from_numpy(imgs).cuda()
+    with pytest.raises(NotImplementedError):
+        ops.VitEncoder(cfg, sd, img_hw, precision="fp16", ws_tag="vitgrad_f16").forward_train(img)
+    with pytest.raises(NotImplementedError):
+        ops.VitEncoder(cfg, sd, img_hw, precision="fp32", ws_tag="vitgrad_f32").forward_train(img)
+    enc = ops.VitEncoder(dict(cfg, layers=0), sd, img_hw, ws_tag="vitgrad_l0")
+    with pytest.raises(RuntimeError, match="code %d" % _lib.ERR_UNSUPPORTED):
+        enc.forward_train(img)
+    enc = ops.VitEncoder(cfg, sd, img_hw, ws_tag="vitgrad_ok")
+    f_last, f, f_proj = enc.forward_train(img, torch.from_numpy(cv).cuda())
+    assert tc.rel_l2(f_last, ref[0]) <= vg.BOUND and tc.rel_l2(f_proj, ref[2]) <= vg.BOUND
+    good()
+
+
+# ---- 5. the transposing and the column-reduction kernels, bit for bit ----------------------------------------------------------
+def _colsum(dy, x, want_sum=True, want_sumx=True):
+    L = _lib.load()
+    rows, cols = dy.shape
+    need = L.mpreid_colsum_workspace_bytes(rows, cols)
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    out = torch.full((2, cols + 2), 7.5, dtype=torch.float32, device="cuda")   # a sentinel on both sides of each output
+    rc = L.mpreid_colsum_f32(dy.data_ptr(), None if x is None else x.data_ptr(), rows, cols,
+                             out[0, 1:].data_ptr() if want_sum else None, out[1, 1:].data_ptr() if want_sumx else None,
+                             ws.data_ptr(), need, _lib.stream_ptr())
+    assert rc == 0, L.mpreid_last_error()
+    torch.cuda.synchronize()
+    assert float(out[0, 0]) == 7.5 and float(out[1, 0]) == 7.5 and float(out[0, -1]) == 7.5 and float(out[1, -1]) == 7.5
+    return out[0, 1:-1].cpu().numpy(), out[1, 1:-1].cpu().numpy()
+
+
+@pytest.mark.parametrize("rows", vg.KERNEL_ROWS)
+def test_transpose_and_colsum_kernels_bit_equal(rows):
+    """mpreid_transpose_pad_f32 and mpreid_colsum_f32 against their sequential fp32 restatements (vit_grad_cases.py), every bit,
+    at every column count; pad columns are zero, nothing is written outside the outputs"""
+    L = _lib.load()
+    for cols in vg.KERNEL_COLS:
+        dy, x = vg.kernel_inputs(rows, cols)
+        d, xd = torch.from_numpy(dy).cuda(), torch.from_numpy(x).cuda()
+        for rows_pad in (rows, (rows + 3) // 4 * 4, rows + 37):
+            buf = torch.full((cols + 2, rows_pad), 3.25, dtype=torch.float32, device="cuda")
+            assert L.mpreid_transpose_pad_f32(d.data_ptr(), rows, cols, buf[1:].data_ptr(), rows_pad, _lib.stream_ptr()) == 0
+            torch.cuda.synchronize()
+            got = buf.cpu().numpy()
+            assert np.array_equal(got[1:-1], vg.transpose_pad_ref(dy, rows_pad)), (rows, cols, rows_pad)
+            assert (got[0] == 3.25).all() and (got[-1] == 3.25).all()
+        want_sum, want_sumx = vg.colsum_ref(dy, x)
+        got_sum, got_sumx = _colsum(d, xd)
+        assert np.array_equal(got_sum, want_sum), (rows, cols)
+        assert np.array_equal(got_sumx, want_sumx), (rows, cols)
+        only_sum, untouched = _colsum(d, None, want_sumx=False)
+        assert np.array_equal(only_sum, want_sum) and (untouched == 7.5).all()
+        untouched, only_sumx = _colsum(d, xd, want_sum=False)
+        assert np.array_equal(only_sumx, want_sumx) and (untouched == 7.5).all()
+
+
+# ---- 6. the tower's gradients against float64 -----------------------------------------------------------------------------------
+_ENC = {}
+
+
+def _trained(name, **kw):
+    key = (name,) + tuple(sorted(kw.items()))
+    if key not in _ENC:
+        cfg, img_hw, sd, _, _, _ = vg.tower_case(name)
+        enc = ops.VitEncoder(cfg, sd, img_hw, ws_tag="vitgrad_" + name, **kw)
+        enc.enable_training()
+        _ENC[key] = enc
+    return _ENC[key]
+
+
+def _seeds(name, use=(True, True, True)):
+    return [torch.from_numpy(d).cuda() if u else None for d, u in zip(vg.make_seeds(name), use)]
+
+
+def _check_grads(name, got, want, host=None):
+    cfg = vg.tower_case(name)[0]
+    worst = 0.0
+    for key, g in got.items():
+        if not bool(want[key].any()):   # a gradient that is exactly zero (a seed left out): exact zeros, no relative figure
+            assert not bool(g.any()), key
+            continue
+        fig = vg.rel_l2(g, want[key])
+        worst = max(worst, fig)
+        line = "%s %s: %.3e" % (name, key, fig)
+        if host is not None:
+            line += "; fp32 autograd on the host %.3e" % vg.rel_l2(host[key], want[key])
+        print(line)
+        assert bool(torch.isfinite(g).all()), key
+        assert tuple(g.shape) == tuple(want[key].shape), key
+        if key.endswith("attn.in_proj_bias"):   # its K third is exactly 0 in exact arithmetic: judged inside the whole tensor only
+            assert vg.k_slice_share(g, cfg["width"]) <= vg.BOUND, key
+        assert fig <= vg.BOUND, key
+    print("%s: worst %.3e over %d tensors" % (name, worst, len(got)))
+
+
+@pytest.mark.parametrize("name", ["t129", "stride12", "t257", "one_layer", "full"])
+def test_tower_gradients_against_float64(name):
+    """every parameter tensor, cv_emb and the embedded sequence, all three seeds and cv_emb given: relative L2 per tensor <= 2e-5
+    against float64 autograd of the restatement; fp32 autograd on the host is printed beside it.  A second call has the same bits."""
+    cfg, img_hw, sd, imgs, cv, _ = vg.tower_case(name)
+    enc = _trained(name)
+    img, cv_d = torch.from_numpy(imgs).cuda(), torch.from_numpy(cv).cuda()
+    want_names = list(enc.masters) + ["cv_emb", "tokens"]
+    got = enc.backward(img, cv_d, *_seeds(name), want=want_names)
+    host = vg.tower_grads(name, dtype=torch.float32) if name != "full" else None
+    _check_grads(name, got, vg.tower_grads(name), host)
+    again = enc.backward(img, cv_d, *_seeds(name), want=want_names)
+    for key in got:
+        assert torch.equal(got[key], again[key]), key
+
+
+@pytest.mark.parametrize("use,with_cv", [((True, False, False), True), ((False, True, False), True), ((False, False, True), True),
+                                         ((True, True, True), False)])
+def test_tower_gradients_each_seed_alone_and_without_cv_emb(use, with_cv):
+    name = "stride12"
+    cfg, img_hw, sd, imgs, cv, _ = vg.tower_case(name)
+    enc = _trained(name)
+    img = torch.from_numpy(imgs).cuda()
+    cv_d = torch.from_numpy(cv).cuda() if with_cv else None
+    want_names = list(enc.masters) + (["cv_emb"] if with_cv else []) + ["tokens"]
+    got = enc.backward(img, cv_d, *_seeds(name, use), want=want_names)
+    want = vg.tower_grads(name, use, with_cv)
+    if use == (True, False, False):   # f_last does not depend on the last block, ln_post or proj: exact zeros
+        last = "transformer.resblocks.%d." % (cfg["layers"] - 1)
+        for key in list(got):
+            if key.startswith(last) or key.startswith("ln_post") or key == "proj":
+                assert not bool(got[key].any()) and not bool(want[key].any()), key
+                del got[key]
+    _check_grads(name, got, want)
+
+
+def test_null_grads_and_null_members_leave_the_other_bits_unchanged():
+    """guard rows and sentinels around every gradient output; a NULL grads struct (only "tokens" wanted), single missing members
+    and a single wanted member give the same bits as the full call"""
+    name = "stride12"
+    cfg, img_hw, sd, imgs, cv, _ = vg.tower_case(name)
+    enc = _trained(name)
+    img, cv_d = torch.from_numpy(imgs).cuda(), torch.from_numpy(cv).cuda()
+    names = list(enc.masters) + ["cv_emb", "tokens"]
+    shapes = {k: tuple(v.shape) for k, v in enc.masters.items()}
+    L = cfg["h_res"] * cfg["w_res"] + 1
+    shapes.update(cv_emb=(imgs.shape[0], cfg["width"]), tokens=(imgs.shape[0], L, cfg["width"]))
+    guard, bufs, views = 64, {}, {}
+    for k in names:
+        n = int(np.prod(shapes[k]))
+        bufs[k] = torch.full((n + 2 * guard,), -123.5, dtype=torch.float32, device="cuda")
+        views[k] = bufs[k][guard:guard + n].view(shapes[k])
+    full = enc.backward(img, cv_d, *_seeds(name), want=names, out=views)
+    for k in names:
+        assert full[k].data_ptr() == views[k].data_ptr()
+        assert bool((bufs[k][:guard] == -123.5).all()) and bool((bufs[k][-guard:] == -123.5).all()), k
+        assert bool(torch.isfinite(views[k]).all()), k
+    _check_grads(name, full, vg.tower_grads(name))
+    only_tokens = enc.backward(img, cv_d, *_seeds(name), want=["tokens"])
+    assert torch.equal(only_tokens["tokens"], full["tokens"])
+    b1 = "transformer.resblocks.1."
+    for missing in (b1 + "mlp.c_fc.weight", b1 + "attn.in_proj_bias", b1 + "ln_1.weight", "conv1.weight", "proj", "cv_emb"):
+        part = enc.backward(img, cv_d, *_seeds(name), want=[k for k in names if k != missing])
+        assert missing not in part
+        for k in part:
+            assert torch.equal(part[k], full[k]), (missing, k)
+    for single in (b1 + "attn.out_proj.weight", b1 + "ln_2.weight", "positional_embedding", "class_embedding", "ln_pre.weight"):
+        assert torch.equal(enc.backward(img, cv_d, *_seeds(name), want=[single])[single], full[single]), single
+    # homogeneity: the sweep is linear in the seeds; a power of two scales the bits
+    tiny = [s * 2.0 ** -40 for s in _seeds(name)]
+    scaled = enc.backward(img, cv_d, *tiny, want=names)
+    for k in names:
+        assert torch.equal(scaled[k] * 2.0 ** 40, full[k]), k
+    zero = enc.backward(img, cv_d, None, None, None, want=names)
+    for k in names:
+        assert not bool(zero[k].any()), k
+
+
+def test_forward_grad_under_torch_autograd():
+    """forward_grad's gradients in the masters and cv_emb are backward()'s, bit for bit"""
+    name = "stride12"
+    cfg, img_hw, sd, imgs, cv, _ = vg.tower_case(name)
+    enc = _trained(name, cls_only_last=False)
+    img = torch.from_numpy(imgs).cuda()
+    cv_d = torch.from_numpy(cv).cuda().requires_grad_(True)
+    seeds = _seeds(name)
+    feats = enc.forward_grad(img, cv_d)
+    plain = enc.forward_train(img, cv_d.detach())
+    for a, b in zip(feats, plain):
+        assert torch.equal(a, b)
+    for m in enc.masters.values():
+        m.grad = None
+    sum((f * d).sum() for f, d in zip(feats, seeds)).backward()
+    want = enc.backward(img, cv_d.detach(), *seeds, want=list(enc.masters) + ["cv_emb"])
+    assert torch.equal(cv_d.grad, want["cv_emb"])
+    for k, m in enc.masters.items():
+        assert torch.equal(m.grad, want[k]), k
+    _check_grads(name, {k: m.grad for k, m in enc.masters.items()}, vg.tower_grads(name))
+
+
+def test_end_to_end_head_step_backward_and_sgd():
+    """6 identities x 4 images: forward_train -> Stage2Head.step (list form: all three features carry a gradient) -> backward,
+    every tower gradient within the bound of the float64 tower + float64 head under ONE backward(); then 20 steps of plain SGD
+    on the masters (p -= lr g, sync_weights()) against the same loop in float64: the loss falls; the largest deviation from the
+    float64 curve is printed (DESIGN section 17 records it)"""
+    import stage2_head_cases as hc
+    name = "e2e"
+    cfg, img_hw, sd, imgs, cv, _ = vg.tower_case(name)
+    B = imgs.shape[0]
+    s = hc.head_setup(cfg["width"], cfg["out_dim"], batch=B, per_id=4, classes=6, seed=3)
+    cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    p = {k: cu(s[k]) for k in hc.PARAMS}
+    bn = {n: dict(weight=p[n + ".weight"], bias=p[n + ".bias"], running_mean=cu(s[n + ".running_mean"]),
+                  running_var=cu(s[n + ".running_var"]), num_batches_tracked=torch.tensor(0, dtype=torch.long, device="cuda"))
+          for n in ("bottleneck", "bottleneck_proj")}
+    head = ops.Stage2Head(p["classifier.weight"], p["classifier_proj.weight"], bn["bottleneck"], bn["bottleneck_proj"], epsilon=0.1,
+                          margin=None, **hc.HEAD_WEIGHTS)
+    enc = _trained(name)
+    img, cv_d, target, text = cu(imgs), cu(cv), cu(s["target"]), cu(s["text"])
+    names = list(enc.masters) + ["cv_emb", "tokens"]
+
+    def device_step():
+        feats = enc.forward_train(img, cv_d)
+        out = head.step(*feats, target, text_features=text, form="list")
+        return float(out.loss.cpu().reshape(-1)[0]), enc.backward(img, cv_d, out.d_f_last, out.d_f, out.d_f_proj, want=names)
+
+    g64 = {k: v.clone().requires_grad_(True) for k, v in vg.weights(sd).items()}
+    t64 = {k: torch.from_numpy(v) if v.dtype == np.int64 else torch.from_numpy(v).double() for k, v in s.items()}
+    cv64 = tc._t64(cv).requires_grad_(True)
+
+    def host_step():
+        taps = {}
+        feats = vg.tower(cfg, g64, tc._t64(imgs), cv64, taps)
+        t = dict(t64, f_last=feats[0], f=feats[1], f_proj=feats[2])
+        loss = hc.head_loss_torch(t, "list", 0.1, None, **hc.HEAD_WEIGHTS)[0]
+        for v in list(g64.values()) + [cv64]:
+            v.grad = None
+        loss.backward()
+        grads = {k: v.grad.detach().clone() for k, v in g64.items()}
+        grads.update(cv_emb=cv64.grad.detach().clone(), tokens=taps["tokens"].grad.detach().clone())
+        return float(loss.detach()), grads
+
+    loss, got = device_step()
+    loss64, want = host_step()
+    assert abs(loss - loss64) <= vg.BOUND * abs(loss64)
+    _check_grads(name, got, want)
+    lr, curve, curve64 = 0.02, [], []
+    for _ in range(20):
+        loss, got = device_step()
+        with torch.no_grad():
+            for k, m in enc.masters.items():
+                m -= lr * got[k]
+        enc.sync_weights()
+        loss64, want = host_step()
+        with torch.no_grad():
+            for k, v in g64.items():
+                v -= lr * want[k]
+        curve.append(loss)
+        curve64.append(loss64)
+    dev = max(abs(a - b) / abs(b) for a, b in zip(curve, curve64))
+    print("20 SGD steps: loss %.6f -> %.6f, float64 %.6f -> %.6f, largest relative deviation %.3e" % (curve[0], curve[-1], curve64[0],
+                                                                                                       curve64[-1], dev))
+    assert curve[-1] < curve[0] and curve64[-1] < curve64[0]
+    _ENC.pop((name,))   # its masters have moved
+
+
+def test_backward_limits_and_errors_leave_the_next_call_intact():
+    name = "one_layer"
+    cfg, img_hw, sd, imgs, cv, _ = vg.tower_case(name)
+    img, cv_d = torch.from_numpy(imgs).cuda(), torch.from_numpy(cv).cuda()
+    enc = _trained(name)
+    want = vg.tower_grads(name)
+
+    def good():
+        got = enc.backward(img, cv_d, *_seeds(name), want=["proj", "conv1.weight", "cv_emb"])
+        for k, g in got.items():
+            assert vg.rel_l2(g, want[k]) <= vg.BOUND, k
+
+    good()
+    with pytest.raises(KeyError):
+        enc.backward(img, cv_d, *_seeds(name), want=["no.such.weight"])
+    with pytest.raises(ValueError):
+        enc.backward(img, None, *_seeds(name), want=["cv_emb"])
+    with pytest.raises(ValueError):
+        enc.backward(img, cv_d, _seeds(name)[0][:1], None, None)
+    fresh = ops.VitEncoder(cfg, sd, img_hw, ws_tag="vitgrad_fresh")
+    with pytest.raises(RuntimeError, match="enable_training"):
+        fresh.backward(img, cv_d, *_seeds(name))
+    for precision in ("fp16", "fp32"):
+        with pytest.raises(NotImplementedError):
+            ops.VitEncoder(cfg, sd, img_hw, precision=precision, ws_tag="vitgrad_p").enable_training()
+    L = _lib.load()
+    need = L.mpreid_vit_backward_workspace_bytes(ctypes.byref(enc.c_cfg), imgs.shape[0])
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    desc = _lib.ImageIn(f32_dev=img.data_ptr(), mean=(ctypes.c_float * 3)(0.5, 0.5, 0.5), std=(ctypes.c_float * 3)(0.5, 0.5, 0.5))
+    rc = L.mpreid_vit_backward(ctypes.byref(enc.c_cfg), ctypes.byref(enc.c_w), ctypes.byref(enc.c_wt), ctypes.byref(desc),
+                               imgs.shape[0], None, None, None, None, None, None, ws.data_ptr(), need - 1, _lib.stream_ptr())
+    assert rc == _lib.ERR_WORKSPACE
+    good()
