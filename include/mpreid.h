@@ -820,6 +820,59 @@ int mpreid_adam_step_f32(float *param_dev, const float *grad_dev, float *exp_avg
                          float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled,
                          mpreid_stream_t stream);
 
+/* ---- Stage-2 training (processor/processor_uniprompt_stage2.py:95-135): one optimizer step over a table of tensors, and the
+ * scales of the split-precision re-pack that follows it ----
+ * Both entry points take a HOST table of tensors.  Every tensor is cut into work chunks of MPREID_OPTIM_CHUNK elements and the
+ * chunks of up to MPREID_OPTIM_TENSORS_PER_LAUNCH tensors go to ONE launch, whose tensor descriptors travel by value in the kernel
+ * arguments: the table is read during the call and may be freed or changed right after it, nothing is uploaded.  A launch's grid is
+ * capped at 2048 workgroups of 256 that stride over the chunks, so a large matrix and a bias of one launch share the chip.
+ * Stream-ordered, no host synchronisation, no atomics; every argument error -- a NULL table, n_entries < 1, a NULL or not 4-byte
+ * aligned pointer, n < 1 or >= 2^38, a class index out of range, a non-finite or negative lr or weight_decay, step < 1 -- is
+ * MPREID_ERR_ARG before anything is launched.  Only the n elements of each buffer are read or written.
+ *
+ * mpreid_optim_step_multi_f32: one step of SGD with momentum, Adam or AdamW on every tensor of the table, in place.
+ * entries[i].hyper picks one of n_classes <= MPREID_OPTIM_MAX_CLASSES {lr, weight_decay} classes (the reference's parameter
+ * groups collapse to three: weights, biases, the large-FC weights).  Launches: mpreid_optim_step_launches(n_entries) =
+ * ceil(n_entries / 64), 3 for the about 155 trained tensors of a dense ViT-B/16 (a launch is also closed at 2^30 chunks, which no
+ * table that fits a device reaches).
+ * ADAM / ADAMW: the constants and the per-element lines of mpreid_adam_step_f32 above, a and lw derived per class -- every tensor
+ * is left BIT-IDENTICAL to one mpreid_adam_step_f32 call on it with its class's lr and weight_decay (ADAMW: decoupled != 0).
+ * SGD: torch.optim.SGD(momentum = mu, dampening = 0, nesterov = False), mu >= 0 and finite; per element, each line rounded once:
+ *   g = fmaf(weight_decay, p, grad)        buf = g at step 1, else buf = fmaf(mu, buf, g)        p = fmaf(-lr, buf, p)
+ * state1_dev is buf (SGD) or exp_avg (Adam), state2_dev exp_avg_sq; SGD ignores state2_dev, which may be NULL; beta1, beta2 and eps
+ * are ignored by SGD, momentum by the other two.  Groups of four elements go through 16-byte accesses where the four (SGD: three)
+ * buffers of an entry are 16-byte aligned, one by one otherwise: the same bits.  No two buffers of the table may overlap. */
+#define MPREID_OPTIM_SGD 0
+#define MPREID_OPTIM_ADAM 1
+#define MPREID_OPTIM_ADAMW 2
+#define MPREID_OPTIM_MAX_CLASSES 8
+#define MPREID_OPTIM_CHUNK 4096
+#define MPREID_OPTIM_TENSORS_PER_LAUNCH 64
+typedef struct {
+    float *param_dev;
+    const float *grad_dev;
+    float *state1_dev, *state2_dev;
+    int64_t n;
+    int32_t hyper, reserved_;
+} mpreid_optim_entry;
+typedef struct {
+    float lr, weight_decay;
+} mpreid_optim_class;
+int mpreid_optim_step_launches(int n_entries);   /* needs no device; 0 for n_entries < 1 */
+int mpreid_optim_step_multi_f32(const mpreid_optim_entry *entries, int n_entries, const mpreid_optim_class *classes, int n_classes,
+                                int algo, int step, float beta1, float beta2, float eps, float momentum, mpreid_stream_t stream);
+/* mpreid_absmax_multi_f32: out_dev[i] = the largest finite |x| of tensor i; NaN and +-Inf count as 0 (an all-NaN tensor gives 0.0) --
+ * torch.nan_to_num(src, 0, 0, 0).abs().max(), and a maximum does not depend on the order: the bits are defined.  Two fixed levels:
+ * one partial per chunk into the workspace, then one workgroup per tensor over its partials; every out_dev[i] is written.
+ * Launches: 2 per 64 tensors.  The workspace (256-byte aligned) holds one float per chunk of the table. */
+typedef struct {
+    const float *src_dev;
+    int64_t n;
+} mpreid_absmax_entry;
+size_t mpreid_absmax_multi_workspace_bytes(const mpreid_absmax_entry *entries, int n_entries);   /* needs no device; 0 for a bad table */
+int mpreid_absmax_multi_f32(const mpreid_absmax_entry *entries, int n_entries, float *out_dev /* [n_entries] */, void *ws_dev,
+                            size_t ws_bytes, mpreid_stream_t stream);
+
 /* ---- Stage-2 head (processor/processor_uniprompt_stage2.py:114-119, loss/make_loss.py): BNNeck in training mode, the bias-free
  * classifiers, the label-smoothed identity loss, the batch-hard triplet loss, and their gradients ----
  * Small fp32 entry points between the tower's output features and the scalar loss.  No atomics and a fixed summation order: the

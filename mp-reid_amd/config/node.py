@@ -79,9 +79,22 @@ def _stage1_defaults():
             "COSINE_SCALE": 30, "CHECKPOINT_PERIOD": 10, "LOG_PERIOD": 100, "EVAL_PERIOD": 10}
 
 
+def _stage2_defaults():
+    """SOLVER.STAGE2 of the reference (config/defaults.py:218-265), its keys and values.  The stage-2 optimizers read
+    OPTIMIZER_NAME, BASE_LR, LARGE_FC_LR, BIAS_LR_FACTOR, MOMENTUM, WEIGHT_DECAY, WEIGHT_DECAY_BIAS and CENTER_LR, the schedule
+    STEPS, GAMMA, WARMUP_FACTOR, WARMUP_ITERS and WARMUP_METHOD, the loop IMS_PER_BATCH (and, through its caller, MAX_EPOCHS,
+    LOG_PERIOD, CHECKPOINT_PERIOD, EVAL_PERIOD); the other keys are accepted and unused, as in the reference."""
+    return {"IMS_PER_BATCH": 64, "OPTIMIZER_NAME": "Adam", "MAX_EPOCHS": 100, "BASE_LR": 3e-4, "LARGE_FC_LR": False,
+            "BIAS_LR_FACTOR": 1, "MOMENTUM": 0.9, "CENTER_LR": 0.5, "CENTER_LOSS_WEIGHT": 0.0005, "WEIGHT_DECAY": 0.0005,
+            "WEIGHT_DECAY_BIAS": 0.0005, "GAMMA": 0.1, "STEPS": [40, 70], "WARMUP_FACTOR": 0.01, "WARMUP_EPOCHS": 5,
+            "WARMUP_LR_INIT": 0.01, "LR_MIN": 0.000016, "WARMUP_ITERS": 500, "WARMUP_METHOD": "linear", "COSINE_MARGIN": 0.5,
+            "COSINE_SCALE": 30, "CHECKPOINT_PERIOD": 10, "LOG_PERIOD": 100, "EVAL_PERIOD": 10}
+
+
 def make_defaults():
     return CfgNode({
         "SOLVER": {"STAGE1": _stage1_defaults(), "STAGE1A": _stage1_defaults(), "STAGE1B": _stage1_defaults(),
+                   "STAGE2": _stage2_defaults(), "SEED": 1234,
                    "MARGIN": 0.3},   # the triplet loss's margin (loss/make_loss.py)
         "MODEL": {"NAME": "ViT-B-16", "DEVICE": "cuda", "DEVICE_ID": "0", "STRIDE_SIZE": [16, 16],
                   # what loss/make_loss.py reads (reference config/defaults.py:39-49)

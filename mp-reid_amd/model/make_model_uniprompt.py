@@ -21,8 +21,21 @@ NOT registered parameters (``state_dict()`` keeps the evaluation model's keys, c
 live in a holder that is built at the first ``get_text`` call -- from the checkpoint when ``load_param`` found a
 complete set (``text_encoder.*`` and ``prompt_learner.{ctx_generic, ctx_modality, ctx_platform, token_prefix,
 token_suffix}``), else from the seeded initialisation (``MODEL.INIT_SEED``), as the image tower does with an empty
-``TEST.WEIGHT``.  ``get_text`` / ``get_raw_text`` without ``label``, the MLP feature fusion (``get_image_update``), the
-multi-token variant (``get_more_image``) and training mode raise NotImplementedError.
+``TEST.WEIGHT``.  ``get_text`` / ``get_raw_text`` without ``label``, the MLP feature fusion (``get_image_update``) and the
+multi-token variant (``get_more_image``) raise NotImplementedError; so does training mode before
+``enable_stage2_training()``.
+
+Stage 2 (reference train_uniprompt.py:137-154, processor/processor_uniprompt_stage2.py:14-175): ``enable_stage2_training()``
+marks every parameter as trained except ``text_encoder`` / ``expert`` / ``prompt_learner`` names (none of which is a registered
+parameter here), moves the module to the device and builds a training encoder without a neck whose fp32 masters ARE the
+module's ``image_encoder.*`` parameters (mpreid.ops.VitEncoder.enable_training(masters)): an optimizer over
+``named_parameters()`` updates what the encoder reads, after a re-pack of the split-precision operands.  In training mode
+``forward(x=, label=, cam_label=, view_label=)`` then returns the reference's training outputs under autograd (see
+``_forward_training``); ``stage2_trainer(cfg, optimizer, text_features)`` gives the fused step without autograd
+(mpreid.ops.Stage2Trainer) over the same parameters.  ``.eval()`` drops the folded evaluation encoders, so the next
+evaluation call rebuilds them from the updated parameters and running statistics.  The dense ViT-B-16 tower in the split
+precision only: MODEL.MOE.ENABLED and RN50 keep NotImplementedError (the MoE tower's backward and an RN50 backward do not
+exist).
 
 Prompt learning (reference processor/processor_uniprompt_stage1.py:44-100): ``enable_stage1a_training()`` /
 ``enable_stage1b_training()`` (:138-157) mark ``ctx_generic``, or ``ctx_modality`` and ``ctx_platform``, as leaves that
@@ -46,6 +59,7 @@ tensor as ``x`` works as well and gives the same bits.
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from mpreid import ops as _ops
 from mpreid import synth as _synth
@@ -192,10 +206,84 @@ class build_transformer(_base.build_transformer):
         self._text_source = None    # (text state dict, prompt tensors) of the last checkpoint that carried a complete set
         self._text_encoder = None
         self._text_sd = None        # the state dict self._text_encoder was built from (text_state_dict)
+        self._train_encoder = None  # enable_stage2_training()
 
     def _invalidate(self):
         super()._invalidate()
         self._proj_encoder = None
+
+    def train(self, mode=True):
+        super().train(mode)
+        if not mode:      # an optimizer may have changed the parameters: the next evaluation call folds them afresh
+            self._invalidate()
+        return self
+
+    # -- stage 2 ----------------------------------------------------------------------------------
+    def _check_stage2_tower(self):
+        if self.model_name == 'RN50':
+            raise NotImplementedError("stage-2 training with MODEL.NAME 'RN50': the RN50 tower has no backward pass (missing: the "
+                                      "gradient kernels of the ModifiedResNet); train the ViT-B-16 tower")
+        if self.vit_cfg.get("num_experts", 0) or self.vit_cfg.get("moe_layers", 0):
+            raise NotImplementedError("stage-2 training with MODEL.MOE.ENABLED: the MoE tower has no backward pass (missing: the "
+                                      "gradients of the router and of the grouped expert GEMMs); train the dense tower")
+
+    def enable_stage2_training(self, device="cuda", set_requires_grad=True):
+        """Stage 2a of the reference (train_uniprompt.py:137-154): every parameter requires grad except those whose name
+        contains text_encoder, expert or prompt_learner; the module moves to the device; the training encoder is built on the
+        module's own image_encoder.* parameters (no copies); the folded evaluation encoders are dropped.  Returns self."""
+        self._check_stage2_tower()
+        print("Enabling Stage 2 Training: image tower, BNNeck, classifiers, SIE table.")
+        self.to(device)
+        if set_requires_grad:     # (False: the caller has marked the trained parameters itself, e.g. make_optimizer_2bstage)
+            for name, p in self.named_parameters():
+                p.requires_grad = not ('text_encoder' in name or 'expert' in name or 'prompt_learner' in name)
+        self._invalidate()
+        enc = self._build_encoder(False, ws_tag="enc_train")
+        enc.enable_training({k: p for k, p in self.named_parameters() if k.startswith("image_encoder.")})
+        self._train_encoder = enc
+        return self
+
+    def _sie_index(self, cam_label, view_label):
+        """the row of cv_embed per image (reference :209-216), or None without SIE labels"""
+        if cam_label is not None and view_label is not None:
+            return cam_label * self.view_num + view_label
+        return cam_label if cam_label is not None else view_label
+
+    def stage2_trainer(self, cfg, optimizer, text_features):
+        """The fused stage-2 step of this model (mpreid.ops.Stage2Trainer) over the module's own parameters, with `optimizer` a
+        mpreid.ops.TensorOptimizer over them (solver/make_optimizer_prompt.py) and the text features of all identities held
+        constant.  step(img, target, cv_index) takes cv_index = _sie_index(cam_label, view_label) when SIE is on."""
+        if self._train_encoder is None:
+            raise RuntimeError("stage2_trainer: call enable_stage2_training() first")
+        sie = bool(cfg.MODEL.SIE_CAMERA or cfg.MODEL.SIE_VIEW)
+        self._train_encoder.sync_weights_batched()
+        return _ops.Stage2Trainer(self._train_encoder, self.stage2_head(cfg), optimizer, text_features,
+                                  cv_table=self.cv_embed if sie else None, sie_coe=self.sie_coe, pixel_mean=self.pixel_mean,
+                                  pixel_std=self.pixel_std)
+
+    def _forward_training(self, x, cam_label, view_label):
+        """The reference's training outputs (:203-231) under autograd: ([cls_score, cls_score_proj], [f_last, f, f_proj], f_proj).
+        The tower is VitEncoder.forward_grad (its backward is the library's gradient sweep, into the module's parameters and
+        the SIE table), the two bottlenecks are F.batch_norm in training mode on the module's own buffers, the classifiers
+        F.linear.  The split-precision operands are re-packed from the parameters first (one wait for the device), so any
+        optimizer may have updated them.  A 3-tuple, which the reference's loop accepts: its fourth output is the all-token
+        projection, which the loop takes for router logits and never reads on a dense tower."""
+        self._check_stage2_tower()
+        enc = self._train_encoder
+        if enc is None:
+            raise NotImplementedError("training-mode forward: call enable_stage2_training() first (stage 2 of the dense ViT-B-16 "
+                                      "tower); there is no other training forward")
+        enc.sync_weights_batched()
+        if isinstance(x, (list, tuple, _ops.PackedRawImages)):
+            x = _ops.resize_bilinear_u8(x, self.img_hw)
+        cv = self._sie(cam_label, view_label)
+        f_last, f, f_proj = enc.forward_grad(x, cv, 0, self.pixel_mean, self.pixel_std)
+        feats = []
+        for bn, t in ((self.bottleneck, f), (self.bottleneck_proj, f_proj)):
+            feats.append(F.batch_norm(t, bn.running_mean, bn.running_var, bn.weight, bn.bias, True, 0.1, 1e-5))
+            bn.num_batches_tracked.add_(1)
+        scores = [F.linear(feats[0], self.classifier.weight), F.linear(feats[1], self.classifier_proj.weight)]
+        return scores, [f_last, f, f_proj], f_proj
 
     def text_tower(self):
         """the device text encoder (mpreid.ops.TextEncoder), built on first use together with the prompt tensors"""
@@ -274,8 +362,6 @@ class build_transformer(_base.build_transformer):
     def forward(self, x=None, label=None, get_image=False, get_text=False, cam_label=None, view_label=None,
                 image_feature=None, get_raw_text=False, view=None, get_image_update=False, text_feature=None,
                 get_more_image=False, exp_setting=None, get_image_vp=False, tta_view=0):
-        if self.training:
-            raise NotImplementedError("training-mode forward is out of scope; call .eval()")
         if get_image_update or get_more_image:
             raise NotImplementedError("feature fusion / multi-token outputs belong to Uni-Prompt training and TTPT, outside "
                                       "the accelerated evaluation path (SURVEY.md §8f)")
@@ -288,6 +374,8 @@ class build_transformer(_base.build_transformer):
         if get_image or get_image_vp:
             proj = self._raw_features(x, tta_view)[:, self.in_planes:]
             return proj + self.visual_prompt[0].to(proj.device) if get_image_vp else proj
+        if self.training:
+            return self._forward_training(x, cam_label, view_label)
         return self._encode(x, self._sie(cam_label, view_label), tta_view)
 
     def load_param(self, trained_path):

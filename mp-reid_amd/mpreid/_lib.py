@@ -68,6 +68,26 @@ SUPCON_MAX_BATCH = 1024   # MPREID_SUPCON_MAX_BATCH
 TRIPLET_MAX_BATCH = 1024  # MPREID_TRIPLET_MAX_BATCH
 
 
+OPTIM_SGD, OPTIM_ADAM, OPTIM_ADAMW = 0, 1, 2   # MPREID_OPTIM_*
+OPTIM_MAX_CLASSES, OPTIM_CHUNK, OPTIM_TENSORS_PER_LAUNCH = 8, 4096, 64
+
+
+class OptimEntry(C.Structure):
+    """mpreid_optim_entry"""
+    _fields_ = [(k, C.c_void_p) for k in ("param", "grad", "state1", "state2")] + [("n", C.c_int64), ("hyper", C.c_int32),
+                                                                                    ("reserved_", C.c_int32)]
+
+
+class OptimClass(C.Structure):
+    """mpreid_optim_class"""
+    _fields_ = [("lr", C.c_float), ("weight_decay", C.c_float)]
+
+
+class AbsmaxEntry(C.Structure):
+    """mpreid_absmax_entry"""
+    _fields_ = [("src", C.c_void_p), ("n", C.c_int64)]
+
+
 class TextCfg(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("tokens", "width", "layers", "heads", "out_dim")]
 
@@ -268,6 +288,11 @@ PROTOTYPES = {
     "mpreid_supcon_f32": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "mpreid_rows_segment_sum_f32": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "mpreid_adam_step_f32": (i32, [vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, f32, i32, vp]),
+    # stage-2 training: one optimizer step over a table of tensors, the largest finite |entry| per tensor of a table
+    "mpreid_optim_step_launches": (i32, [i32]),
+    "mpreid_optim_step_multi_f32": (i32, [P(OptimEntry), i32, P(OptimClass), i32, i32, i32, f32, f32, f32, f32, vp]),
+    "mpreid_absmax_multi_workspace_bytes": (sz, [P(AbsmaxEntry), i32]),
+    "mpreid_absmax_multi_f32": (i32, [P(AbsmaxEntry), i32, vp, vp, sz, vp]),
     # the stage-2 head: row cross-entropy, batch-hard triplet loss, BatchNorm1d in training mode, the linear products, the total
     "mpreid_xent_rows_f32": (i32, [vp, i64, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp]),
     "mpreid_triplet_workspace_bytes": (sz, [i32, i32]),

@@ -972,14 +972,30 @@ class VitEncoder:
         if self.cfg["layers"] < 1:
             raise NotImplementedError(f"{what}: a tower of at least one layer")
 
-    def enable_training(self):
+    def enable_training(self, masters: Optional[dict] = None):
         """fp32 master copies of every parameter as device tensors (leaves that require grad) in self.masters, under the
         reference's checkpoint key names and in its shapes; the split pairs the forward reads and the transposed fp32 copies
-        [in][out] the gradient GEMMs read are rebuilt from them by sync_weights().  Returns self.masters."""
+        [in][out] the gradient GEMMs read are rebuilt from them by sync_weights().  Returns self.masters.
+        masters: {key: tensor} (keys optionally prefixed 'image_encoder.') to ADOPT as the masters instead of cloning -- fp32,
+        contiguous, on the encoder's device, in the checkpoint's shapes; a model's own parameters become the masters that way,
+        and whoever updates them calls sync_weights() / sync_weights_batched() afterwards."""
         self._check_trainable("enable_training")
+        if masters is not None:
+            adopted = {}
+            for key, _, _ in self._param_fields():
+                m = masters[key] if key in masters else masters.get("image_encoder." + key)
+                if m is None:
+                    raise KeyError(f"enable_training: no master given for {key!r}")
+                if not (torch.is_tensor(m) and m.dtype == torch.float32 and m.is_contiguous() and m.device == self.device
+                        and tuple(m.shape) == tuple(self._get(key).shape)):
+                    raise ValueError(f"enable_training: the master of {key!r} must be a contiguous fp32 tensor "
+                                     f"{tuple(self._get(key).shape)} on {self.device}")
+                adopted[key] = m
+            self.masters = None
         if self.masters is None:
-            self.masters = {key: self._get(key).to(device=self.device, dtype=torch.float32).contiguous().clone().requires_grad_(True)
-                            for key, _, _ in self._param_fields()}
+            self.masters = adopted if masters is not None else {
+                key: self._get(key).to(device=self.device, dtype=torch.float32).contiguous().clone().requires_grad_(True)
+                for key, _, _ in self._param_fields()}
             self._pairs, self._wt = {}, {}
             self._layers_t = (_lib.TextLayerT * self.cfg["layers"])()
             self.c_wt = _lib.VitWeightsT(C.cast(self._layers_t, C.POINTER(_lib.TextLayerT)))
@@ -1012,6 +1028,51 @@ class VitEncoder:
             else:
                 setattr(target, field, m.data_ptr())
         torch.cuda.current_stream().synchronize()
+
+    @torch.no_grad()
+    def sync_weights_batched(self):
+        """sync_weights() with ONE wait for the device: the largest finite entry of all GEMM weights by one absmax_multi call
+        (mpreid_absmax_multi_f32), one copy of those floats into pinned host memory, one synchronisation; the scales are then
+        computed on the host as _split_pack computes them and the same pack and transpose launches follow, enqueued and not
+        waited for (their sources are the masters, their targets the buffers this encoder keeps).  Leaves the pairs, the
+        transposed copies, every scale and every struct pointer as sync_weights() leaves them, bit for bit."""
+        if self.masters is None:
+            raise RuntimeError("sync_weights_batched: call enable_training() first")
+        L = _lib.load()
+        fields = self._param_fields()
+        mats = []
+        for key, i, field in fields:
+            m = self.masters[key]
+            assert m.is_contiguous() and m.dtype == torch.float32 and m.device == self.device, key
+            if field.endswith("_w"):
+                mats.append((key, i, field, m.detach().reshape(m.shape[0], -1)))
+        sb = getattr(self, "_sync_bufs", None)
+        if sb is None or sb[0].numel() != len(mats):
+            sb = self._sync_bufs = (torch.empty(len(mats), dtype=torch.float32, device=self.device),
+                                    torch.empty(len(mats), dtype=torch.float32).pin_memory())
+        absmax_multi([m2 for _, _, _, m2 in mats], out=sb[0])
+        sb[1].copy_(sb[0], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        amax = sb[1].tolist()
+        for (key, i, field, m2), a in zip(mats, amax):
+            target = self.c_w if i is None else self._layers[i]
+            e = 9 - int(np.floor(np.log2(a))) if a > 0 else 0
+            n, k = m2.shape
+            pair = self._pairs.get(key)
+            if pair is None:
+                pair = self._pairs[key] = torch.empty((n, 2 * k), dtype=torch.float16, device=self.device)
+            _lib.check(L.mpreid_split_pack_f32(_ptr(m2), n, k, float(2.0 ** e), _ptr(pair), _lib.stream_ptr()), "mpreid_split_pack_f32")
+            setattr(target, field, pair.data_ptr())
+            setattr(target, field[:-2] + "_s" if i is not None else "conv_s", float(2.0 ** -e))
+            if i is not None:
+                if key not in self._wt:
+                    self._wt[key] = torch.empty((k, n), dtype=torch.float32, device=self.device)
+                _lib.check(L.mpreid_transpose_pad_f32(_ptr(m2), n, k, _ptr(self._wt[key]), n, _lib.stream_ptr()),
+                           "mpreid_transpose_pad_f32")
+                setattr(self._layers_t[i], field[:-2] + "_t", self._wt[key].data_ptr())
+        for key, i, field in fields:
+            if not field.endswith("_w"):
+                setattr(self.c_w if i is None else self._layers[i], field, self.masters[key].data_ptr())
 
     @torch.no_grad()
     def backward(self, img: torch.Tensor, cv_emb: Optional[torch.Tensor], d_f_last: Optional[torch.Tensor],
@@ -2206,6 +2267,329 @@ class Stage2Head:
         if self.on_update is not None:
             self.on_update()
         return Stage2Step(b["parts"], scores, b.get("i2t"), b.get("argmax"), target, b["d_f_last"], b["d_f"], b["d_f_proj"], b["grads"])
+
+
+# ----------------------------------------------------------------------------------------------
+# Stage-2 training (include/mpreid.h: mpreid_optim_step_multi_f32, mpreid_absmax_multi_f32)
+# ----------------------------------------------------------------------------------------------
+OPTIM_ALGOS = {"SGD": _lib.OPTIM_SGD, "Adam": _lib.OPTIM_ADAM, "AdamW": _lib.OPTIM_ADAMW}
+
+
+class OptimTable:
+    """The HOST table of mpreid_optim_step_multi_f32 over fp32 device tensors: entries = [(param, grad, state1, state2 or None,
+    class index)], each tensor contiguous and of the parameter's size.  The table keeps the tensors alive; set_classes rewrites
+    the class indices in place."""
+
+    def __init__(self, entries):
+        entries = list(entries)
+        if not entries:
+            raise ValueError("OptimTable: an empty table")
+        self.c = (_lib.OptimEntry * len(entries))()
+        self.keep = entries
+        for e, (p, g, s1, s2, cls) in zip(self.c, entries):
+            n = p.numel()
+            for t in (p, g, s1) + (() if s2 is None else (s2,)):
+                if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+                    raise ValueError("OptimTable: every buffer of an entry is a contiguous fp32 device tensor of the parameter's size")
+            e.param, e.grad, e.state1, e.state2 = p.data_ptr(), g.data_ptr(), s1.data_ptr(), None if s2 is None else s2.data_ptr()
+            e.n, e.hyper = n, int(cls)
+
+    def __len__(self):
+        return len(self.c)
+
+    def set_classes(self, classes):
+        for e, c in zip(self.c, classes):
+            e.hyper = int(c)
+
+
+def optim_step_launches(n_tensors: int) -> int:
+    """the number of kernel launches of one optim_step_multi call over n_tensors tensors (needs no device)"""
+    return int(_lib.load().mpreid_optim_step_launches(int(n_tensors)))
+
+
+def optim_step_multi(table: OptimTable, classes, algo: str, step: int, betas=(0.9, 0.999), eps: float = 1e-8,
+                     momentum: float = 0.0) -> None:
+    """One optimizer step over every tensor of `table`, in place (mpreid_optim_step_multi_f32): algo 'SGD' (momentum, torch's
+    form), 'Adam' (weight decay added to the gradient) or 'AdamW'; classes = [(lr, weight_decay)], at most OPTIM_MAX_CLASSES,
+    indexed by the entries; step >= 1.  Adam / AdamW leave every tensor bit-identical to adam_step on it.  A few launches for
+    the whole table (optim_step_launches), nothing synchronised."""
+    _lib.require_gpu()
+    if algo not in OPTIM_ALGOS:
+        raise ValueError(f"optim_step_multi: algo must be one of {sorted(OPTIM_ALGOS)}, got {algo!r}")
+    cls = (_lib.OptimClass * len(classes))(*[_lib.OptimClass(float(lr), float(wd)) for lr, wd in classes])
+    _lib.check(_lib.load().mpreid_optim_step_multi_f32(table.c, len(table), cls, len(classes), OPTIM_ALGOS[algo], int(step),
+                                                       float(betas[0]), float(betas[1]), float(eps), float(momentum),
+                                                       _lib.stream_ptr()), "mpreid_optim_step_multi_f32")
+
+
+def absmax_multi(tensors, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i] = the largest finite |entry| of tensors[i] (NaN and +-Inf count as 0: torch.nan_to_num(t, 0, 0, 0).abs().max()) for
+    a list of contiguous fp32 device tensors, by one mpreid_absmax_multi_f32 call -> fp32 [len(tensors)] on the device; nothing
+    is synchronised"""
+    dev = _lib.require_gpu()
+    tensors = list(tensors)
+    if not tensors:
+        raise ValueError("absmax_multi: an empty list")
+    tab = (_lib.AbsmaxEntry * len(tensors))()
+    for e, t in zip(tab, tensors):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= 1):
+            raise ValueError("absmax_multi: contiguous non-empty fp32 device tensors")
+        e.src, e.n = t.data_ptr(), t.numel()
+    L = _lib.load()
+    out = _f32_buffer(out, (len(tensors),), dev, "out")
+    ws = _workspace("absmax", L.mpreid_absmax_multi_workspace_bytes(tab, len(tensors)), dev)
+    _lib.check(L.mpreid_absmax_multi_f32(tab, len(tensors), _ptr(out), _ptr(ws), ws.numel(), _lib.stream_ptr()),
+               "mpreid_absmax_multi_f32")
+    return out
+
+
+class TensorOptimizer:
+    """torch.optim.SGD (momentum, no dampening, no Nesterov) / Adam / AdamW over fp32 device tensors whose step is ONE
+    optim_step_multi call over all of them: param_groups (one group per entry of `params`: a tensor, or a dict with "params" and
+    its own lr / weight_decay, the form solver/make_optimizer_prompt.py builds), zero_grad, step, state_dict and load_state_dict
+    in the shape of torch's optimizers.  bind(param, grad_buffer) fixes the buffer a parameter's step reads its gradient from
+    (a trainer's persistent buffers: the table is then built once); a parameter bound to no buffer is stepped from its .grad,
+    and skipped -- no state, no weight decay -- when it has none, as in torch.  betas, eps and momentum are the optimizer's;
+    lr and weight_decay are per group (at most OPTIM_MAX_CLASSES distinct pairs go into one call, more are split over calls).
+    No amsgrad, dampening or Nesterov momentum."""
+
+    def __init__(self, params, algo: str = "Adam", lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, momentum: float = 0.0,
+                 weight_decay: float = 0.0):
+        if algo not in OPTIM_ALGOS:
+            raise ValueError(f"TensorOptimizer: algo must be one of {sorted(OPTIM_ALGOS)}, got {algo!r}")
+        self.algo = algo
+        self.defaults = dict(lr=lr, weight_decay=weight_decay)
+        self.defaults.update(dict(momentum=momentum) if algo == "SGD" else dict(betas=tuple(betas), eps=eps))
+        self.param_groups = []
+        for g in params:
+            g = dict(g) if isinstance(g, dict) else {"params": [g]}
+            g["params"] = [g["params"]] if torch.is_tensor(g["params"]) else list(g["params"])
+            for k, v in self.defaults.items():
+                g.setdefault(k, v)
+            self.param_groups.append(g)
+        seen = set()
+        for p in self._params():
+            if not (torch.is_tensor(p) and p.dtype == torch.float32 and p.is_contiguous()):
+                raise ValueError("TensorOptimizer: parameters are contiguous fp32 tensors (on the device by the first step)")
+            if id(p) in seen:
+                raise ValueError("TensorOptimizer: a parameter appears in more than one group")
+            seen.add(id(p))
+        self.state = {}
+        self._bound = {}
+        self._table = None   # (key, OptimTable, class indices) of the last step
+
+    def _params(self):
+        return [p for g in self.param_groups for p in g["params"]]
+
+    def zero_grad(self, set_to_none: bool = True):
+        """the parameters' .grad, as torch does; a bound buffer is its owner's to overwrite"""
+        for p in self._params():
+            if p.grad is not None:
+                if set_to_none:
+                    p.grad = None
+                else:
+                    p.grad.zero_()
+
+    def bind(self, param: torch.Tensor, grad_buffer: Optional[torch.Tensor]):
+        """the step of `param` reads `grad_buffer` (contiguous fp32, on the device, of the parameter's size) from now on;
+        None unbinds"""
+        if not any(q is param for q in self._params()):
+            raise KeyError("TensorOptimizer.bind: not a parameter of this optimizer")
+        if grad_buffer is None:
+            self._bound.pop(id(param), None)
+        else:
+            g = grad_buffer
+            if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.numel() == param.numel()):
+                raise ValueError("TensorOptimizer.bind: the gradient buffer is a contiguous fp32 device tensor of the parameter's size")
+            self._bound[id(param)] = g
+        self._table = None
+
+    def _state_of(self, p):
+        st = self.state.get(id(p))
+        if st is None:
+            if self.algo == "SGD":
+                st = {"step": 0, "momentum_buffer": torch.zeros_like(p, requires_grad=False)}
+            else:
+                st = {"step": 0, "exp_avg": torch.zeros_like(p, requires_grad=False),
+                      "exp_avg_sq": torch.zeros_like(p, requires_grad=False)}
+            self.state[id(p)] = st
+        return st
+
+    @torch.no_grad()
+    def step(self):
+        rows = []   # (param, grad, group)
+        for g in self.param_groups:
+            for k in ("betas", "eps", "momentum"):
+                if k in self.defaults and g[k] != self.defaults[k]:
+                    raise ValueError(f"TensorOptimizer: {k} is the optimizer's, not a group's")
+            for p in g["params"]:
+                grad = self._bound.get(id(p))
+                if grad is None and p.grad is not None:
+                    grad = _dev_f32(p.grad, p.device)
+                if grad is not None:
+                    rows.append((p, grad, g))
+        if not rows:
+            return
+        if not all(p.is_cuda for p, _, _ in rows):
+            raise RuntimeError("TensorOptimizer.step: the parameters are not on the device; there is no CPU fallback")
+        # the calls: rows of one step number, at most OPTIM_MAX_CLASSES (lr, weight_decay) pairs each -- one call in a loop
+        # whose parameters step together and whose groups collapse to the reference's weights / biases / large-FC
+        calls = {}
+        for p, grad, g in rows:
+            st = self._state_of(p)
+            st["step"] += 1
+            pair = (float(g["lr"]), float(g["weight_decay"]))
+            for (step, part), c in calls.items():
+                if step == st["step"] and (pair in c["classes"] or len(c["classes"]) < _lib.OPTIM_MAX_CLASSES):
+                    break
+            else:
+                c = calls[(st["step"], len(calls))] = {"classes": [], "rows": [], "cls": []}
+            if pair not in c["classes"]:
+                c["classes"].append(pair)
+            c["rows"].append((p, grad, st))
+            c["cls"].append(c["classes"].index(pair))
+        key = tuple((id(p), grad.data_ptr()) for c in calls.values() for p, grad, _ in c["rows"])
+        if self._table is None or self._table[0] != key:
+            tables = []
+            for c in calls.values():
+                sk = ("momentum_buffer", None) if self.algo == "SGD" else ("exp_avg", "exp_avg_sq")
+                tables.append(OptimTable([(p.detach(), grad, st[sk[0]], st[sk[1]] if sk[1] else None, k)
+                                          for (p, grad, st), k in zip(c["rows"], c["cls"])]))
+            self._table = (key, tables)
+        d = self.defaults
+        for ((step, _), c), table in zip(calls.items(), self._table[1]):
+            table.set_classes(c["cls"])
+            optim_step_multi(table, c["classes"], self.algo, step, d.get("betas", (0.9, 0.999)), d.get("eps", 1e-8),
+                             d.get("momentum", 0.0))
+
+    def state_dict(self):
+        order = {id(p): i for i, p in enumerate(self._params())}
+        groups = [dict({k: v for k, v in g.items() if k != "params"}, params=[order[id(p)] for p in g["params"]])
+                  for g in self.param_groups]
+        return {"state": {order[k]: {n: (t.clone() if torch.is_tensor(t) else t) for n, t in v.items()}
+                          for k, v in self.state.items() if k in order}, "param_groups": groups, "algo": self.algo}
+
+    def load_state_dict(self, sd):
+        if sd.get("algo", self.algo) != self.algo:
+            raise ValueError(f"TensorOptimizer.load_state_dict: a state of {sd['algo']!r} for an optimizer of {self.algo!r}")
+        params = self._params()
+        if len(sd["param_groups"]) != len(self.param_groups) or any(
+                len(a["params"]) != len(b["params"]) for a, b in zip(sd["param_groups"], self.param_groups)):
+            raise ValueError("TensorOptimizer.load_state_dict: the parameter groups do not match")
+        for mine, theirs in zip(self.param_groups, sd["param_groups"]):
+            mine.update({k: v for k, v in theirs.items() if k != "params"})
+        self.state = {}
+        for i, v in sd["state"].items():
+            p = params[int(i)]
+            self.state[id(p)] = {n: (t.detach().to(device=p.device, dtype=torch.float32).reshape(p.shape).contiguous().clone()
+                                     if torch.is_tensor(t) else int(t)) for n, t in v.items()}
+        self._table = None
+
+
+class Stage2Trainer:
+    """One fused stage-2 step on the device (reference processor/processor_uniprompt_stage2.py:88-135 without autograd):
+    VitEncoder.forward_train, Stage2Head.step in the Uni-Prompt form, VitEncoder.backward into persistent gradient buffers, the
+    gradient of the SIE table, ONE TensorOptimizer.step over every bound tensor, VitEncoder.sync_weights_batched -- all enqueued
+    without a wait except the one of the re-pack.
+    encoder: a VitEncoder after enable_training (the dense tower in the split precision; anything else is the encoder's
+    NotImplementedError); head: the Stage2Head over the same model's parameters; optimizer: a TensorOptimizer.  Of the
+    optimizer's parameters the trainer binds those it computes a gradient for: the encoder's masters, classifier.weight,
+    bottleneck.weight / .bias, and cv_table.  classifier_proj.weight, bottleneck_proj.weight / .bias and anything else are NEVER
+    bound: the reference's loss leaves cls_score_proj out, they have no .grad there, and torch skips them -- no update and no
+    weight decay (the head's exact zeros for them would decay them under coupled Adam).  bottleneck_proj still runs in training
+    mode in the reference's forward, so its running statistics move: one bn1d_train forward on f_proj does the same here.
+    cv_table: the SIE table cv_embed [rows, width] (the encoder's cv_emb is sie_coe * cv_table[cv_index]); its gradient is
+    sie_coe * the rows of d cv_emb summed per table row in batch order (rows_segment_sum with a window of one token).
+    Not reproduced: autocast and GradScaler (the features and gradients are fp32-grade, nothing to scale)."""
+
+    HEAD_BOUND = ("classifier.weight", "bottleneck.weight", "bottleneck.bias")
+
+    def __init__(self, encoder: "VitEncoder", head: Stage2Head, optimizer: TensorOptimizer, text_features: torch.Tensor,
+                 cv_table: Optional[torch.Tensor] = None, sie_coe: float = 3.0, pixel_mean=(0.5, 0.5, 0.5),
+                 pixel_std=(0.5, 0.5, 0.5)):
+        if not isinstance(encoder, VitEncoder):
+            raise NotImplementedError("Stage2Trainer: the dense ViT tower in the split precision only (no RN50 tower)")
+        encoder._check_trainable("Stage2Trainer")
+        if encoder.masters is None:
+            raise RuntimeError("Stage2Trainer: call encoder.enable_training() first")
+        if not isinstance(optimizer, TensorOptimizer):
+            raise TypeError("Stage2Trainer: the optimizer is a TensorOptimizer (any other optimizer takes the autograd path)")
+        self.enc, self.head, self.optimizer = encoder, head, optimizer
+        self.text_features = _dev_f32(text_features, encoder.device)
+        self.cv_table, self.sie_coe = cv_table, float(sie_coe)
+        self.pixel_mean, self.pixel_std = tuple(pixel_mean), tuple(pixel_std)
+        mine = {id(p) for p in optimizer._params()}
+        self.grads = {}      # encoder key | "cv_embed" -> the persistent gradient buffer
+        for key, m in encoder.masters.items():
+            if id(m) in mine:
+                self.grads[key] = torch.zeros_like(m, requires_grad=False)
+                optimizer.bind(m, self.grads[key])
+        self._want = list(self.grads)
+        self._head_bound = [k for k in self.HEAD_BOUND if id(head.params[k]) in mine]
+        self._cv_trained = cv_table is not None and id(cv_table) in mine
+        if cv_table is not None:
+            w = encoder.cfg["width"]
+            if not (cv_table.is_cuda and cv_table.dtype == torch.float32 and cv_table.is_contiguous() and cv_table.dim() == 2
+                    and cv_table.shape[1] == w):
+                raise ValueError(f"Stage2Trainer: cv_table is a contiguous fp32 device tensor [rows, {w}]")
+            if self._cv_trained:
+                self.grads["cv_embed"] = torch.zeros_like(cv_table, requires_grad=False)
+                optimizer.bind(cv_table, self.grads["cv_embed"])
+                self._seg = torch.empty((cv_table.shape[0], 1, w), dtype=torch.float32, device=encoder.device)
+        self._bufs = {}
+        self._head_batch = None
+
+    def _buffers(self, B: int):
+        b = self._bufs.get(B)
+        if b is None:
+            dev, Dp = self.enc.device, self.head.Dp
+            b = self._bufs[B] = dict(y=torch.empty((B, Dp), dtype=torch.float32, device=dev),
+                                     mean=torch.empty(Dp, dtype=torch.float32, device=dev),
+                                     invstd=torch.empty(Dp, dtype=torch.float32, device=dev))
+            if self._cv_trained:
+                b["d_cv"] = torch.empty((B, 1, self.enc.cfg["width"]), dtype=torch.float32, device=dev)
+        return b
+
+    @torch.no_grad()
+    def step(self, img: torch.Tensor, target: torch.Tensor, cv_index: Optional[torch.Tensor] = None,
+             validate: bool = False) -> Stage2Step:
+        """img fp32 [B, 3, H, W] or uint8 [B, H, W, 3], target int64 [B], cv_index int64 [B] (rows of cv_table; needed exactly
+        when the trainer has one) -> the Stage2Step of the batch BEFORE the update: device tensors the next step overwrites.
+        The labels and the SIE indices address tables on the device: validate=True checks them on the host first, which
+        waits for the device; a loop checks its whole label set once instead."""
+        enc, head = self.enc, self.head
+        if (cv_index is None) != (self.cv_table is None):
+            raise ValueError("Stage2Trainer.step: cv_index comes exactly with a cv_table")
+        B = img.shape[0]
+        b = self._buffers(B)
+        cv_emb = None
+        if self.cv_table is not None:
+            if validate:
+                check_segment_index(cv_index, B, self.cv_table.shape[0])
+            cv_index = _dev_i64(cv_index, enc.device)
+            cv_emb = self.sie_coe * self.cv_table.detach()[cv_index]
+        f_last, f, f_proj = enc.forward_train(img, cv_emb, VIEW_ORIGINAL, self.pixel_mean, self.pixel_std)
+        st = head.step(f_last, f, f_proj, target, self.text_features, form="uniprompt", validate=validate)
+        if self._head_batch != B:   # the head's gradient buffers are per batch size: bound once per size
+            for k in self._head_bound:
+                self.optimizer.bind(head.params[k], st.grads[k])
+            self._head_batch = B
+        # bottleneck_proj(f_proj) of the reference's training forward: nothing reads the output, the statistics move
+        bp_w, bp_b = head.params["bottleneck_proj.weight"].detach(), head.params["bottleneck_proj.bias"].detach()
+        rm, rv, nbt = head.bn["bottleneck_proj"]
+        bn1d_train(f_proj, bp_w, bp_b, rm, rv, head.momentum, head.bn_eps, y=b["y"], mean=b["mean"], invstd=b["invstd"])
+        nbt.add_(1)
+        want, out = self._want, {k: self.grads[k] for k in self._want}
+        if self._cv_trained:
+            want, out = want + ["cv_emb"], dict(out, cv_emb=b["d_cv"].view(B, -1))
+        # (d_f_last: exact zeros in the Uni-Prompt form -- a None seed is zero and costs nothing)
+        enc.backward(img, cv_emb, None, st.d_f, st.d_f_proj, want, VIEW_ORIGINAL, self.pixel_mean, self.pixel_std, out=out)
+        if self._cv_trained:
+            rows_segment_sum(b["d_cv"], cv_index, 0, 1, self.cv_table.shape[0], out=self._seg, validate=False)
+            torch.mul(self._seg.view(self.cv_table.shape), self.sie_coe, out=self.grads["cv_embed"])
+        self.optimizer.step()
+        enc.sync_weights_batched()
+        return st
 
 
 def _np_getter(state_dict):

@@ -1,5 +1,7 @@
-"""Drop-in for the evaluation entry points of the reference's ``processor/processor_uniprompt_stage2.py``:
+"""Drop-in for the reference's ``processor/processor_uniprompt_stage2.py``:
 
+  do_train_stage2(cfg, model, center_criterion, train_loader_stage2, val_loader, optimizer, optimizer_center, scheduler,
+                  loss_fn, num_query, local_rank, max_epochs, log_period, checkpoint_period, eval_period)   reference :14-223
   do_inference(cfg, model, val_loader, num_query)                 reference :225-266
   do_inference_ttpt_option_a(cfg, model, val_loader, num_query)   reference :530-693  (TTA "option A")
 
@@ -14,8 +16,28 @@ BEFORE it (:594), so a batch straddling num_query is augmented as a whole; TEST.
 optimises prompts at test time.  The text tower and its prompt gradient exist (model(label=..., get_text=True) after
 model.enable_stage1a_training()), but the reference's branch reads prompt_learner.cls_ctx and num_class, which its own
 PromptLearner does not have: there is no reference behaviour to reproduce -> NotImplementedError.
+
+``do_train_stage2`` is the reference's loop: the text features of all identities once (``get_text`` in batches of
+SOLVER.STAGE2.IMS_PER_BATCH labels, no grad), then per epoch ``scheduler.step(epoch)``, ``model.train()`` and one step per batch
+on ``loss_fn(score, feat, target, target_cam, image_features_proj @ text_features.t())``; the reference's log lines; every
+``checkpoint_period`` epochs ``OUTPUT_DIR/EXP_SETTING/NAME_{epoch}.pth`` (the module's ``state_dict()`` plus
+``text_state_dict()``, which ``load_param`` reads back); every ``eval_period`` epochs the validation with the evaluator.  The model
+must have had ``enable_stage2_training()`` (the optimizers of solver/make_optimizer_prompt.py are built over its device
+parameters); a model that has not is enabled here, its ``requires_grad`` flags kept.  With a ``mpreid.ops.TensorOptimizer`` a
+batch is ONE ``mpreid.ops.Stage2Trainer.step`` -- forward, head, backward, the multi-tensor optimizer step and the re-pack, no
+autograd graph -- and the loss and accuracy are read back only at the log lines and at the epoch's end.  With any other
+optimizer a batch takes the autograd path through the training-mode forward and ``loss_fn``.  Not reproduced:
+  * autocast and ``GradScaler``: features, loss and gradients are fp32-grade throughout, there is nothing to scale;
+  * ``nn.DataParallel`` over several GPUs: one device;
+  * the center-loss branch: the reference's ``loss_func`` never calls ``center_criterion``, its loop touches the centers only
+    when ``'center' in MODEL.METRIC_LOSS_TYPE``, a configuration ``make_loss`` cannot answer -- ``optimizer_center`` is built,
+    passed along, zeroed and never stepped.  The same holds here;
+  * the MoE load-balancing term: the MoE tower has no backward, ``enable_stage2_training()`` refuses it.
+The labels and the SIE rows address tables on the device: each batch's are range-checked on the host before they are copied
+(no wait for the device).
 """
 import logging
+import os
 import time
 
 import torch
@@ -159,3 +181,118 @@ def _report_option_a(logger, cmc, mAP, limit=50, extra=None):
     top = [float(cmc[r - 1]) if len(cmc) >= r else 0.0 for r in (1, 5)]
     logger.info("Returning Rank-1: {:.1%}, Rank-5: {:.1%}".format(*top))
     return top[0], top[1]
+
+
+def _stage2_text_features(model, num_classes, batch):
+    """the text features of every identity, in label order (reference :58-73)"""
+    out = []
+    with torch.no_grad():
+        for lo in range(0, num_classes, batch):
+            out.append(model(label=torch.arange(lo, min(lo + batch, num_classes)), get_text=True))
+    return torch.cat(out, 0).cuda().float().contiguous()
+
+
+def _check_range(t, n, what):
+    if torch.is_tensor(t) and not t.is_cuda and t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
+        raise ValueError(f"stage 2: {what} outside 0 .. {n - 1}")
+
+
+def do_train_stage2(cfg, model, center_criterion, train_loader_stage2, val_loader, optimizer, optimizer_center, scheduler,
+                    loss_fn, num_query, local_rank, max_epochs, log_period, checkpoint_period, eval_period):
+    from datetime import timedelta
+    from utils.meter import AverageMeter
+    device = "cuda"
+    epochs = max_epochs
+    logger = logging.getLogger("transreid.train")
+    logger.info('start training')
+    if getattr(model, "_train_encoder", None) is None:
+        model.enable_stage2_training(set_requires_grad=False)
+    model.to(device)
+    num_classes = model.num_classes
+    loss_meter, acc_meter = AverageMeter(), AverageMeter()
+    evaluator = R1_mAP_eval(num_query, max_rank=50, feat_norm=cfg.TEST.FEAT_NORM)
+    all_start_time = time.monotonic()
+
+    model.eval()
+    text_features = _stage2_text_features(model, num_classes, cfg.SOLVER.STAGE2.IMS_PER_BATCH)
+    trainer = model.stage2_trainer(cfg, optimizer, text_features) if isinstance(optimizer, _ops.TensorOptimizer) else None
+    logger.info("stage 2: {} identities, {} step".format(
+        num_classes, "fused (mpreid.ops.Stage2Trainer)" if trainer is not None else "autograd"))
+    sie_rows = model.cv_embed.shape[0] if (cfg.MODEL.SIE_CAMERA or cfg.MODEL.SIE_VIEW) else 0
+    rank0 = not (cfg.MODEL.DIST_TRAIN and torch.distributed.is_initialized()) or torch.distributed.get_rank() == 0
+
+    for epoch in range(1, epochs + 1):
+        start_time = time.time()
+        loss_meter.reset()
+        acc_meter.reset()
+        evaluator.reset()
+        scheduler.step(epoch)
+        model.train()
+        pending = []     # (loss, accuracy, batch size) of the steps that have not been read back yet: device scalars
+        n_batches = len(train_loader_stage2)
+        n_iter = -1
+        for n_iter, (img, vid, target_cam, target_view) in enumerate(train_loader_stage2):
+            vid = torch.as_tensor(vid)
+            _check_range(vid, num_classes, "labels")
+            target = vid.to(device).long()
+            target_cam = torch.as_tensor(target_cam).long() if cfg.MODEL.SIE_CAMERA else None
+            target_view = torch.as_tensor(target_view).long() if cfg.MODEL.SIE_VIEW else None
+            if sie_rows:
+                _check_range(model._sie_index(target_cam, target_view), sie_rows, "SIE rows")
+            target_cam = None if target_cam is None else target_cam.to(device)
+            target_view = None if target_view is None else target_view.to(device)
+            img = img.to(device)
+            if trainer is not None:
+                st = trainer.step(img, target, model._sie_index(target_cam, target_view))
+                loss, acc = st.loss.clone(), st.acc
+            else:
+                optimizer.zero_grad()
+                optimizer_center.zero_grad()
+                scores, feats_all, image_features_proj = model(x=img, label=target, cam_label=target_cam, view_label=target_view)[:3]
+                logits_i2t = image_features_proj @ text_features.t()
+                loss = loss_fn(scores[0], feats_all[1], target, target_cam, logits_i2t)
+                loss.backward()
+                optimizer.step()
+                acc = (logits_i2t.max(1)[1] == target).float().mean()
+                loss = loss.detach()
+            pending.append((loss, acc, img.shape[0]))
+            if (n_iter + 1) % log_period == 0 or n_iter + 1 == n_batches:
+                for value, a, n in pending:
+                    loss_meter.update(float(value), n)
+                    acc_meter.update(float(a), 1)
+                pending = []
+            if (n_iter + 1) % log_period == 0:
+                logger.info("Epoch[{}] Iteration[{}/{}] Loss: {:.3f}, Acc: {:.3f}, Base Lr: {:.2e}"
+                            .format(epoch, (n_iter + 1), n_batches, loss_meter.avg, acc_meter.avg, optimizer.param_groups[0]['lr']))
+        torch.cuda.synchronize()
+        time_per_batch = (time.time() - start_time) / max(n_iter + 1, 1)
+        if not cfg.MODEL.DIST_TRAIN:
+            batch_size = getattr(train_loader_stage2, "batch_size", None) or cfg.SOLVER.STAGE2.IMS_PER_BATCH
+            logger.info("Epoch {} done. Time per batch: {:.3f}[s] Speed: {:.1f}[samples/s]"
+                        .format(epoch, time_per_batch, batch_size / time_per_batch))
+
+        if epoch % checkpoint_period == 0 and rank0:
+            out_dir = os.path.join(cfg.OUTPUT_DIR, cfg.DATASETS.EXP_SETTING)
+            os.makedirs(out_dir, exist_ok=True)
+            state = dict(model.state_dict())
+            state.update(model.text_state_dict())
+            torch.save(state, os.path.join(out_dir, cfg.MODEL.NAME + '_{}.pth'.format(epoch)))
+
+        if epoch % eval_period == 0 and rank0:
+            model.eval()
+            for img, pid, camid, camids, target_view, _ in val_loader:
+                with torch.no_grad():
+                    img = img.to(device)
+                    camids = camids.to(device) if cfg.MODEL.SIE_CAMERA else None
+                    target_view = target_view.to(device) if cfg.MODEL.SIE_VIEW else None
+                    feat = model(x=img, cam_label=camids, view_label=target_view)
+                    evaluator.update((feat, pid, camid))
+            cmc, mAP = evaluator.compute()[:2]
+            logger.info("Validation Results - Epoch: {}".format(epoch))
+            logger.info("mAP: {:.1%}".format(mAP))
+            for r in [1, 5, 10]:
+                logger.info("CMC curve, Rank-{:<3}:{:.1%}".format(r, cmc[r - 1]))
+            torch.cuda.empty_cache()
+
+    total_time = timedelta(seconds=time.monotonic() - all_start_time)
+    logger.info("Total running time: {}".format(total_time))
