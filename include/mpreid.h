@@ -596,6 +596,83 @@ int mpreid_moe_route(const float *x_dev, int64_t rows, int width, const float *l
 int mpreid_moe_mlp_split(const void *a_pairs_dev, int64_t rows, int width, const int32_t *sel_dev, const float *w_dev,
                          int num_experts, int top_k, const mpreid_moe_layer *layer, float *x_inout_dev, void *ws_dev,
                          size_t ws_bytes, mpreid_stream_t stream);
+/* ---- The gradient through one routed MLP and the gradient of the router (csrc/moe_grad.hip) ------------------------------
+ * The building blocks of the MoE tower's backward (mpreid_vit_backward_moe, below), as unit seams.  Stage 2 freezes every expert
+ * matrix, so these deliver the gradient THROUGH the experts and the gradient OF the routing weights; the expert matrices' own
+ * gradients are not implemented: mpreid_moe_expert_grads keeps their place, and a non-NULL member is MPREID_ERR_UNSUPPORTED.
+ *   per slot s = (row r, expert e = sel[r][k]):  u_s = c_fc_e(h_r), t_s = QuickGELU(u_s), y_s = c_proj_e(t_s) + b_proj_e
+ *   d_w[r][k] = <dy_r, y_s>;  dt_s = (w[r][k] dy_r) . Wproj_e;  du_s = dt_s * QuickGELU'(u_s)
+ *   d_a[r] = sum over the row's experts, ASCENDING e, of du_s . Wfc_e
+ * u and y are recomputed by the forward's own grouped GEMMs (y has the forward's bits); the two gradient GEMMs are exact fp32
+ * (one k-ascending fmaf chain per element, the arithmetic of the dense sweep's mpreid_gemm_f32_linear) on fp32 transposed
+ * copies of the expert matrices.
+ * mpreid_moe_mlp_backward: a_pairs / sel / w / layer as for mpreid_moe_mlp_split; dy_dev fp32 [rows][width]; d_a_out fp32
+ * [rows][width] is WRITTEN; d_w_out fp32 [rows][top_k] (entry k belongs to sel[r][k]) is written, or added to with one rounded
+ * add per entry when accumulate_d_w != 0 (the tower sums it over its MoE blocks).  Either output may be NULL (not both); the
+ * other's bits do not change.  Stateless, stream-ordered, no host synchronisation, every error before a launch.
+ * LIMIT: as for mpreid_moe_mlp_split the CONTENTS of sel_dev are not checked.  An entry outside 0 .. E-1 contributes nothing,
+ * gets d_w = 0 and is never used as an address; of a repeated expert the last entry is the one the forward used, the earlier
+ * ones get d_w = 0.
+ * Workspace (mpreid_moe_grad_workspace_bytes, 256-byte aligned), per routed slot (<= rows * top_k + 128 * num_experts of
+ * them): the forward's 20 * width bytes (hidden pairs, y) and 16 * width bytes more (u, overwritten by du); per row 8 * top_k
+ * bytes of tables.  Nothing else is written.
+ * mpreid_moe_route_backward: logits [rows][E], sel / w [rows][K] of mpreid_moe_route, d_w [rows][K] (NULL: zeros).
+ *   c_r = sum_k w[r][k] d_w[r][k];  d_logits[r][sel[r][k]] = w[r][k] (d_w[r][k] - c_r), every other entry exactly 0
+ *   (top_k == 1: all exactly 0);  with aux_coef != 0 also  d_logits[r][j] += p_rj (g_j - sum_e p_re g_e),
+ *   g_e = aux_coef * E * f_e / rows, p = softmax(logits), f_e = the share of rows whose sel holds e
+ *   l_aux = E * sum_e f_e P_e,  P_e = mean_r p_re   (model/clip/model.py:342-377 on ONE layer of logits; NOT times aux_coef)
+ * aux_coef == 0 adds nothing: the bits are those of the routing term alone.  d_logits_out or l_aux_out may be NULL.  Its
+ * workspace (mpreid_moe_route_backward_workspace_bytes, 256-byte aligned): one float per row, and 4 * num_experts bytes per
+ * 1024 rows of expert counts. */
+typedef struct {                 /* fp32 device copies, per expert the TRANSPOSE of the checkpoint's [out][in] matrix */
+    const float *fc_t;           /* [E][width][4*width] */
+    const float *proj_t;         /* [E][4*width][width] */
+} mpreid_moe_layer_t;
+typedef struct {                 /* the expert matrices' own gradients: NOT IMPLEMENTED, every member must be NULL */
+    float *fc_w, *fc_b, *proj_w, *proj_b;
+} mpreid_moe_expert_grads;
+size_t mpreid_moe_grad_workspace_bytes(int64_t rows, int width, int num_experts, int top_k);   /* 0: outside the limits */
+int mpreid_moe_mlp_backward(const void *a_pairs_dev, int64_t rows, int width, const int32_t *sel_dev, const float *w_dev,
+                            int num_experts, int top_k, const mpreid_moe_layer *layer, const mpreid_moe_layer_t *layer_t,
+                            const float *dy_dev, float *d_a_out, float *d_w_out, int accumulate_d_w,
+                            const mpreid_moe_expert_grads *d_experts /* NULL */, void *ws_dev, size_t ws_bytes,
+                            mpreid_stream_t stream);
+/* ---- The MoE tower's training forward and backward (csrc/vit.hip, csrc/vit_grad.hip) ---------------------------------------
+ * mpreid_vit_forward_train_moe: mpreid_vit_forward_train for a tower with at least one MoE block.  With MoE the reference's
+ * tower hands out x11 = x12 = the transformer's output (model/clip/model.py:448-454), so f_last is the CLS row of the LAST
+ * block's OUTPUT (the dense tower's: of its input).  f | f_proj keep the bits of mpreid_vit_forward_moe of a tower without a
+ * neck (the same launches; cfg.cls_only_last is honoured as there).  logits_out [B * L][E] (rows b * L + l; the reference's
+ * flat order is l * B + b) and l_aux_out [1] = the load-balancing loss of those logits, each optional.  Workspace:
+ * mpreid_vit_forward_train_moe_workspace_bytes.  moe_layers == 0: MPREID_ERR_UNSUPPORTED (that is the dense tower).
+ * mpreid_vit_backward_moe: mpreid_vit_backward for that tower -- the gradients of
+ *   sum(f_last o d_f_last) + sum(f o d_f) + sum(f_proj o d_f_proj) + aux_coef * l_aux
+ * with the dense entry point's contract: stateless, stream-ordered, no host synchronisation, gradients written not
+ * accumulated, NULL members skipped without changing the other outputs' bits, every error found before a launch (a NaN or
+ * infinite aux_coef is MPREID_ERR_ARG),
+ * cfg.cls_only_last ignored.  Dense blocks (l >= moe_layers) go through the dense sweep's own code; of an MoE block the
+ * attention half does too, and the MLP half is mpreid_moe_mlp_backward's.  The routing (w, sel) of block 0 serves every MoE
+ * block, so d_w is summed over them (swept last block first, one rounded add per block) and reaches block 0's gate:
+ *   d gate.weight [E][width] = d_logits^T . h,  dh += d_logits . gate.weight   (h = the fp32 ln_2 output the router saw)
+ * d_gate_w_out (block 0's; later gates are never read, so they have no gradient) and l_aux_out may be NULL.  Of an MoE block
+ * grads->layers[l].fc_w / fc_b / proj_w / proj_b must be NULL (it has no dense MLP) and wt->layers[l].fc_t / proj_t are not
+ * read; the expert matrices' own gradients are not implemented (there is no member to ask for them).  moe_t: per MoE block the
+ * fp32 transposed expert matrices (mpreid_moe_layer_t), a HOST array of moe_layers entries.
+ * Workspace (mpreid_vit_backward_moe_workspace_bytes): the dense sweep's, plus per row 8 * (top_k + num_experts) + 4 * top_k
+ * bytes (routing, logits, d_logits, d_w) and mpreid_moe_grad_workspace_bytes(batch * tokens, width, num_experts, top_k).
+ * Limits: those of mpreid_vit_backward and of mpreid_vit_forward_moe (rows * top_k <= 2^23 follows from them). */
+typedef struct {
+    const mpreid_moe_layer_t *layers;   /* HOST array of moe_layers entries */
+} mpreid_vit_moe_t;
+size_t mpreid_vit_forward_train_moe_workspace_bytes(const mpreid_vit_cfg *cfg, const mpreid_vit_moe *moe, int batch);
+int mpreid_vit_forward_train_moe(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_moe *moe,
+                                 const mpreid_image_in *img, int batch, const float *cv_emb_dev, float *f_last_out, float *f_out,
+                                 float *f_proj_out, float *logits_out, float *l_aux_out, void *ws_dev, size_t ws_bytes,
+                                 mpreid_stream_t stream);
+size_t mpreid_vit_backward_moe_workspace_bytes(const mpreid_vit_cfg *cfg, const mpreid_vit_moe *moe, int batch);
+size_t mpreid_moe_route_backward_workspace_bytes(int64_t rows, int num_experts);   /* 0: outside the limits */
+int mpreid_moe_route_backward(const float *logits_dev, int64_t rows, int num_experts, int top_k, const int32_t *sel_dev,
+                              const float *w_dev, const float *d_w_dev, float aux_coef, float *d_logits_out, float *l_aux_out,
+                              void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
 
 /* ---- CLIP text tower, model/clip/model.py:609-619 after the embedding lookup (= model/make_model_uniprompt.py:58-68) ----
  * x = prompts + pos_emb; cfg.layers residual blocks with CAUSAL attention (key j takes part in query row i iff j <= i,
@@ -735,8 +812,7 @@ int mpreid_vit_attention_backward(const float *qkv_dev, const float *d_o_dev, in
  * operands, 16 bytes per (head, row) attention statistics, and the reductions' partial sums (8 x 4 W bytes per 128 rows)
  * and row statistics (8 bytes per row).  Errors, all before anything is launched: NULL or misaligned pointers, batch <= 0,
  * batch * L above 65 535 * 128 rows (the column reduction's grid): MPREID_ERR_ARG; a short workspace (256-byte aligned): MPREID_ERR_WORKSPACE; layers < 1, a precision other than
- * MPREID_VIT_SPLIT or a shape outside mpreid_vit_forward's: MPREID_ERR_UNSUPPORTED.  (The C entry point has no MoE argument;
- * mpreid.ops refuses an MoE tower.) */
+ * MPREID_VIT_SPLIT or a shape outside mpreid_vit_forward's: MPREID_ERR_UNSUPPORTED.  (An MoE tower: mpreid_vit_backward_moe.) */
 typedef struct {                       /* device pointers, fp32, [in][out] = the transpose of the checkpoint's [out][in] */
     const float *in_proj_t;            /* [width][3 * width] */
     const float *out_proj_t;           /* [width][width] */
@@ -758,6 +834,12 @@ int mpreid_vit_backward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, 
                         const mpreid_image_in *img, int batch, const float *cv_emb_dev, const float *d_f_last_dev,
                         const float *d_f_dev, const float *d_f_proj_dev, const mpreid_vit_grads *grads, float *d_tokens_dev,
                         void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
+/* the MoE tower's sweep: described with mpreid_vit_forward_train_moe ("The MoE tower's training forward and backward") */
+int mpreid_vit_backward_moe(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_weights_t *wt,
+                            const mpreid_vit_moe *moe, const mpreid_vit_moe_t *moe_t, const mpreid_image_in *img, int batch,
+                            const float *cv_emb_dev, const float *d_f_last_dev, const float *d_f_dev, const float *d_f_proj_dev,
+                            float aux_coef, const mpreid_vit_grads *grads, float *d_gate_w_out, float *d_tokens_dev,
+                            float *l_aux_out, void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
 /* The two small kernels of the parameter gradients alone, for unit tests and tools.
  * mpreid_transpose_pad_f32: dst [cols][rows_pad] = src [rows][cols] transposed, columns rows .. rows_pad - 1 zero.
  * mpreid_colsum_f32: out_sum[c] = sum_m dy[m][c] and out_sumx[c] = sum_m dy[m][c] xhat[m][c], xhat = (x - mean) / sigma per row
@@ -1131,6 +1213,13 @@ int mpreid_cast_f32_to_f16(const float *x_dev, void *y_dev, int64_t n, mpreid_st
 #define MPREID_PROF_MOE_FC1 112
 #define MPREID_PROF_MOE_FC2 113
 #define MPREID_PROF_MOE_COMBINE 114
+/* the MoE gradient kernels (csrc/moe_grad.hip); the grouped fp32 GEMMs: n = N, k = K, work 0 as above (2 * slots * N * K) */
+#define MPREID_PROF_MOE_GRAD_U 115         /* FC1 once more through the fp32 epilogue: the pre-activation u */
+#define MPREID_PROF_MOE_GRAD_DW 116
+#define MPREID_PROF_MOE_GRAD_DT 117        /* (w dy) . Wproj_e times QuickGELU'(u) */
+#define MPREID_PROF_MOE_GRAD_DH 118        /* du . Wfc_e */
+#define MPREID_PROF_MOE_GRAD_COMBINE 119
+#define MPREID_PROF_MOE_GRAD_ROUTER 120    /* the router gradient's launches together */
 typedef struct {
     int32_t epilogue;        /* GemmEpi id of the fp16 GEMM class, or MPREID_PROF_* */
     int32_t n, k;            /* GEMM N and K (split epilogues: K = 2 * kseg halfs per operand row; 3 * kseg is executed) */

@@ -32,7 +32,7 @@ __device__ __forceinline__ void moe_dma16(const void *gsrc, unsigned char *lds_d
 // layout of the workspace
 // ---------------------------------------------------------------------------------------------
 constexpr int MOE_ROWS_PER_BLOCK = 1024;   // dispatch kernels: 16 sub-chunks of 64 rows (one wave each) per workgroup
-constexpr int MOE_META_INTS = 256;         // [0] tile count, [64 .. 64 + E) first slot of expert e
+constexpr int MOE_META_INTS = 256;         // [0] tile count, [64 .. 64 + E) first slot of expert e, [128 .. 128 + E) rows of expert e
 
 MoeLayout moe_layout(int64_t rows, int W, int E, int K) {
     MoeLayout m{};
@@ -312,6 +312,7 @@ __global__ __launch_bounds__(64) void moe_scan_kernel(int *__restrict__ blk_cnt,
     __syncthreads();
     if (e < E) {
         meta[64 + e] = seg[e];
+        meta[MOE_META_COUNTS + e] = cnt[e];   // (read by the router's gradient: the shares f_e of the load-balancing loss)
         const int nt = (cnt[e] + MOE_BM - 1) / MOE_BM;
         for (int i = 0; i < nt; ++i) tile_tab[tbase[e] + i] = make_int2(e, seg[e] + i * MOE_BM);
     }
@@ -521,12 +522,13 @@ __global__ __launch_bounds__(256, 2) void moe_gemm_kernel(MoeGemmArgs g) {
 }
 
 template <int EPI>
-static int moe_gemm_launch(const MoeGemmArgs &g, int64_t rows, hipStream_t stream) {
+static int moe_gemm_launch(const MoeGemmArgs &g, int64_t rows, hipStream_t stream,
+                           int prof_id = EPI == MG_GELU_PAIR ? MPREID_PROF_MOE_FC1 : MPREID_PROF_MOE_FC2) {
     int rc = mpreid_dyn_lds(moe_gemm_kernel<EPI>, (size_t)MG_LDS_BYTES);
     if (rc) return rc;
     void *ptok = mpreid_prof_begin(stream);
     hipLaunchKernelGGL(moe_gemm_kernel<EPI>, dim3((unsigned)((int64_t)g.tiles_max * g.tiles_n)), dim3(256), MG_LDS_BYTES, stream, g);
-    mpreid_prof_end(ptok, stream, EPI == MG_GELU_PAIR ? MPREID_PROF_MOE_FC1 : MPREID_PROF_MOE_FC2, rows, g.N, 2 * g.kseg, 0.0);
+    mpreid_prof_end(ptok, stream, prof_id, rows, g.N, 2 * g.kseg, 0.0);
     LAUNCH_CHECK();
     return MPREID_OK;
 }
@@ -561,8 +563,8 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(const float *__restric
     *reinterpret_cast<float4 *>(x + row * W + c) = xv;
 }
 
-int moe_mlp_launch(const _Float16 *a_pairs, const MoeLayout &m, const mpreid_moe_layer *ly, float *x, void *ws,
-                   hipStream_t stream) {
+int moe_experts_launch(const _Float16 *a_pairs, const MoeLayout &m, const mpreid_moe_layer *ly, void *ws, float *u_out,
+                       hipStream_t stream) {
     char *base = (char *)ws;
     const int W = m.W;
     MoeGemmArgs g{};
@@ -578,9 +580,13 @@ int moe_mlp_launch(const _Float16 *a_pairs, const MoeLayout &m, const mpreid_moe
     g.N = 4 * W;
     g.kseg = W;
     g.tiles_n = g.N / 128;
+    int rc;
+    if (u_out) {   // the gradient's recompute: the same accumulator through the fp32 epilogue, acc * s + b = the value QuickGELU sees
+        g.out = u_out;
+        if ((rc = moe_gemm_launch<MG_F32>(g, m.rows, stream, MPREID_PROF_MOE_GRAD_U))) return rc;
+    }
     g.out = base + m.hidden;
-    int rc = moe_gemm_launch<MG_GELU_PAIR>(g, m.rows, stream);
-    if (rc) return rc;
+    if ((rc = moe_gemm_launch<MG_GELU_PAIR>(g, m.rows, stream))) return rc;
     // FC2: slot order in, slot order out
     g.A = (const _Float16 *)(base + m.hidden);
     g.gather = nullptr;
@@ -591,7 +597,15 @@ int moe_mlp_launch(const _Float16 *a_pairs, const MoeLayout &m, const mpreid_moe
     g.kseg = 4 * W;
     g.tiles_n = g.N / 128;
     g.out = base + m.y;
-    if ((rc = moe_gemm_launch<MG_F32>(g, m.rows, stream))) return rc;
+    return moe_gemm_launch<MG_F32>(g, m.rows, stream);
+}
+
+int moe_mlp_launch(const _Float16 *a_pairs, const MoeLayout &m, const mpreid_moe_layer *ly, float *x, void *ws,
+                   hipStream_t stream) {
+    char *base = (char *)ws;
+    const int W = m.W;
+    int rc = moe_experts_launch(a_pairs, m, ly, ws, nullptr, stream);
+    if (rc) return rc;
     const int64_t n4 = m.rows * (W / 4);
     void *ptok = mpreid_prof_begin(stream);
     hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, (const float *)(base + m.y),

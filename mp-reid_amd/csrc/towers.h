@@ -69,6 +69,11 @@ int vit_block_attention(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer
                         int M, int Mpad, hipStream_t stream);
 int vit_block_mlp_recompute(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *u, int M,
                             int Mpad, hipStream_t stream);
+// vit_block_mid: only x += out_proj(a), a = ln_2(x) as pairs (what an MoE block runs in front of its router and experts)
+int vit_block_mid(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, int M, int Mpad,
+                  hipStream_t stream);
+// the checks of an MoE tower call (vit.hip): the tower's shape, the row limit at this batch, the gate, every MoE block
+int vit_check_moe_call(const mpreid_vit_cfg *cfg, const mpreid_vit_moe *moe, int B);
 
 // text_grad.hip: the kernels the image tower's sweep borrows
 int launch_layernorm_backward(const float *x, const float *dy, const float *g, int64_t rows, int W, bool acc, float *out,

@@ -325,9 +325,10 @@ extern "C" size_t mpreid_vit_workspace_bytes(const mpreid_vit_cfg *cfg, int batc
 // The MoE forward's share of the workspace, behind the dense layout: the routing of block 0 and the routed-MLP workspace
 struct VitMoeLayout {
     MoeLayout m;
-    size_t sel, w, moe, total;
+    size_t sel, w, moe, logits, route, total;   // logits / route: the training forward's router logits and l_aux tables
+    float *logits_dst = nullptr;                // where block 0's router writes its logits (nullptr: nowhere)
 };
-static VitMoeLayout vit_moe_layout(const mpreid_vit_cfg *c, const mpreid_vit_moe *moe, int B) {
+static VitMoeLayout vit_moe_layout(const mpreid_vit_cfg *c, const mpreid_vit_moe *moe, int B, bool train = false) {
     const VitLayout v = vit_layout(c, B);
     VitMoeLayout o{};
     o.m = moe_layout((int64_t)v.M, c->width, moe->num_experts, moe->top_k);
@@ -335,6 +336,10 @@ static VitMoeLayout vit_moe_layout(const mpreid_vit_cfg *c, const mpreid_vit_moe
     o.sel = take((size_t)v.M * moe->top_k * 4);
     o.w = take((size_t)v.M * moe->top_k * 4);
     o.moe = take(o.m.total);   // (a multiple of 256 already: moe_layout)
+    if (train) {               // mpreid_vit_forward_train_moe: the router's logits and the tables of l_aux
+        o.logits = take((size_t)v.M * moe->num_experts * 4);
+        o.route = take(moe_route_grad_bytes((int64_t)v.M, moe->num_experts));
+    }
     o.total = take.off;
     return o;
 }
@@ -399,6 +404,19 @@ static int block_attention_part(const BlockCtx &c, const mpreid_vit_layer &ly, c
     return rc ? rc : attention_profiled(c, qkv, a, kind);
 }
 
+// xr += out_proj(ar) (the block's mid-point); ar = ln_2(xr) as the MLP's operand
+static int block_mid_part(const BlockCtx &c, const mpreid_vit_layer &ly, float *xr, _Float16 *ar, int rows, int rows_pad) {
+    const int W = c.W;
+    GemmArgs g{};
+    g.A = ar; g.W = (const _Float16 *)ly.out_proj_w; g.M = rows_pad; g.N = W;
+    g.out = xr; g.ldo = W; g.bias = ly.out_proj_b;
+    const int rc = linear(c, g, W, ly.out_proj_s, GE_BIAS_RES, GE_S_BIAS_RES);
+    if (rc) return rc;
+    block_layernorm(c, xr, rows, ly.ln2_g, ly.ln2_b, ar);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
 // xr += out_proj(ar); xr += mlp(ln_2(xr)) over `rows` rows (rows_pad: the GEMMs' row count; hr: the MLP's hidden buffer).
 // Blocks l < moe->moe_layers of an MoE tower (moe != nullptr; vm places its workspace share behind base) run router and
 // dispatch (l == 0 only), grouped FC1 / FC2 and combine (csrc/moe.hip) in place of FC1 and FC2
@@ -409,19 +427,15 @@ static int block_mlp_part(const BlockCtx &c, const mpreid_vit_layer &ly, float *
                           float *fc1_f32 = nullptr) {
     const int W = c.W;
     int rc;
+    if ((rc = block_mid_part(c, ly, xr, ar, rows, rows_pad))) return rc;
     GemmArgs g{};
-    g.A = ar; g.W = (const _Float16 *)ly.out_proj_w; g.M = rows_pad; g.N = W;
-    g.out = xr; g.ldo = W; g.bias = ly.out_proj_b;
-    if ((rc = linear(c, g, W, ly.out_proj_s, GE_BIAS_RES, GE_S_BIAS_RES))) return rc;
-    block_layernorm(c, xr, rows, ly.ln2_g, ly.ln2_b, ar);
-    LAUNCH_CHECK();
     if (moe && l < moe->moe_layers) {
         char *mws = base + vm->moe;
         int32_t *sel = (int32_t *)(base + vm->sel);
         float *rw = (float *)(base + vm->w);
         if (l == 0) {
             if ((rc = moe_route_launch(xr, (int64_t)rows, W, ly.ln2_g, ly.ln2_b, moe->layers[0].gate_w, moe->num_experts,
-                                       moe->top_k, sel, rw, nullptr, c.stream)))
+                                       moe->top_k, sel, rw, vm->logits_dst, c.stream)))
                 return rc;
             if ((rc = moe_dispatch_launch(sel, rw, vm->m, mws, c.stream))) return rc;
         }
@@ -486,6 +500,7 @@ static int vit_embed_tokens_impl(const BlockCtx &ctx, const mpreid_vit_cfg *cfg,
 // The three features of the training forward (mpreid_vit_forward_train) in place of `out`: no neck, f | f_proj apart
 struct TrainOut {
     float *f_last, *f, *f_proj;   // [B][W], [B][W], [B][out_dim]
+    float *logits, *l_aux;        // an MoE tower's router logits [B * L][E] and load-balancing loss [1]; either may be nullptr
 };
 
 // moe == nullptr: the dense tower (mpreid_vit_forward).  Otherwise blocks l < moe->moe_layers run the routed MLP.
@@ -508,7 +523,7 @@ static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights 
     VitMoeLayout vm{};
     if (moe) {
         ARG_CHECK(((uintptr_t)ws & 255) == 0 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)cv_emb & 3) == 0);
-        vm = vit_moe_layout(cfg, moe, B);
+        vm = vit_moe_layout(cfg, moe, B, tr != nullptr);
     }
     const size_t ws_need = moe ? vm.total : v.total;
     if (!ws || ws_bytes < ws_need) {
@@ -531,6 +546,7 @@ static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights 
     const bool cls_last = cfg->cls_only_last != 0 && cfg->layers > 0 && n_moe < cfg->layers;
     const bool split = cfg->precision != MPREID_VIT_F16;
     const BlockCtx ctx{stream, split, split ? 2 : 1, W, cfg->heads, B, L};
+    if (tr && moe && (tr->logits || tr->l_aux)) vm.logits_dst = (float *)(base + vm.logits);
 
     // patch embedding (conv1, no bias) + positional embedding; CLS row; ln_pre
     if ((rc = vit_embed_tokens_impl(ctx, cfg, w, in, B, cv_emb, v, patches, x))) return rc;
@@ -542,7 +558,7 @@ static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights 
         // in the last block only the CLS row reaches the output (model/make_model.py:98-100): the
         // attention runs the first query tile only and everything after it runs on the B CLS rows.
         const bool tail = cls_last && (l == cfg->layers - 1);
-        if (tr && l == cfg->layers - 1)   // f_last: the CLS row of the last block's input (model/clip/model.py:458-468)
+        if (tr && !moe && l == cfg->layers - 1)   // f_last: the CLS row of the last block's input (model/clip/model.py:458-468)
             HIP_TRY(hipMemcpy2DAsync(tr->f_last, (size_t)W * 4, x, (size_t)L * W * 4, (size_t)W * 4, (size_t)B,
                                      hipMemcpyDeviceToDevice, stream));
         if ((rc = block_attention_part(ctx, ly, x, a, qkv, v.M, v.Mpad, tail ? ATTN_CLS_TILE : ATTN_ALL_ROWS))) return rc;
@@ -553,6 +569,24 @@ static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights 
         if ((rc = tail ? block_mlp_part(ctx, ly, x_cls, a_cls, h_cls, B, v.Bpad, moe, l, &vm, base)
                        : block_mlp_part(ctx, ly, x, a, hbuf, v.M, v.Mpad, moe, l, &vm, base)))
             return rc;
+    }
+    if (tr && moe) {
+        // with MoE the tower hands out x11 = x12 = the transformer's output (model/clip/model.py:448-454): f_last is the CLS
+        // row of the LAST block's OUTPUT
+        const float *xo = cls_last ? x_cls : x;
+        HIP_TRY(hipMemcpy2DAsync(tr->f_last, (size_t)W * 4, xo, cls_last ? (size_t)W * 4 : (size_t)L * W * 4, (size_t)W * 4,
+                                 (size_t)B, hipMemcpyDeviceToDevice, stream));
+        if (vm.logits_dst) {
+            const size_t lbytes = (size_t)v.M * moe->num_experts * 4;
+            if (tr->logits) HIP_TRY(hipMemcpyAsync(tr->logits, vm.logits_dst, lbytes, hipMemcpyDeviceToDevice, stream));
+            if (tr->l_aux) {
+                if ((rc = moe_route_backward_ws(vm.logits_dst, (const int32_t *)(base + vm.sel), (const float *)(base + vm.w),
+                                                nullptr, v.M, moe->num_experts, moe->top_k, 0.f, nullptr, tr->l_aux,
+                                                (const int *)(base + vm.moe + vm.m.meta) + MOE_META_COUNTS, base + vm.route,
+                                                stream)))
+                    return rc;
+            }
+        }
     }
     if (tr)   // the head's own kernels: the normalised rows land in f (the forward's scratch y), the projection in f_proj
         return tower_head(cls_last ? x_cls : x, cls_last ? (int64_t)W : (int64_t)L * W, nullptr, 1, B, W, cfg->out_dim,
@@ -566,7 +600,7 @@ extern "C" int mpreid_vit_forward_train(const mpreid_vit_cfg *cfg, const mpreid_
                                         mpreid_stream_t stream_) {
     ARG_CHECK(f_last && f && f_proj);
     ARG_CHECK((((uintptr_t)f_last | (uintptr_t)f | (uintptr_t)f_proj) & 3) == 0);
-    const TrainOut tr{f_last, f, f_proj};
+    const TrainOut tr{f_last, f, f_proj, nullptr, nullptr};
     return vit_forward_impl(cfg, w, nullptr, img, B, cv_emb, nullptr, ws, ws_bytes, stream_, &tr);
 }
 
@@ -596,9 +630,8 @@ extern "C" size_t mpreid_vit_workspace_bytes_moe(const mpreid_vit_cfg *cfg, cons
     return vit_moe_layout(cfg, moe, batch).total;
 }
 
-extern "C" int mpreid_vit_forward_moe(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_moe *moe,
-                                      const mpreid_image_in *img, int B, const float *cv_emb, float *out, void *ws,
-                                      size_t ws_bytes, mpreid_stream_t stream_) {
+// the checks of an MoE tower call that need the batch: the row limit, the gate, every MoE block's pointers
+int vit_check_moe_call(const mpreid_vit_cfg *cfg, const mpreid_vit_moe *moe, int B) {
     int rc = vit_check_moe(cfg, moe);
     if (rc) return rc;
     ARG_CHECK(B > 0);
@@ -609,7 +642,42 @@ extern "C" int mpreid_vit_forward_moe(const mpreid_vit_cfg *cfg, const mpreid_vi
         for (int l = 0; l < moe->moe_layers; ++l)
             if ((rc = moe_check_layer(&moe->layers[l]))) return rc;
     }
+    return MPREID_OK;
+}
+
+extern "C" int mpreid_vit_forward_moe(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_moe *moe,
+                                      const mpreid_image_in *img, int B, const float *cv_emb, float *out, void *ws,
+                                      size_t ws_bytes, mpreid_stream_t stream_) {
+    const int rc = vit_check_moe_call(cfg, moe, B);
+    if (rc) return rc;
     return vit_forward_impl(cfg, w, moe, img, B, cv_emb, out, ws, ws_bytes, stream_);
+}
+
+static int vit_check_moe_train(const mpreid_vit_moe *moe) {
+    if (moe->moe_layers < 1) {
+        mpreid_set_error("the MoE training entry points need at least one MoE block (moe_layers %d): a tower without one is the "
+                         "dense tower of mpreid_vit_forward_train / mpreid_vit_backward", moe->moe_layers);
+        return MPREID_ERR_UNSUPPORTED;
+    }
+    return MPREID_OK;
+}
+
+extern "C" size_t mpreid_vit_forward_train_moe_workspace_bytes(const mpreid_vit_cfg *cfg, const mpreid_vit_moe *moe, int batch) {
+    if (!cfg || !moe || batch <= 0 || vit_check_moe(cfg, moe) || vit_check_moe_train(moe)) return 0;
+    return vit_moe_layout(cfg, moe, batch, true).total;
+}
+
+extern "C" int mpreid_vit_forward_train_moe(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_moe *moe,
+                                            const mpreid_image_in *img, int B, const float *cv_emb, float *f_last, float *f,
+                                            float *f_proj, float *logits_out, float *l_aux_out, void *ws, size_t ws_bytes,
+                                            mpreid_stream_t stream_) {
+    int rc = vit_check_moe_call(cfg, moe, B);
+    if (rc) return rc;
+    if ((rc = vit_check_moe_train(moe))) return rc;
+    ARG_CHECK(f_last && f && f_proj);
+    ARG_CHECK((((uintptr_t)f_last | (uintptr_t)f | (uintptr_t)f_proj | (uintptr_t)logits_out | (uintptr_t)l_aux_out) & 3) == 0);
+    const TrainOut tr{f_last, f, f_proj, logits_out, l_aux_out};
+    return vit_forward_impl(cfg, w, moe, img, B, cv_emb, nullptr, ws, ws_bytes, stream_, &tr);
 }
 
 // =============================================================================================
@@ -764,6 +832,12 @@ int vit_block_attention(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer
                         int M, int Mpad, hipStream_t stream) {
     const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, cfg->h_res * cfg->w_res + 1};
     return block_attention_part(ctx, ly, x, a, qkv, M, Mpad, ATTN_ALL_ROWS);
+}
+
+int vit_block_mid(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, int M, int Mpad,
+                  hipStream_t stream) {
+    const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, cfg->h_res * cfg->w_res + 1};
+    return block_mid_part(ctx, ly, x, a, M, Mpad);
 }
 
 int vit_block_mlp_recompute(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *u, int M,

@@ -4,6 +4,7 @@
 // over a small workspace of row statistics and streams the other operand through LDS in 64-row blocks, so its LDS request
 // does not depend on which operand is long.  No atomics: every sum has one fixed order, the same bits from run to run and
 // for an image alone or inside a batch.
+#include "moe.h"
 #include "towers.h"
 
 namespace {
@@ -434,9 +435,13 @@ struct VitGradLayout {
     VitLayout f;
     int64_t Mp4, Bp4, tw;
     size_t tok, xs, dx, dh, t, dqkv, aot, at, bt, stats, red, small, total;
+    // an MoE tower's share, behind the dense sweep's: the routing of block 0, its logits, d_w summed over the MoE blocks,
+    // d_logits, and the routed MLP's gradient workspace (tables of the dispatch, hidden, y, u)
+    MoeGradLayout mg;
+    size_t sel, rw, logits, d_w, d_logits, moe;
 };
 
-VitGradLayout vit_grad_layout(const mpreid_vit_cfg *c, int B) {
+VitGradLayout vit_grad_layout(const mpreid_vit_cfg *c, int B, const mpreid_vit_moe *moe = nullptr) {
     VitGradLayout v{};
     v.f = vit_layout(c, B);
     const size_t W = (size_t)c->width;
@@ -461,6 +466,16 @@ VitGradLayout vit_grad_layout(const mpreid_vit_cfg *c, int B) {
     const size_t red_pos = colsum_ws_bytes(B, (int64_t)v.f.L * (int64_t)W);
     v.red = take(red > red_pos ? red : red_pos);   // the column reductions' partial sums and row statistics
     v.small = take(4 * align_up((size_t)B * W * 4, 256));   // CLS rows of x, the head's seed, f, the CLS rows' gradient
+    if (moe) {
+        const size_t E = (size_t)moe->num_experts, K = (size_t)moe->top_k, M = (size_t)v.f.M;
+        v.mg = moe_grad_layout((int64_t)M, c->width, moe->num_experts, moe->top_k);
+        v.sel = take(M * K * 4);
+        v.rw = take(M * K * 4);
+        v.logits = take(M * E * 4);
+        v.d_w = take(M * K * 4);
+        v.d_logits = take(M * E * 4);
+        v.moe = take(v.mg.total);
+    }
     v.total = take.off;
     return v;
 }
@@ -508,12 +523,32 @@ extern "C" size_t mpreid_vit_backward_workspace_bytes(const mpreid_vit_cfg *cfg,
     return vit_grad_layout(cfg, batch).total;
 }
 
-extern "C" int mpreid_vit_backward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_weights_t *wt,
-                                   const mpreid_image_in *img, int B, const float *cv_emb, const float *d_f_last,
-                                   const float *d_f, const float *d_f_proj, const mpreid_vit_grads *grads, float *d_tokens,
-                                   void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
+// The sweep of both towers.  moe == nullptr: the dense tower.  Otherwise blocks l < moe->moe_layers (at least one) carry the
+// routed MLP: their MLP half goes through csrc/moe_grad.hip, everything else through the same code as a dense block's.
+static int vit_backward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_weights_t *wt,
+                             const mpreid_vit_moe *moe, const mpreid_vit_moe_t *moe_t, float aux_coef, float *d_gate_w,
+                             float *l_aux_out, const mpreid_image_in *img, int B, const float *cv_emb, const float *d_f_last,
+                             const float *d_f, const float *d_f_proj, const mpreid_vit_grads *grads, float *d_tokens, void *ws,
+                             size_t ws_bytes, mpreid_stream_t stream_) {
     int rc = vit_backward_check_cfg(cfg);
     if (rc) return rc;
+    const int n_moe = moe ? moe->moe_layers : 0;
+    if (moe) {
+        if ((rc = vit_check_moe_call(cfg, moe, B))) return rc;
+        if (n_moe < 1) {
+            mpreid_set_error("mpreid_vit_backward_moe needs at least one MoE block (moe_layers %d): a tower without one is the "
+                             "dense tower of mpreid_vit_backward", n_moe);
+            return MPREID_ERR_UNSUPPORTED;
+        }
+        ARG_CHECK(moe_t && moe_t->layers);
+        for (int l = 0; l < n_moe; ++l) {
+            const mpreid_moe_layer_t &t = moe_t->layers[l];
+            ARG_CHECK(t.fc_t && t.proj_t && (((uintptr_t)t.fc_t | (uintptr_t)t.proj_t) & 15) == 0);
+        }
+        // (asked of moe_grad.hip: this file is compiled with -ffinite-math-only, which folds any test for NaN or infinity away)
+        ARG_CHECK(moe_coef_is_finite(aux_coef));
+        ARG_CHECK((((uintptr_t)d_gate_w | (uintptr_t)l_aux_out) & 3) == 0);
+    }
     mpreid_image_in in;
     if ((rc = mpreid_check_image_in(img, &in))) return rc;
     ARG_CHECK(w && wt && B > 0 && w->layers && wt->layers);
@@ -521,15 +556,16 @@ extern "C" int mpreid_vit_backward(const mpreid_vit_cfg *cfg, const mpreid_vit_w
     ARG_CHECK(!grads || grads->layers);
     ARG_CHECK((((uintptr_t)cv_emb | (uintptr_t)d_f_last | (uintptr_t)d_f | (uintptr_t)d_f_proj) & 3) == 0 &&
               ((uintptr_t)d_tokens & 15) == 0);
-    const VitGradLayout v = vit_grad_layout(cfg, B);
+    const VitGradLayout v = vit_grad_layout(cfg, B, moe);
     ARG_CHECK((int64_t)B * v.f.L <= ((int64_t)1 << 31) - 256);   // GemmArgs::M is an int
     ARG_CHECK(colsum_pieces((int64_t)B * v.f.L) <= 65535);       // launch_colsum: the pieces are the grid's y
     for (int l = 0; l < cfg->layers; ++l) {
         const mpreid_vit_layer_t &t = wt->layers[l];
-        ARG_CHECK(t.in_proj_t && t.out_proj_t && t.fc_t && t.proj_t);
+        ARG_CHECK(t.in_proj_t && t.out_proj_t && (l < n_moe || (t.fc_t && t.proj_t)));   // an MoE block has no dense MLP
         ARG_CHECK((((uintptr_t)t.in_proj_t | (uintptr_t)t.out_proj_t | (uintptr_t)t.fc_t | (uintptr_t)t.proj_t) & 15) == 0);
         if (grads) {
             const mpreid_vit_layer_grads &g = grads->layers[l];
+            ARG_CHECK(l >= n_moe || !(g.fc_w || g.fc_b || g.proj_w || g.proj_b));
             ARG_CHECK((((uintptr_t)g.in_proj_w | (uintptr_t)g.in_proj_b | (uintptr_t)g.out_proj_w | (uintptr_t)g.out_proj_b |
                         (uintptr_t)g.fc_w | (uintptr_t)g.fc_b | (uintptr_t)g.proj_w | (uintptr_t)g.proj_b | (uintptr_t)g.ln1_g |
                         (uintptr_t)g.ln1_b | (uintptr_t)g.ln2_g | (uintptr_t)g.ln2_b) & 3) == 0);
@@ -571,6 +607,12 @@ extern "C" int mpreid_vit_backward(const mpreid_vit_cfg *cfg, const mpreid_vit_w
     const size_t xbytes = (size_t)M * W * 4, xstride = (size_t)Mpad * W;
     const size_t rowb = (size_t)W * 4, seqb = (size_t)L * W * 4;
     const mpreid_vit_layer_grads none{};
+    // the MoE share (untouched offsets of a dense tower are never used)
+    int32_t *sel = (int32_t *)(base + v.sel);
+    float *rw = (float *)(base + v.rw), *logits = (float *)(base + v.logits), *d_w = (float *)(base + v.d_w),
+          *d_logits = (float *)(base + v.d_logits);
+    char *mws = base + v.moe;
+    const int E = moe ? moe->num_experts : 0, K = moe ? moe->top_k : 0;
     // dW [n][k] = sum_m dY[m][n] X[m][k]: at = dY^T and bt = X^T hold the operands
     auto wgrad = [&](float *out, int n, int k) {
         return mpreid_gemm_f32_linear(at, bt, n, k, (int)Mp4, nullptr, out, k, F32_LIN, stream);
@@ -581,7 +623,19 @@ extern "C" int mpreid_vit_backward(const mpreid_vit_cfg *cfg, const mpreid_vit_w
     if ((rc = vit_layernorm_f32(tok, M, W, w->ln_pre_g, w->ln_pre_b, x, stream))) return rc;
     for (int l = 0; l < cfg->layers; ++l) {
         HIP_TRY(hipMemcpyAsync(xs + l * xstride, x, xbytes, hipMemcpyDeviceToDevice, stream));
-        if ((rc = vit_block(cfg, B, w->layers[l], x, a, qkv, hbuf, M, Mpad, stream))) return rc;
+        if (l >= n_moe) {
+            if ((rc = vit_block(cfg, B, w->layers[l], x, a, qkv, hbuf, M, Mpad, stream))) return rc;
+            continue;
+        }
+        // an MoE block, launch for launch what mpreid_vit_forward_moe runs; block 0 keeps its routing and logits
+        const mpreid_vit_layer &ly = w->layers[l];
+        if ((rc = vit_block_attention(cfg, B, ly, x, a, qkv, M, Mpad, stream))) return rc;
+        if ((rc = vit_block_mid(cfg, B, ly, x, a, M, Mpad, stream))) return rc;
+        if (l == 0) {
+            if ((rc = moe_route_launch(x, M, W, ly.ln2_g, ly.ln2_b, moe->layers[0].gate_w, E, K, sel, rw, logits, stream))) return rc;
+            if ((rc = moe_dispatch_launch(sel, rw, v.mg.fwd, mws, stream))) return rc;
+        }
+        if ((rc = moe_mlp_launch(a, v.mg.fwd, &moe->layers[l], x, mws, stream))) return rc;
     }
     // the head at the CLS rows: f = ln_post(x[:, 0]), f_proj = f @ proj
     HIP_TRY(hipMemcpy2DAsync(xc, rowb, x, seqb, rowb, (size_t)B, hipMemcpyDeviceToDevice, stream));
@@ -602,6 +656,15 @@ extern "C" int mpreid_vit_backward(const mpreid_vit_cfg *cfg, const mpreid_vit_w
     if ((rc = launch_layernorm_backward(xc, hy, w->ln_post_g, B, W, false, dxc, stream))) return rc;
     HIP_TRY(hipMemsetAsync(dx, 0, xbytes, stream));
     HIP_TRY(hipMemcpy2DAsync(dx, seqb, dxc, rowb, rowb, (size_t)B, hipMemcpyDeviceToDevice, stream));
+    auto seed_f_last = [&]() -> int {
+        hipLaunchKernelGGL(add_cls_rows_kernel, dim3((unsigned)(((int64_t)B * W + 255) / 256)), dim3(256), 0, stream, d_f_last, B, L,
+                           W, dx);
+        LAUNCH_CHECK();
+        return MPREID_OK;
+    };
+    // an MoE tower's f_last is the CLS row of the LAST block's OUTPUT (model/clip/model.py:448-454): its seed joins dx in
+    // front of the sweep
+    if (moe && d_f_last && (rc = seed_f_last())) return rc;
 
     for (int l = cfg->layers - 1; l >= 0; --l) {
         const mpreid_vit_layer &ly = w->layers[l];
@@ -611,23 +674,43 @@ extern "C" int mpreid_vit_backward(const mpreid_vit_cfg *cfg, const mpreid_vit_w
         HIP_TRY(hipMemcpyAsync(x, xl, xbytes, hipMemcpyDeviceToDevice, stream));
         if ((rc = vit_block_attention(cfg, B, ly, x, a, qkv, M, Mpad, stream))) return rc;
         if (g.out_proj_w && (rc = launch_transpose(2, a, M, W, 2 * W, 0, aot, Mp4, stream))) return rc;
-        if ((rc = vit_block_mlp_recompute(cfg, B, ly, x, a, u, M, Mpad, stream))) return rc;   // x = x_mid, a = ln_2(x_mid)
-        // x_{l+1} = x_mid + c_proj(quickgelu(c_fc(ln_2(x_mid))))
-        if (g.proj_w) {   // X = quickgelu(u), the fp32 value the forward's hidden pair is split from
-            if ((rc = launch_transpose(0, dx, M, W, W, 0, at, Mp4, stream))) return rc;
-            if ((rc = launch_transpose(1, u, M, 4 * W, 4 * W, 0, bt, Mp4, stream))) return rc;
-            if ((rc = wgrad(g.proj_w, W, 4 * W))) return rc;
+        if (l < n_moe) {
+            // x_{l+1} = x_mid + sum_e w_e expert_e(ln_2(x_mid)): t = d/dh through the experts, d_w summed over the MoE blocks
+            if ((rc = vit_block_mid(cfg, B, ly, x, a, M, Mpad, stream))) return rc;   // x = x_mid, a = ln_2(x_mid)
+            if ((rc = moe_mlp_backward_launch(a, sel, v.mg, &moe->layers[l], &moe_t->layers[l], dx, t, d_w, l != n_moe - 1, mws,
+                                              stream)))
+                return rc;
+            if (l == 0) {   // every MoE block has added to d_w: the router, its gate, and the gate's share of d/dh
+                if ((rc = moe_route_backward_ws(logits, sel, rw, d_w, M, E, K, aux_coef, d_logits, l_aux_out,
+                                                (const int *)(mws + v.mg.fwd.meta) + MOE_META_COUNTS, mws + v.mg.cnt_blk, stream)))
+                    return rc;
+                if (d_gate_w) {   // d gate = d_logits^T . h, h the fp32 LayerNorm output the router saw
+                    if ((rc = vit_layernorm_f32(x, M, W, ly.ln2_g, ly.ln2_b, dh, stream))) return rc;
+                    if ((rc = launch_transpose(0, d_logits, M, E, E, 0, at, Mp4, stream))) return rc;
+                    if ((rc = launch_transpose(0, dh, M, W, W, 0, bt, Mp4, stream))) return rc;
+                    if ((rc = wgrad(d_gate_w, E, W))) return rc;
+                }
+                if ((rc = moe_gate_dh_launch(d_logits, moe->layers[0].gate_w, M, W, E, t, stream))) return rc;
+            }
+        } else {
+            if ((rc = vit_block_mlp_recompute(cfg, B, ly, x, a, u, M, Mpad, stream))) return rc;   // x = x_mid, a = ln_2(x_mid)
+            // x_{l+1} = x_mid + c_proj(quickgelu(c_fc(ln_2(x_mid))))
+            if (g.proj_w) {   // X = quickgelu(u), the fp32 value the forward's hidden pair is split from
+                if ((rc = launch_transpose(0, dx, M, W, W, 0, at, Mp4, stream))) return rc;
+                if ((rc = launch_transpose(1, u, M, 4 * W, 4 * W, 0, bt, Mp4, stream))) return rc;
+                if ((rc = wgrad(g.proj_w, W, 4 * W))) return rc;
+            }
+            if ((rc = launch_colsum(dx, W, nullptr, 0, M, W, g.proj_b, nullptr, red, stream))) return rc;
+            if ((rc = mpreid_gemm_f32_linear(dx, lt.proj_t, M, 4 * W, W, nullptr, dh, 4 * W, F32_LIN, stream))) return rc;
+            if ((rc = launch_quickgelu_backward(u, dh, (int64_t)M * W, stream))) return rc;   // dh = d/du
+            if (g.fc_w) {
+                if ((rc = launch_transpose(0, dh, M, 4 * W, 4 * W, 0, at, Mp4, stream))) return rc;
+                if ((rc = launch_transpose(2, a, M, W, 2 * W, 0, bt, Mp4, stream))) return rc;
+                if ((rc = wgrad(g.fc_w, 4 * W, W))) return rc;
+            }
+            if ((rc = launch_colsum(dh, 4 * W, nullptr, 0, M, 4 * W, g.fc_b, nullptr, red, stream))) return rc;
+            if ((rc = mpreid_gemm_f32_linear(dh, lt.fc_t, M, W, 4 * W, nullptr, t, W, F32_LIN, stream))) return rc;
         }
-        if ((rc = launch_colsum(dx, W, nullptr, 0, M, W, g.proj_b, nullptr, red, stream))) return rc;
-        if ((rc = mpreid_gemm_f32_linear(dx, lt.proj_t, M, 4 * W, W, nullptr, dh, 4 * W, F32_LIN, stream))) return rc;
-        if ((rc = launch_quickgelu_backward(u, dh, (int64_t)M * W, stream))) return rc;   // dh = d/du
-        if (g.fc_w) {
-            if ((rc = launch_transpose(0, dh, M, 4 * W, 4 * W, 0, at, Mp4, stream))) return rc;
-            if ((rc = launch_transpose(2, a, M, W, 2 * W, 0, bt, Mp4, stream))) return rc;
-            if ((rc = wgrad(g.fc_w, 4 * W, W))) return rc;
-        }
-        if ((rc = launch_colsum(dh, 4 * W, nullptr, 0, M, 4 * W, g.fc_b, nullptr, red, stream))) return rc;
-        if ((rc = mpreid_gemm_f32_linear(dh, lt.fc_t, M, W, 4 * W, nullptr, t, W, F32_LIN, stream))) return rc;
         if ((rc = launch_colsum(t, W, x, W, M, W, g.ln2_b, g.ln2_g, red, stream))) return rc;
         if ((rc = launch_layernorm_backward(x, t, ly.ln2_g, M, W, true, dx, stream))) return rc;   // dx = d/dx_mid
         // x_mid = x_l + out_proj(attention(in_proj(ln_1(x_l))))
@@ -648,11 +731,8 @@ extern "C" int mpreid_vit_backward(const mpreid_vit_cfg *cfg, const mpreid_vit_w
         if ((rc = mpreid_gemm_f32_linear(dqkv, lt.in_proj_t, M, W, 3 * W, nullptr, t, W, F32_LIN, stream))) return rc;
         if ((rc = launch_colsum(t, W, xl, W, M, W, g.ln1_b, g.ln1_g, red, stream))) return rc;
         if ((rc = launch_layernorm_backward(xl, t, ly.ln1_g, M, W, true, dx, stream))) return rc;   // dx = d/dx_l
-        if (l == cfg->layers - 1 && d_f_last) {   // f_last is the CLS row of the last block's input
-            hipLaunchKernelGGL(add_cls_rows_kernel, dim3((unsigned)(((int64_t)B * W + 255) / 256)), dim3(256), 0, stream, d_f_last,
-                               B, L, W, dx);
-            LAUNCH_CHECK();
-        }
+        // the dense tower's f_last is the CLS row of the last block's input
+        if (!moe && l == cfg->layers - 1 && d_f_last && (rc = seed_f_last())) return rc;
     }
     // ln_pre, then the embedding: tokens = [class_emb + cv_emb | conv1(patches)] + pos_emb
     if (grads && (rc = launch_colsum(dx, W, tok, W, M, W, grads->ln_pre_b, grads->ln_pre_g, red, stream))) return rc;
@@ -672,4 +752,29 @@ extern "C" int mpreid_vit_backward(const mpreid_vit_cfg *cfg, const mpreid_vit_w
         if ((rc = mpreid_gemm_f32_linear(at, bt, W, v.f.Kp, (int)MP4, nullptr, grads->conv_w, v.f.Kp, F32_LIN, stream))) return rc;
     }
     return MPREID_OK;
+}
+
+extern "C" int mpreid_vit_backward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_weights_t *wt,
+                                   const mpreid_image_in *img, int B, const float *cv_emb, const float *d_f_last,
+                                   const float *d_f, const float *d_f_proj, const mpreid_vit_grads *grads, float *d_tokens,
+                                   void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
+    return vit_backward_impl(cfg, w, wt, nullptr, nullptr, 0.f, nullptr, nullptr, img, B, cv_emb, d_f_last, d_f, d_f_proj, grads,
+                             d_tokens, ws, ws_bytes, stream_);
+}
+
+extern "C" size_t mpreid_vit_backward_moe_workspace_bytes(const mpreid_vit_cfg *cfg, const mpreid_vit_moe *moe, int batch) {
+    if (!cfg || !moe || batch <= 0 || vit_backward_check_cfg(cfg) || moe->moe_layers < 1) return 0;
+    // (a query carries no pointers: only the shape checks of the call count)
+    if (vit_check_moe_call(cfg, moe, batch) == MPREID_ERR_UNSUPPORTED) return 0;
+    return vit_grad_layout(cfg, batch, moe).total;
+}
+
+extern "C" int mpreid_vit_backward_moe(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_weights_t *wt,
+                                       const mpreid_vit_moe *moe, const mpreid_vit_moe_t *moe_t, const mpreid_image_in *img, int B,
+                                       const float *cv_emb, const float *d_f_last, const float *d_f, const float *d_f_proj,
+                                       float aux_coef, const mpreid_vit_grads *grads, float *d_gate_w, float *d_tokens,
+                                       float *l_aux_out, void *ws, size_t ws_bytes, mpreid_stream_t stream_) {
+    ARG_CHECK(moe != nullptr);
+    return vit_backward_impl(cfg, w, wt, moe, moe_t, aux_coef, d_gate_w, l_aux_out, img, B, cv_emb, d_f_last, d_f, d_f_proj, grads,
+                             d_tokens, ws, ws_bytes, stream_);
 }

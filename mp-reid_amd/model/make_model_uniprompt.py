@@ -189,6 +189,20 @@ def split_text_checkpoint(param_dict, num_class):
     return {k: text[k] for k in want_t}, prompt, used
 
 
+LOAD_BALANCE_LOSS_COEFF = 0.01   # processor/processor_uniprompt_stage2.py:76 of the reference
+
+
+def load_balancing_loss_func(gate_logits, top_k):
+    """model/clip/model.py:342-377 restated: gate_logits [rows, E] of ONE layer -> E * sum_e f_e P_e, f_e the share of rows
+    whose top-k holds e (not differentiated), P_e the mean softmax probability of e.  The row order does not matter."""
+    num_experts = gate_logits.shape[-1]
+    gate_logits = gate_logits.reshape(-1, num_experts)
+    routing_weights = F.softmax(gate_logits, dim=-1)
+    _, selected = torch.topk(routing_weights, top_k, dim=-1)
+    tokens_per_expert = F.one_hot(selected, num_experts).float().mean(dim=0)
+    return (tokens_per_expert * routing_weights.mean(dim=0)).sum() * num_experts
+
+
 class build_transformer(_base.build_transformer):
     def __init__(self, num_classes, camera_num, view_num, cfg):
         eot = int(getattr(cfg.MODEL, "PROMPT_EOT_INDEX", 19))
@@ -206,7 +220,9 @@ class build_transformer(_base.build_transformer):
         self._text_source = None    # (text state dict, prompt tensors) of the last checkpoint that carried a complete set
         self._text_encoder = None
         self._text_sd = None        # the state dict self._text_encoder was built from (text_state_dict)
-        self._train_encoder = None  # enable_stage2_training()
+        self._train_encoder = None  # enable_stage2_training() / enable_stage2_moe_training()
+        self._moe_training = False  # enable_stage2_moe_training(): the explicit opt-in to train an MoE tower
+        self.router_aux_loss = None  # the last training forward's load-balancing loss [1], differentiable (MoE towers)
 
     def _invalidate(self):
         super()._invalidate()
@@ -219,18 +235,42 @@ class build_transformer(_base.build_transformer):
         return self
 
     # -- stage 2 ----------------------------------------------------------------------------------
-    def _check_stage2_tower(self):
+    def _is_moe(self):
+        return bool(self.vit_cfg.get("num_experts", 0) or self.vit_cfg.get("moe_layers", 0))
+
+    def _check_stage2_tower(self, moe_ok=False):
         if self.model_name == 'RN50':
             raise NotImplementedError("stage-2 training with MODEL.NAME 'RN50': the RN50 tower has no backward pass (missing: the "
                                       "gradient kernels of the ModifiedResNet); train the ViT-B-16 tower")
-        if self.vit_cfg.get("num_experts", 0) or self.vit_cfg.get("moe_layers", 0):
-            raise NotImplementedError("stage-2 training with MODEL.MOE.ENABLED: the MoE tower has no backward pass (missing: the "
-                                      "gradients of the router and of the grouped expert GEMMs); train the dense tower")
+        if self._is_moe() and not (moe_ok or self._moe_training):
+            raise NotImplementedError("stage-2 training with MODEL.MOE.ENABLED: the MoE tower has no backward pass behind this "
+                                      "call (missing: the expert matrices' own gradients -- the experts stay frozen, the gate "
+                                      "and the dense parts are trained); opt in with enable_stage2_moe_training()")
+
+    def enable_stage2_moe_training(self, device="cuda", set_requires_grad=True):
+        """enable_stage2_training() for an MoE tower, as an explicit opt-in: the reference's 2a marking does real work here --
+        every `expert` name is frozen (the gradient flows THROUGH the experts), block 0's gate and the dense parts are trained;
+        the gates of later blocks are never read (model/clip/model.py:310-322), so they get no gradient and nothing moves them.
+        set_requires_grad=False keeps the caller's marking, which must have frozen the experts already (an expert that requires
+        grad is the encoder's NotImplementedError: their own gradients are not implemented).
+        Afterwards a training-mode forward returns the 4-tuple (scores, feats, f_proj, router_logits), router_logits
+        [L * B, E] in the reference's flat order.  ValueError on a dense tower.  Returns self."""
+        if not self._is_moe():
+            raise ValueError("enable_stage2_moe_training: the tower has no MoE block (MODEL.MOE.ENABLED is off); "
+                             "call enable_stage2_training()")
+        self._check_stage2_tower(moe_ok=True)
+        self._moe_training = True
+        try:
+            return self.enable_stage2_training(device, set_requires_grad)
+        except Exception:
+            self._moe_training = False
+            raise
 
     def enable_stage2_training(self, device="cuda", set_requires_grad=True):
         """Stage 2a of the reference (train_uniprompt.py:137-154): every parameter requires grad except those whose name
         contains text_encoder, expert or prompt_learner; the module moves to the device; the training encoder is built on the
-        module's own image_encoder.* parameters (no copies); the folded evaluation encoders are dropped.  Returns self."""
+        module's own image_encoder.* parameters (no copies); the folded evaluation encoders are dropped.  Returns self.
+        An MoE tower: through enable_stage2_moe_training() only."""
         self._check_stage2_tower()
         print("Enabling Stage 2 Training: image tower, BNNeck, classifiers, SIE table.")
         self.to(device)
@@ -259,7 +299,7 @@ class build_transformer(_base.build_transformer):
         self._train_encoder.sync_weights_batched()
         return _ops.Stage2Trainer(self._train_encoder, self.stage2_head(cfg), optimizer, text_features,
                                   cv_table=self.cv_embed if sie else None, sie_coe=self.sie_coe, pixel_mean=self.pixel_mean,
-                                  pixel_std=self.pixel_std)
+                                  pixel_std=self.pixel_std, aux_coef=LOAD_BALANCE_LOSS_COEFF if self._is_moe() else None)
 
     def _forward_training(self, x, cam_label, view_label):
         """The reference's training outputs (:203-231) under autograd: ([cls_score, cls_score_proj], [f_last, f, f_proj], f_proj).
@@ -277,12 +317,23 @@ class build_transformer(_base.build_transformer):
         if isinstance(x, (list, tuple, _ops.PackedRawImages)):
             x = _ops.resize_bilinear_u8(x, self.img_hw)
         cv = self._sie(cam_label, view_label)
-        f_last, f, f_proj = enc.forward_grad(x, cv, 0, self.pixel_mean, self.pixel_std)
+        router_logits = None
+        if self._is_moe():
+            # Under autograd the logits are DATA (the sweep takes no gradient with respect to them); the load-balancing term
+            # reaches the gate through the fifth output: router_aux_loss [1] is load_balancing_loss_func of these logits as a
+            # differentiable node, and the gradient that arrives at it is the term's coefficient.
+            f_last, f, f_proj, logits, self.router_aux_loss = enc.forward_grad(x, cv, 0, self.pixel_mean, self.pixel_std)
+            n_tok = logits.shape[0] // f.shape[0]
+            router_logits = logits.view(f.shape[0], n_tok, -1).transpose(0, 1).reshape(logits.shape)   # rows l * B + b
+        else:
+            f_last, f, f_proj = enc.forward_grad(x, cv, 0, self.pixel_mean, self.pixel_std)
         feats = []
         for bn, t in ((self.bottleneck, f), (self.bottleneck_proj, f_proj)):
             feats.append(F.batch_norm(t, bn.running_mean, bn.running_var, bn.weight, bn.bias, True, 0.1, 1e-5))
             bn.num_batches_tracked.add_(1)
         scores = [F.linear(feats[0], self.classifier.weight), F.linear(feats[1], self.classifier_proj.weight)]
+        if router_logits is not None:
+            return scores, [f_last, f, f_proj], f_proj, router_logits
         return scores, [f_last, f, f_proj], f_proj
 
     def text_tower(self):

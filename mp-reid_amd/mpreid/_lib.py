@@ -59,6 +59,21 @@ class MoeLayer(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("gate_w", "fc_w", "fc_b", "proj_w", "proj_b", "fc_s", "proj_s")]
 
 
+class MoeLayerT(C.Structure):
+    """mpreid_moe_layer_t: per expert the fp32 transpose of the checkpoint's matrices, fc_t [E][w][4w], proj_t [E][4w][w]"""
+    _fields_ = [(k, C.c_void_p) for k in ("fc_t", "proj_t")]
+
+
+class MoeExpertGrads(C.Structure):
+    """mpreid_moe_expert_grads: the expert matrices' own gradients (not implemented: every member NULL)"""
+    _fields_ = [(k, C.c_void_p) for k in ("fc_w", "fc_b", "proj_w", "proj_b")]
+
+
+class VitMoeT(C.Structure):
+    """mpreid_vit_moe_t: a HOST array of moe_layers mpreid_moe_layer_t"""
+    _fields_ = [("layers", C.POINTER(MoeLayerT))]
+
+
 class VitMoe(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("num_experts", "top_k", "moe_layers")] + [("layers", C.POINTER(MoeLayer))]
 
@@ -259,6 +274,13 @@ PROTOTYPES = {
     "mpreid_moe_workspace_bytes": (sz, [i64, i32, i32, i32]),
     "mpreid_moe_route": (i32, [vp, i64, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     "mpreid_moe_mlp_split": (i32, [vp, i64, i32, vp, vp, i32, i32, P(MoeLayer), vp, vp, sz, vp]),
+    # the gradient through one routed MLP (a_pairs, rows, width, sel, w, E, K, layer, layer_t, dy, d_a, d_w, accumulate, d_experts,
+    # workspace, bytes, stream) and of the router (logits, rows, E, K, sel, w, d_w, aux_coef, d_logits, l_aux, workspace, bytes, stream)
+    "mpreid_moe_grad_workspace_bytes": (sz, [i64, i32, i32, i32]),
+    "mpreid_moe_mlp_backward": (i32, [vp, i64, i32, vp, vp, i32, i32, P(MoeLayer), P(MoeLayerT), vp, vp, vp, i32, P(MoeExpertGrads),
+                                      vp, sz, vp]),
+    "mpreid_moe_route_backward_workspace_bytes": (sz, [i64, i32]),
+    "mpreid_moe_route_backward": (i32, [vp, i64, i32, i32, vp, vp, vp, f32, vp, vp, vp, sz, vp]),
     # the text tower: (cfg, weights, prompts, eot rows, B, out, workspace, workspace bytes, stream)
     "mpreid_text_workspace_bytes": (sz, [P(TextCfg), i32]),
     "mpreid_text_forward": (i32, [P(TextCfg), P(TextWeights), vp, vp, i32, vp, vp, sz, vp]),
@@ -279,6 +301,14 @@ PROTOTYPES = {
     "mpreid_vit_backward_workspace_bytes": (sz, [P(VitCfg), i32]),
     "mpreid_vit_backward": (i32, [P(VitCfg), P(VitWeights), P(VitWeightsT), P(ImageIn), i32, vp, vp, vp, vp, P(VitGrads), vp, vp,
                                   sz, vp]),
+    # the MoE tower: (cfg, weights, moe, image batch, B, cv_emb, f_last, f, f_proj, logits, l_aux, workspace, bytes, stream) and
+    # (cfg, weights, transposed, moe, moe transposed, image batch, B, cv_emb, d_f_last, d_f, d_f_proj, aux_coef, grads, d_gate_w,
+    # d_tokens, l_aux, workspace, bytes, stream)
+    "mpreid_vit_forward_train_moe_workspace_bytes": (sz, [P(VitCfg), P(VitMoe), i32]),
+    "mpreid_vit_forward_train_moe": (i32, [P(VitCfg), P(VitWeights), P(VitMoe), P(ImageIn), i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "mpreid_vit_backward_moe_workspace_bytes": (sz, [P(VitCfg), P(VitMoe), i32]),
+    "mpreid_vit_backward_moe": (i32, [P(VitCfg), P(VitWeights), P(VitWeightsT), P(VitMoe), P(VitMoeT), P(ImageIn), i32, vp, vp, vp,
+                                      vp, f32, P(VitGrads), vp, vp, vp, vp, sz, vp]),
     "mpreid_transpose_pad_f32": (i32, [vp, i64, i32, vp, i64, vp]),
     "mpreid_colsum_workspace_bytes": (sz, [i64, i32]),
     "mpreid_colsum_f32": (i32, [vp, vp, i64, i32, vp, vp, vp, sz, vp]),

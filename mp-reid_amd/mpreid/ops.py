@@ -932,19 +932,34 @@ class VitEncoder:
 
     @torch.no_grad()
     def forward_train(self, img: torch.Tensor, cv_emb: Optional[torch.Tensor] = None, view: int = VIEW_ORIGINAL,
-                      pixel_mean=(0.5, 0.5, 0.5), pixel_std=(0.5, 0.5, 0.5)):
+                      pixel_mean=(0.5, 0.5, 0.5), pixel_std=(0.5, 0.5, 0.5), want_router: bool = False):
         """The three features stage 2 differentiates (mpreid_vit_forward_train) -> (f_last [B, width], f [B, width],
         f_proj [B, out_dim]): the CLS row of the last block's input, ln_post of the CLS row, and that @ proj; no BatchNorm neck
         (Stage2Head owns BNNeck).  f | f_proj carries the bits of forward() of an encoder without a neck.  img as forward_view
-        takes it: fp32 [B,3,H,W] or uint8 [B,H,W,3], any view -- pixels are data, there is no pixel gradient.  The dense tower
-        in the split precision only."""
-        if self.precision != "split" or self.c_moe is not None:
-            raise NotImplementedError("forward_train: the dense ViT tower in the split precision only (no MoE, fp16 or fp32 tower)")
+        takes it: fp32 [B,3,H,W] or uint8 [B,H,W,3], any view -- pixels are data, there is no pixel gradient.  The split
+        precision only.
+        An MoE tower (mpreid_vit_forward_train_moe): f_last is the CLS row of the last block's OUTPUT (model/clip/model.py:
+        448-454), and want_router=True appends (router_logits [B * L, E] in rows b * L + l, l_aux [1] = the load-balancing loss
+        of those logits)."""
+        if self.precision != "split":
+            raise NotImplementedError("forward_train: the ViT tower in the split precision only (no fp16 or fp32 tower)")
         L = _lib.load()
         img, cv, desc = _stage_images(self, img, img.dtype == torch.uint8, view, cv_emb, pixel_mean, pixel_std)
         B, w = img.shape[0], self.cfg["width"]
         f_last, f = (torch.empty((B, w), dtype=torch.float32, device=self.device) for _ in range(2))
         f_proj = torch.empty((B, self.cfg["out_dim"]), dtype=torch.float32, device=self.device)
+        if self.c_moe is not None:
+            n_tok = self.cfg["h_res"] * self.cfg["w_res"] + 1
+            logits = torch.empty((B * n_tok, self.c_moe.num_experts), dtype=torch.float32, device=self.device) if want_router else None
+            l_aux = torch.empty((1,), dtype=torch.float32, device=self.device) if want_router else None
+            ws = _workspace(self.ws_tag + "_train_moe",
+                            L.mpreid_vit_forward_train_moe_workspace_bytes(C.byref(self.c_cfg), C.byref(self.c_moe), B), self.device)
+            _lib.check(L.mpreid_vit_forward_train_moe(C.byref(self.c_cfg), C.byref(self.c_w), C.byref(self.c_moe), C.byref(desc), B,
+                                                      _ptr(cv), _ptr(f_last), _ptr(f), _ptr(f_proj), _ptr(logits), _ptr(l_aux),
+                                                      _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_vit_forward_train_moe")
+            return (f_last, f, f_proj, logits, l_aux) if want_router else (f_last, f, f_proj)
+        if want_router:
+            raise ValueError("forward_train: want_router needs an MoE tower")
         ws = _workspace(self.ws_tag, L.mpreid_vit_workspace_bytes(C.byref(self.c_cfg), B), self.device)
         _lib.check(L.mpreid_vit_forward_train(C.byref(self.c_cfg), C.byref(self.c_w), C.byref(desc), B, _ptr(cv), _ptr(f_last),
                                               _ptr(f), _ptr(f_proj), _ptr(ws), ws.numel(), _lib.stream_ptr()),
@@ -959,16 +974,25 @@ class VitEncoder:
                        ln_pre_g="ln_pre.weight", ln_pre_b="ln_pre.bias", ln_post_g="ln_post.weight", ln_post_b="ln_post.bias",
                        proj="proj")
 
+    _MLP_FIELDS = ("fc_w", "fc_b", "proj_w", "proj_b")
+    GATE_KEY = "transformer.resblocks.0.gate.weight"
+
     def _param_fields(self):
-        """(reference key name, layer index or None, struct field) of every trained parameter, in a fixed order"""
+        """(reference key name, layer index or None, struct field) of every trained parameter, in a fixed order.  An MoE tower:
+        the dense parameters of every block (an MoE block has no mlp.*) and block 0's gate.weight (field "gate_w").  Later gates
+        are never read and the experts are frozen in stage 2: neither is a master, their .grad stays None."""
+        n_moe = self.c_moe.moe_layers if self.c_moe is not None else 0
         out = [(key, None, field) for field, key in self._TOWER_KEYS.items()]
         for i in range(self.cfg["layers"]):
-            out += [(f"transformer.resblocks.{i}.{key}", i, field) for field, key in self._LAYER_KEYS.items()]
+            out += [(f"transformer.resblocks.{i}.{key}", i, field) for field, key in self._LAYER_KEYS.items()
+                    if i >= n_moe or field not in self._MLP_FIELDS]
+        if n_moe:
+            out.append((self.GATE_KEY, 0, "gate_w"))
         return out
 
     def _check_trainable(self, what: str):
-        if self.precision != "split" or self.c_moe is not None:
-            raise NotImplementedError(f"{what}: the dense ViT tower in the split precision only (no MoE, fp16 or fp32 tower)")
+        if self.precision != "split":
+            raise NotImplementedError(f"{what}: the ViT tower in the split precision only (no fp16 or fp32 tower)")
         if self.cfg["layers"] < 1:
             raise NotImplementedError(f"{what}: a tower of at least one layer")
 
@@ -980,6 +1004,12 @@ class VitEncoder:
         contiguous, on the encoder's device, in the checkpoint's shapes; a model's own parameters become the masters that way,
         and whoever updates them calls sync_weights() / sync_weights_batched() afterwards."""
         self._check_trainable("enable_training")
+        if masters is not None and self.c_moe is not None:
+            for key, m in masters.items():
+                if ".experts." in key and torch.is_tensor(m) and m.requires_grad:
+                    raise NotImplementedError(f"enable_training: {key!r} requires grad, and the expert matrices' own gradients are "
+                                              "not implemented (stage 2 freezes every parameter whose name contains 'expert'); "
+                                              "missing: the grouped weight-gradient GEMMs per expert")
         if masters is not None:
             adopted = {}
             for key, _, _ in self._param_fields():
@@ -999,6 +1029,17 @@ class VitEncoder:
             self._pairs, self._wt = {}, {}
             self._layers_t = (_lib.TextLayerT * self.cfg["layers"])()
             self.c_wt = _lib.VitWeightsT(C.cast(self._layers_t, C.POINTER(_lib.TextLayerT)))
+            if self.c_moe is not None and getattr(self, "c_moe_t", None) is None:
+                # the frozen experts' fp32 transposed copies, built once: what the gradient GEMMs through the experts multiply by
+                n_moe, n_exp = self.c_moe.moe_layers, self.c_moe.num_experts
+                self._moe_layers_t = (_lib.MoeLayerT * n_moe)()
+                for i in range(n_moe):
+                    for part, name in (("fc", "c_fc"), ("proj", "c_proj")):
+                        t = torch.stack([self._get(f"transformer.resblocks.{i}.experts.{e}.{name}.weight").to(
+                            device=self.device, dtype=torch.float32).t().contiguous() for e in range(n_exp)])
+                        self._keep.append(t)
+                        setattr(self._moe_layers_t[i], part + "_t", t.data_ptr())
+                self.c_moe_t = _lib.VitMoeT(C.cast(self._moe_layers_t, C.POINTER(_lib.MoeLayerT)))
             self.sync_weights()
         return self.masters
 
@@ -1012,7 +1053,9 @@ class VitEncoder:
             m = self.masters[key]
             assert m.is_contiguous() and m.dtype == torch.float32 and m.device == self.device, key
             target = self.c_w if i is None else self._layers[i]
-            if field.endswith("_w"):   # a GEMM weight: conv_w and the four matrices of a block
+            if field == "gate_w":      # block 0's gate: the router reads the master itself (fp32, no pair)
+                self._moe_layers[0].gate_w = m.data_ptr()
+            elif field.endswith("_w"):   # a GEMM weight: conv_w and the four matrices of a block
                 m2 = m.detach().reshape(m.shape[0], -1)
                 pair, scale, _ = _split_pack(m2, out=self._pairs.get(key))
                 self._pairs[key] = pair
@@ -1044,7 +1087,7 @@ class VitEncoder:
         for key, i, field in fields:
             m = self.masters[key]
             assert m.is_contiguous() and m.dtype == torch.float32 and m.device == self.device, key
-            if field.endswith("_w"):
+            if field.endswith("_w") and field != "gate_w":
                 mats.append((key, i, field, m.detach().reshape(m.shape[0], -1)))
         sb = getattr(self, "_sync_bufs", None)
         if sb is None or sb[0].numel() != len(mats):
@@ -1071,20 +1114,24 @@ class VitEncoder:
                            "mpreid_transpose_pad_f32")
                 setattr(self._layers_t[i], field[:-2] + "_t", self._wt[key].data_ptr())
         for key, i, field in fields:
-            if not field.endswith("_w"):
+            if field == "gate_w":
+                self._moe_layers[0].gate_w = self.masters[key].data_ptr()
+            elif not field.endswith("_w"):
                 setattr(self.c_w if i is None else self._layers[i], field, self.masters[key].data_ptr())
 
     @torch.no_grad()
     def backward(self, img: torch.Tensor, cv_emb: Optional[torch.Tensor], d_f_last: Optional[torch.Tensor],
                  d_f: Optional[torch.Tensor], d_f_proj: Optional[torch.Tensor], want=None, view: int = VIEW_ORIGINAL,
-                 pixel_mean=(0.5, 0.5, 0.5), pixel_std=(0.5, 0.5, 0.5), out: Optional[dict] = None):
+                 pixel_mean=(0.5, 0.5, 0.5), pixel_std=(0.5, 0.5, 0.5), out: Optional[dict] = None, aux_coef: float = 0.0):
         """The gradients of sum(f_last o d_f_last) + sum(f o d_f) + sum(f_proj o d_f_proj) over forward_train's features
         (mpreid_vit_backward; a None seed is zero) -> {reference key name: fp32 gradient in the checkpoint's shape}.  want: the
         names to compute (default: every parameter, and "cv_emb" when cv_emb is given); "cv_emb" [B, width] is the gradient of
         the cv_emb rows as given, "tokens" [B, L, width] that of the embedded sequence.  Names left out cost nothing.
         out: optional {name: a contiguous fp32 device tensor of the gradient's shape} to write into (it may be a view into a
         larger buffer).  The call re-runs the forward itself; img as forward_train takes it (pixels are data: there is no
-        pixel gradient)."""
+        pixel gradient).
+        An MoE tower (mpreid_vit_backward_moe): + aux_coef * l_aux in the function differentiated, and
+        "transformer.resblocks.0.gate.weight" among the names; aux_coef is ignored by a dense tower."""
         self._check_trainable("backward")
         if self.masters is None:
             raise RuntimeError("backward: call enable_training() first")
@@ -1118,10 +1165,19 @@ class VitEncoder:
         g = _lib.VitGrads()
         g.layers = C.cast(lg, C.POINTER(_lib.VitLayerGrads))
         for key, i, field in fields:
-            if key in want:
+            if key in want and field != "gate_w":
                 setattr(g if i is None else lg[i], field, out[key].data_ptr())
         if "cv_emb" in want:
             g.cv_emb = out["cv_emb"].data_ptr()
+        if self.c_moe is not None:
+            ws = _workspace(self.ws_tag + "_grad_moe",
+                            L.mpreid_vit_backward_moe_workspace_bytes(C.byref(self.c_cfg), C.byref(self.c_moe), B), self.device)
+            _lib.check(L.mpreid_vit_backward_moe(C.byref(self.c_cfg), C.byref(self.c_w), C.byref(self.c_wt), C.byref(self.c_moe),
+                                                 C.byref(self.c_moe_t), C.byref(desc), B, _ptr(cv), _ptr(seeds[0]), _ptr(seeds[1]),
+                                                 _ptr(seeds[2]), float(aux_coef), C.byref(g), _ptr(out.get(self.GATE_KEY)),
+                                                 _ptr(out.get("tokens")), None, _ptr(ws), ws.numel(), _lib.stream_ptr()),
+                       "mpreid_vit_backward_moe")
+            return out
         ws = _workspace(self.ws_tag + "_grad", L.mpreid_vit_backward_workspace_bytes(C.byref(self.c_cfg), B), self.device)
         _lib.check(L.mpreid_vit_backward(C.byref(self.c_cfg), C.byref(self.c_w), C.byref(self.c_wt), C.byref(desc), B, _ptr(cv),
                                          _ptr(seeds[0]), _ptr(seeds[1]), _ptr(seeds[2]), C.byref(g), _ptr(out.get("tokens")),
@@ -1132,7 +1188,9 @@ class VitEncoder:
                      pixel_mean=(0.5, 0.5, 0.5), pixel_std=(0.5, 0.5, 0.5)):
         """forward_train as a node of torch's autograd graph -> (f_last, f, f_proj), differentiable in self.masters and in
         cv_emb (not in the pixels): its backward is backward() with the incoming gradients, so torch.optim.* can drive the
-        masters; call sync_weights() after each optimizer step."""
+        masters; call sync_weights() after each optimizer step.
+        An MoE tower -> (f_last, f, f_proj, router_logits, l_aux): the logits are data (non-differentiable); l_aux [1] is
+        differentiable, and the gradient that reaches it is backward()'s aux_coef (read back once per backward)."""
         self._check_trainable("forward_grad")
         if self.masters is None:
             raise RuntimeError("forward_grad: call enable_training() first")
@@ -1154,13 +1212,20 @@ class _VitForwardGrad(torch.autograd.Function):
     def forward(ctx, enc, img, how, keys, cv_emb, *masters):
         ctx.enc, ctx.img, ctx.how, ctx.keys = enc, img, how, keys
         ctx.cv = None if cv_emb is None else cv_emb.detach()
-        return enc.forward_train(img, ctx.cv, *how)
+        if enc.c_moe is None:
+            return enc.forward_train(img, ctx.cv, *how)
+        # an MoE tower: (f_last, f, f_proj, router_logits, l_aux).  The logits are data; l_aux is differentiable, and the
+        # gradient that reaches it IS the coefficient of the load-balancing term in the caller's loss.
+        out = enc.forward_train(img, ctx.cv, *how, want_router=True)
+        ctx.mark_non_differentiable(out[3])
+        return out
 
     @staticmethod
-    def backward(ctx, d_f_last, d_f, d_f_proj):
+    def backward(ctx, d_f_last, d_f, d_f_proj, *router):
         need = ctx.needs_input_grad   # (enc, img, how, keys, cv_emb, *masters)
         want = [k for k, n in zip(ctx.keys, need[5:]) if n] + (["cv_emb"] if need[4] else [])
-        g = ctx.enc.backward(ctx.img, ctx.cv, d_f_last, d_f, d_f_proj, want, *ctx.how)
+        aux = float(router[1]) if len(router) == 2 and router[1] is not None else 0.0   # (one read-back: the autograd path)
+        g = ctx.enc.backward(ctx.img, ctx.cv, d_f_last, d_f, d_f_proj, want, *ctx.how, aux_coef=aux)
         return (None, None, None, None, g.get("cv_emb")) + tuple(g.get(k) for k in ctx.keys)
 
 
@@ -1429,6 +1494,79 @@ def moe_mlp(a_pairs: torch.Tensor, sel: torch.Tensor, w: torch.Tensor, layer, x:
     _lib.check(L.mpreid_moe_mlp_split(_ptr(a_pairs), rows, width, _ptr(sel), _ptr(w), int(num_experts), K, C.byref(layer), _ptr(x),
                                       _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_moe_mlp_split")
     return x
+
+
+def pack_moe_layer_t(fc_w, proj_w, dev=None):
+    """fp32 expert weights [E, 4w, w] and [E, w, 4w] (the checkpoint's [out][in]) -> (mpreid_moe_layer_t, the tensors it points
+    to): per expert the fp32 transpose, fc_t [E, w, 4w] and proj_t [E, 4w, w], what the gradient GEMMs multiply by"""
+    dev = dev or _lib.require_gpu()
+    keep = []
+    lt = _lib.MoeLayerT()
+    for part, wt in (("fc", fc_w), ("proj", proj_w)):
+        t = torch.stack([_dev_f32(m, dev).t().contiguous() for m in wt])
+        keep.append(t)
+        setattr(lt, part + "_t", t.data_ptr())
+    return lt, keep
+
+
+def _refuse_expert_grads(d_experts):
+    if d_experts is not None and any(v is not None for v in (d_experts.values() if isinstance(d_experts, dict) else d_experts)):
+        raise NotImplementedError("MoE backward: the expert matrices' own gradients are not implemented (stage 2 freezes every "
+                                  "parameter whose name contains 'expert'); missing: the grouped weight-gradient GEMMs per expert")
+
+
+def moe_mlp_backward(a_pairs: torch.Tensor, sel: torch.Tensor, w: torch.Tensor, layer, layer_t, dy: torch.Tensor, num_experts: int,
+                     d_a: Optional[torch.Tensor] = None, d_w: Optional[torch.Tensor] = None, accumulate_d_w: bool = False,
+                     want_d_a: bool = True, want_d_w: bool = True, d_experts=None, ws: Optional[torch.Tensor] = None):
+    """The gradient through one routed MLP (include/mpreid.h: mpreid_moe_mlp_backward).  a_pairs / sel / w / layer as for
+    moe_mlp, layer_t from pack_moe_layer_t, dy fp32 [rows, width].  Returns (d_a fp32 [rows, width] or None, d_w fp32 [rows, K]
+    or None); d_w is added to the caller's tensor with accumulate_d_w.  d_experts: must be None (not implemented)."""
+    _refuse_expert_grads(d_experts)
+    dev = _lib.require_gpu()
+    L = _lib.load()
+    rows, K = sel.shape
+    width = a_pairs.shape[1] // 2
+    assert a_pairs.dtype == torch.float16 and a_pairs.is_cuda and a_pairs.is_contiguous() and a_pairs.shape[0] >= rows
+    assert sel.dtype == torch.int32 and w.dtype == torch.float32 and sel.is_contiguous() and w.is_contiguous() and w.shape == sel.shape
+    assert dy.dtype == torch.float32 and dy.is_cuda and dy.is_contiguous() and dy.shape[0] >= rows and dy.shape[1] == width
+    assert want_d_a or want_d_w
+    if want_d_a and d_a is None:
+        d_a = torch.empty((rows, width), dtype=torch.float32, device=dev)
+    if want_d_w and d_w is None:
+        assert not accumulate_d_w, "accumulate_d_w needs the caller's d_w"
+        d_w = torch.empty((rows, K), dtype=torch.float32, device=dev)
+    for t, cols in ((d_a if want_d_a else None, width), (d_w if want_d_w else None, K)):
+        assert t is None or (t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.shape[0] >= rows and t.shape[1] == cols)
+    if ws is None:
+        ws = _workspace("moe_grad", L.mpreid_moe_grad_workspace_bytes(rows, width, int(num_experts), K), dev)
+    _lib.check(L.mpreid_moe_mlp_backward(_ptr(a_pairs), rows, width, _ptr(sel), _ptr(w), int(num_experts), K, C.byref(layer),
+                                         C.byref(layer_t), _ptr(dy), _ptr(d_a if want_d_a else None),
+                                         _ptr(d_w if want_d_w else None), int(bool(accumulate_d_w)), None, _ptr(ws), ws.numel(),
+                                         _lib.stream_ptr()), "mpreid_moe_mlp_backward")
+    return (d_a if want_d_a else None), (d_w if want_d_w else None)
+
+
+def moe_route_backward(logits: torch.Tensor, sel: torch.Tensor, w: torch.Tensor, d_w: Optional[torch.Tensor], aux_coef: float = 0.0,
+                       want_d_logits: bool = True, want_l_aux: bool = True, ws: Optional[torch.Tensor] = None):
+    """The router's gradient and the load-balancing loss (include/mpreid.h: mpreid_moe_route_backward).  logits fp32 [rows, E],
+    sel int32 / w fp32 [rows, K] of moe_route, d_w fp32 [rows, K] or None (zeros).  Returns (d_logits fp32 [rows, E] or None,
+    l_aux fp32 [1] or None); l_aux is the reference's load_balancing_loss_func of these logits, NOT multiplied by aux_coef."""
+    dev = _lib.require_gpu()
+    L = _lib.load()
+    rows, E = logits.shape
+    K = sel.shape[1]
+    assert logits.dtype == torch.float32 and logits.is_cuda and logits.is_contiguous()
+    assert sel.dtype == torch.int32 and w.dtype == torch.float32 and sel.is_cuda and w.is_cuda and sel.is_contiguous() and \
+        w.is_contiguous() and tuple(sel.shape) == (rows, K) and w.shape == sel.shape
+    assert d_w is None or (d_w.dtype == torch.float32 and d_w.is_cuda and d_w.is_contiguous() and d_w.shape == sel.shape)
+    assert want_d_logits or want_l_aux
+    d_logits = torch.empty((rows, E), dtype=torch.float32, device=dev) if want_d_logits else None
+    l_aux = torch.empty((1,), dtype=torch.float32, device=dev) if want_l_aux else None
+    if ws is None:
+        ws = _workspace("moe_route_grad", L.mpreid_moe_route_backward_workspace_bytes(rows, E), dev)
+    _lib.check(L.mpreid_moe_route_backward(_ptr(logits), rows, E, K, _ptr(sel), _ptr(w), _ptr(d_w), float(aux_coef), _ptr(d_logits),
+                                           _ptr(l_aux), _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_moe_route_backward")
+    return d_logits, l_aux
 
 
 def split_pairs_f32(x: torch.Tensor) -> torch.Tensor:
@@ -2098,6 +2236,7 @@ class Stage2Step:
         self.loss, self.id_loss, self.triplet_loss, self.i2t_loss = parts[0:1], parts[1], parts[2], parts[3]
         self.scores, self.i2t_logits, self.i2t_argmax, self._target = scores, i2t_logits, argmax, target
         self.d_f_last, self.d_f, self.d_f_proj, self.grads = d_f_last, d_f, d_f_proj, grads
+        self.aux_loss = None   # an MoE tower's load-balancing loss [1] (Stage2Trainer.step sets it)
 
     @property
     def acc(self):
@@ -2500,15 +2639,22 @@ class Stage2Trainer:
     mode in the reference's forward, so its running statistics move: one bn1d_train forward on f_proj does the same here.
     cv_table: the SIE table cv_embed [rows, width] (the encoder's cv_emb is sie_coe * cv_table[cv_index]); its gradient is
     sie_coe * the rows of d cv_emb summed per table row in batch order (rows_segment_sum with a window of one token).
-    Not reproduced: autocast and GradScaler (the features and gradients are fp32-grade, nothing to scale)."""
+    Not reproduced: autocast and GradScaler (the features and gradients are fp32-grade, nothing to scale).
+    An MoE encoder: the step differentiates loss + aux_coef * l_aux (l_aux: the load-balancing loss of block 0's router logits,
+    processor_uniprompt_stage2.py:121-128 with the documented one-layer contract) and reports that sum in Stage2Step.loss, with
+    l_aux itself in Stage2Step.aux_loss; block 0's gate.weight is a master like any other and joins the optimizer's table; the
+    experts and the later gates are no masters, so nothing touches them.  aux_coef: default 0.01 for an MoE tower, ignored
+    for a dense one."""
 
     HEAD_BOUND = ("classifier.weight", "bottleneck.weight", "bottleneck.bias")
 
     def __init__(self, encoder: "VitEncoder", head: Stage2Head, optimizer: TensorOptimizer, text_features: torch.Tensor,
                  cv_table: Optional[torch.Tensor] = None, sie_coe: float = 3.0, pixel_mean=(0.5, 0.5, 0.5),
-                 pixel_std=(0.5, 0.5, 0.5)):
+                 pixel_std=(0.5, 0.5, 0.5), aux_coef: Optional[float] = None):
         if not isinstance(encoder, VitEncoder):
-            raise NotImplementedError("Stage2Trainer: the dense ViT tower in the split precision only (no RN50 tower)")
+            raise NotImplementedError("Stage2Trainer: the ViT tower in the split precision only (no RN50 tower)")
+        self.moe = encoder.c_moe is not None
+        self.aux_coef = (0.01 if aux_coef is None else float(aux_coef)) if self.moe else 0.0
         encoder._check_trainable("Stage2Trainer")
         if encoder.masters is None:
             raise RuntimeError("Stage2Trainer: call encoder.enable_training() first")
@@ -2568,8 +2714,16 @@ class Stage2Trainer:
                 check_segment_index(cv_index, B, self.cv_table.shape[0])
             cv_index = _dev_i64(cv_index, enc.device)
             cv_emb = self.sie_coe * self.cv_table.detach()[cv_index]
-        f_last, f, f_proj = enc.forward_train(img, cv_emb, VIEW_ORIGINAL, self.pixel_mean, self.pixel_std)
+        l_aux = None
+        if self.moe:
+            f_last, f, f_proj, _, l_aux = enc.forward_train(img, cv_emb, VIEW_ORIGINAL, self.pixel_mean, self.pixel_std,
+                                                            want_router=True)
+        else:
+            f_last, f, f_proj = enc.forward_train(img, cv_emb, VIEW_ORIGINAL, self.pixel_mean, self.pixel_std)
         st = head.step(f_last, f, f_proj, target, self.text_features, form="uniprompt", validate=validate)
+        st.aux_loss = l_aux
+        if l_aux is not None:   # the loss the step reports is the one it differentiates
+            st.loss.add_(l_aux, alpha=self.aux_coef)
         if self._head_batch != B:   # the head's gradient buffers are per batch size: bound once per size
             for k in self._head_bound:
                 self.optimizer.bind(head.params[k], st.grads[k])
@@ -2583,7 +2737,9 @@ class Stage2Trainer:
         if self._cv_trained:
             want, out = want + ["cv_emb"], dict(out, cv_emb=b["d_cv"].view(B, -1))
         # (d_f_last: exact zeros in the Uni-Prompt form -- a None seed is zero and costs nothing)
-        enc.backward(img, cv_emb, None, st.d_f, st.d_f_proj, want, VIEW_ORIGINAL, self.pixel_mean, self.pixel_std, out=out)
+        # (an MoE tower's f_last is the last block's OUTPUT; its seed is exact zeros in the Uni-Prompt form all the same)
+        enc.backward(img, cv_emb, None, st.d_f, st.d_f_proj, want, VIEW_ORIGINAL, self.pixel_mean, self.pixel_std, out=out,
+                     aux_coef=self.aux_coef)
         if self._cv_trained:
             rows_segment_sum(b["d_cv"], cv_index, 0, 1, self.cv_table.shape[0], out=self._seg, validate=False)
             torch.mul(self._seg.view(self.cv_table.shape), self.sie_coe, out=self.grads["cv_embed"])

@@ -32,7 +32,9 @@ optimizer a batch takes the autograd path through the training-mode forward and 
   * the center-loss branch: the reference's ``loss_func`` never calls ``center_criterion``, its loop touches the centers only
     when ``'center' in MODEL.METRIC_LOSS_TYPE``, a configuration ``make_loss`` cannot answer -- ``optimizer_center`` is built,
     passed along, zeroed and never stepped.  The same holds here;
-  * the MoE load-balancing term: the MoE tower has no backward, ``enable_stage2_training()`` refuses it.
+  * the reference's loop over the rows of the tower's fourth output: its own MoE stage 2 cannot run (its model wrapper unpacks
+    three values from a four-value tower).  Here the load-balancing term is the documented contract of
+    ``load_balancing_loss_func``: ONE layer of logits [L * B, E], coefficient 0.01.
 The labels and the SIE rows address tables on the device: each batch's are range-checked on the host before they are copied
 (no wait for the device).
 """
@@ -205,8 +207,14 @@ def do_train_stage2(cfg, model, center_criterion, train_loader_stage2, val_loade
     epochs = max_epochs
     logger = logging.getLogger("transreid.train")
     logger.info('start training')
+    moe = bool(getattr(model, "_is_moe", lambda: False)())
     if getattr(model, "_train_encoder", None) is None:
-        model.enable_stage2_training(set_requires_grad=False)
+        if moe:   # the caller's marking is kept: it must have frozen every `expert` name, as both stage-2 optimizers do
+            model.enable_stage2_moe_training(set_requires_grad=False)
+        else:
+            model.enable_stage2_training(set_requires_grad=False)
+    from model.make_model_uniprompt import LOAD_BALANCE_LOSS_COEFF, load_balancing_loss_func
+    aux_meter = AverageMeter()
     model.to(device)
     num_classes = model.num_classes
     loss_meter, acc_meter = AverageMeter(), AverageMeter()
@@ -225,10 +233,11 @@ def do_train_stage2(cfg, model, center_criterion, train_loader_stage2, val_loade
         start_time = time.time()
         loss_meter.reset()
         acc_meter.reset()
+        aux_meter.reset()
         evaluator.reset()
         scheduler.step(epoch)
         model.train()
-        pending = []     # (loss, accuracy, batch size) of the steps that have not been read back yet: device scalars
+        pending = []     # (loss, accuracy, batch size, aux loss) of the steps that have not been read back yet: device scalars
         n_batches = len(train_loader_stage2)
         n_iter = -1
         for n_iter, (img, vid, target_cam, target_view) in enumerate(train_loader_stage2):
@@ -243,27 +252,37 @@ def do_train_stage2(cfg, model, center_criterion, train_loader_stage2, val_loade
             target_view = None if target_view is None else target_view.to(device)
             img = img.to(device)
             if trainer is not None:
-                st = trainer.step(img, target, model._sie_index(target_cam, target_view))
+                st = trainer.step(img, target, model._sie_index(target_cam, target_view))   # (an MoE tower: + 0.01 l_aux inside)
                 loss, acc = st.loss.clone(), st.acc
+                aux = None if st.aux_loss is None else st.aux_loss.clone()
             else:
                 optimizer.zero_grad()
                 optimizer_center.zero_grad()
-                scores, feats_all, image_features_proj = model(x=img, label=target, cam_label=target_cam, view_label=target_view)[:3]
+                out = model(x=img, label=target, cam_label=target_cam, view_label=target_view)
+                scores, feats_all, image_features_proj = out[:3]
                 logits_i2t = image_features_proj @ text_features.t()
                 loss = loss_fn(scores[0], feats_all[1], target, target_cam, logits_i2t)
+                aux = None
+                if len(out) == 4:   # an MoE tower (reference :121-128, on ONE layer of logits [L * B, E])
+                    aux = load_balancing_loss_func(out[3], cfg.MODEL.MOE.TOP_K).detach()   # the value logged: the logits are data
+                    loss = loss + LOAD_BALANCE_LOSS_COEFF * model.router_aux_loss.sum()    # the same function, differentiable
                 loss.backward()
                 optimizer.step()
                 acc = (logits_i2t.max(1)[1] == target).float().mean()
                 loss = loss.detach()
-            pending.append((loss, acc, img.shape[0]))
+            pending.append((loss, acc, img.shape[0], aux))
             if (n_iter + 1) % log_period == 0 or n_iter + 1 == n_batches:
-                for value, a, n in pending:
+                for value, a, n, x in pending:
                     loss_meter.update(float(value), n)
                     acc_meter.update(float(a), 1)
+                    if x is not None:
+                        aux_meter.update(float(x), n)
                 pending = []
             if (n_iter + 1) % log_period == 0:
                 logger.info("Epoch[{}] Iteration[{}/{}] Loss: {:.3f}, Acc: {:.3f}, Base Lr: {:.2e}"
                             .format(epoch, (n_iter + 1), n_batches, loss_meter.avg, acc_meter.avg, optimizer.param_groups[0]['lr']))
+                if moe:   # reference :154-155
+                    logger.info("Epoch[{}] Iteration[{}/{}] AuxLoss: {:.4f}".format(epoch, (n_iter + 1), n_batches, aux_meter.avg))
         torch.cuda.synchronize()
         time_per_batch = (time.time() - start_time) / max(n_iter + 1, 1)
         if not cfg.MODEL.DIST_TRAIN:
