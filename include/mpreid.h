@@ -721,7 +721,7 @@ int mpreid_text_attention(const void *qkv_dev, int batch, int tokens, int width,
  * result is exactly homogeneous in grad_out under power-of-two scaling (short of underflow); every element of grad_prompts
  * is written.  Limits and errors as for mpreid_text_forward (all before anything is launched); prompts_dev, grad_prompts_dev
  * and the transposed matrices 16-byte aligned, the workspace 256; the contents of eot_dev are validated by the caller. */
-typedef struct {                       /* device pointers, fp32, [in][out] = the transpose of the checkpoint's [out][in] */
+typedef struct {   /* device pointers, fp32, [in][out] = the checkpoint's [out][in] transposed; also mpreid_vit_layer_t (below) */
     const float *in_proj_t;            /* [width][3 * width] */
     const float *out_proj_t;           /* [width][width] */
     const float *fc_t;                 /* [width][4 * width] */
@@ -813,12 +813,7 @@ int mpreid_vit_attention_backward(const float *qkv_dev, const float *d_o_dev, in
  * and row statistics (8 bytes per row).  Errors, all before anything is launched: NULL or misaligned pointers, batch <= 0,
  * batch * L above 65 535 * 128 rows (the column reduction's grid): MPREID_ERR_ARG; a short workspace (256-byte aligned): MPREID_ERR_WORKSPACE; layers < 1, a precision other than
  * MPREID_VIT_SPLIT or a shape outside mpreid_vit_forward's: MPREID_ERR_UNSUPPORTED.  (An MoE tower: mpreid_vit_backward_moe.) */
-typedef struct {                       /* device pointers, fp32, [in][out] = the transpose of the checkpoint's [out][in] */
-    const float *in_proj_t;            /* [width][3 * width] */
-    const float *out_proj_t;           /* [width][width] */
-    const float *fc_t;                 /* [width][4 * width] */
-    const float *proj_t;               /* [4 * width][width] */
-} mpreid_vit_layer_t;
+typedef mpreid_text_layer_t mpreid_vit_layer_t;   /* a block's transposed matrices: ONE struct for both towers (above) */
 typedef struct {
     const mpreid_vit_layer_t *layers;  /* HOST array of cfg.layers entries */
 } mpreid_vit_weights_t;

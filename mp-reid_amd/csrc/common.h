@@ -144,6 +144,33 @@ __device__ __forceinline__ float wave_bfly_add(float s) {
     return s;
 }
 
+__device__ __forceinline__ float wave_bfly_max(float s) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s = fmaxf(s, __shfl_xor(s, off, 64));
+    return s;
+}
+
+// LDS written by this wave is read by this wave
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// sum_c a[c] * b[c] over the 64 features of a head, c ascending in one fmaf chain: the SAME bits wherever a score is needed
+__device__ __forceinline__ float dot64(const float *__restrict__ a, const float *__restrict__ b) {
+    float acc = 0.f;
+#pragma unroll
+    for (int c = 0; c < 64; c += 4) {
+        const float4 x = *reinterpret_cast<const float4 *>(a + c);
+        const float4 y = *reinterpret_cast<const float4 *>(b + c);
+        acc = fmaf(x.x, y.x, acc);
+        acc = fmaf(x.y, y.y, acc);
+        acc = fmaf(x.z, y.z, acc);
+        acc = fmaf(x.w, y.w, acc);
+    }
+    return acc;
+}
 
 // Per-launch event timing shared by the kernels bench.py reports a roofline for (gemm_f16.hip owns the registry).
 // prof_begin returns an opaque token (nullptr while profiling is disabled); prof_end records the closing event and files

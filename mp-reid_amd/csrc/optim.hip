@@ -143,15 +143,9 @@ __device__ __forceinline__ float finite_abs(float x) {
     return x < INFINITY ? x : 0.f;   // NaN and the infinities count as 0
 }
 
-__device__ __forceinline__ float wave_max(float s) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s = fmaxf(s, __shfl_xor(s, off, 64));
-    return s;
-}
-
 // the maximum over a workgroup's 256 values, valid in thread 0 (all values are >= 0 and finite)
 __device__ __forceinline__ float block_max(float s, float *red) {
-    s = wave_max(s);
+    s = wave_bfly_max(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     const float r = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));

@@ -8,12 +8,6 @@
 
 namespace {
 
-__device__ __forceinline__ float wave_bfly_max(float s) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s = fmaxf(s, __shfl_xor(s, off, 64));
-    return s;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // S = img . txt^T and its transpose: a 16 x 16 tile of S per workgroup, one entry per thread, one fmaf chain over the features
 // ---------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // text.hip — the forward of CLIP's text tower for gfx950 (mpreid_text_forward; model/clip/model.py:609-619 after the embedding
-// lookup, model/make_model_uniprompt.py:58-68): the residual blocks of the split mode (the block driver of vit.hip: text_block,
+// lookup, model/make_model_uniprompt.py:58-68): the residual blocks of the split mode (the block driver of vit.hip: tower_block,
 // towers.h) with a CAUSAL attention (attention_causal_kernel, attention.hip), ln_final on the end-of-text row and
 // text_projection (tower_head, vit.hip).  Split precision only: the text side is never the throughput path.
 #include "towers.h"
@@ -87,8 +87,9 @@ extern "C" int mpreid_text_forward(const mpreid_text_cfg *cfg, const mpreid_text
     _Float16 *hbuf = (_Float16 *)(base + v.hbuf);
     float *y = (float *)(base + v.y);
     if ((rc = text_embed(prompts, w->pos_emb, v.M, L, W, x, stream))) return rc;
+    const BlockShape shape{W, cfg->heads, B, L, true};
     for (int l = 0; l < cfg->layers; ++l)
-        if ((rc = text_block(cfg, B, w->layers[l], x, a, qkv, hbuf, (int)v.M, (int)v.Mpad, stream))) return rc;
+        if ((rc = tower_block(shape, w->layers[l], x, a, qkv, hbuf, (int)v.Mpad, stream))) return rc;
     // ln_final on the end-of-text row alone (LayerNorm is per row: the same values as normalising every row first), @ proj
     return tower_head(x, (int64_t)L * W, eot, L, B, W, cfg->out_dim, w->ln_final_g, w->ln_final_b, w->proj, nullptr, nullptr,
                       nullptr, nullptr, y, out, cfg->out_dim, 0, false, stream);

@@ -1,23 +1,13 @@
 // text_grad.hip — mpreid_text_backward: the gradient of the text features with respect to the prompts, every tower weight
 // frozen (include/mpreid.h).  The call re-runs the forward's own blocks (csrc/vit.hip through towers.h), keeps each
-// block's input, and walks the layers back: per layer it recomputes q | k | v, the block's mid-point and the FC1
-// pre-activation with the forward's launchers, and propagates the gradient with the exact fp32 GEMM over transposed fp32
-// weights (dX = dY . W) and the fp32 kernels below.  No weight gradient, no atomics: the same bits from run to run.
+// block's input, and walks the layers back through the one differentiation of a block (block_mlp_backward /
+// block_attention_backward, csrc/vit_grad.hip) with no parameter gradient asked for: per layer q | k | v, the block's
+// mid-point and the FC1 pre-activation are recomputed with the forward's launchers, and the gradient is propagated with the
+// exact fp32 GEMM over transposed fp32 weights (dX = dY . W) and the fp32 kernels below, which the image tower's sweep
+// launches as well (all but the causal attention gradient).  No weight gradient, no atomics: the same bits from run to run.
 #include "towers.h"
 
 namespace {
-
-__device__ __forceinline__ void wave_lds_sync() {   // LDS written by this wave is read by this wave (distance.hip's mirror)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ float wave_max(float s) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s = fmaxf(s, __shfl_xor(s, off, 64));
-    return s;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // causal attention backward: one workgroup per (prompt, head), Q, K, V and dO of the head in LDS
@@ -27,21 +17,6 @@ constexpr int AB_LD = 68;    // floats per LDS row: 64 + 4, so that the 16-byte 
 constexpr int AB_MAXL = MPREID_TEXT_MAX_TOKENS;
 
 static size_t attn_bwd_lds_bytes(int L) { return ((size_t)4 * L * AB_LD + 4 * AB_MAXL + AB_NW * 2 * AB_MAXL) * sizeof(float); }
-
-// sum_c a[c] * b[c] over the 64 features of a head, c ascending in one fmaf chain: the SAME bits wherever a score is needed
-__device__ __forceinline__ float dot64(const float *__restrict__ a, const float *__restrict__ b) {
-    float acc = 0.f;
-#pragma unroll
-    for (int c = 0; c < 64; c += 4) {
-        const float4 x = *reinterpret_cast<const float4 *>(a + c);
-        const float4 y = *reinterpret_cast<const float4 *>(b + c);
-        acc = fmaf(x.x, y.x, acc);
-        acc = fmaf(x.y, y.y, acc);
-        acc = fmaf(x.z, y.z, acc);
-        acc = fmaf(x.w, y.w, acc);
-    }
-    return acc;
-}
 
 // qkv [B * L][3W] (q | k | v, head h in columns h * 64 ..), d_o [B * L][W] -> d_qkv [B * L][3W].
 // P = softmax(mask(q k^T / 8)), dV = P^T dO, dP = dO V^T, dS = P o (dP - rowsum(P o dP)), dQ = dS K / 8, dK = dS^T Q / 8.
@@ -93,7 +68,7 @@ __global__ __launch_bounds__(64 * AB_NW) void text_attention_backward_kernel(con
                 dp[t] = dot64(Gs + i * AB_LD, Vs + j * AB_LD);
             }
         }
-        const float m = wave_max(fmaxf(s[0], s[1]));
+        const float m = wave_bfly_max(fmaxf(s[0], s[1]));
         float e[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) e[t] = (lane + 64 * t <= i) ? expf(s[t] - m) : 0.f;
@@ -249,7 +224,11 @@ __global__ __launch_bounds__(256) void text_head_backward_kernel(const float *__
             dst[(int64_t)r * W + k] = r == e ? ((dy[k] - c1) - ((xr[k] - mean) * rstd) * c2) * rstd : 0.f;
 }
 
-int launch_attention_backward(const float *qkv, const float *d_o, int B, int L, int W, int heads, float *d_qkv, hipStream_t s) {
+}   // namespace
+
+// (towers.h: launched by the differentiation of a block, csrc/vit_grad.hip)
+int launch_causal_attention_backward(const float *qkv, const float *d_o, int B, int L, int W, int heads, float *d_qkv,
+                                     hipStream_t s) {
     const size_t lds = attn_bwd_lds_bytes(L);
     const int rc = mpreid_dyn_lds(text_attention_backward_kernel, lds);
     if (rc) return rc;
@@ -259,9 +238,6 @@ int launch_attention_backward(const float *qkv, const float *d_o, int B, int L, 
     return MPREID_OK;
 }
 
-}   // namespace
-
-// (towers.h: the image tower's sweep, csrc/vit_grad.hip, launches these two as well)
 int launch_layernorm_backward(const float *x, const float *dy, const float *g, int64_t rows, int W, bool acc, float *out,
                               hipStream_t s) {
     const dim3 grid((unsigned)((rows + 3) / 4));
@@ -285,25 +261,16 @@ namespace {
 // pre-activation of the sweep: the same 16 W bytes per row), then the kept block inputs and the gradient buffers
 struct TextGradLayout {
     TextLayout f;
-    size_t xs, dx, dh, t, dqkv, total;
+    SweepRegions r;
+    size_t total;
 };
 
 TextGradLayout text_grad_layout(const mpreid_text_cfg *c, int B) {
     TextGradLayout v{};
     v.f = text_layout(c, B);
-    const size_t row = (size_t)v.f.Mpad * c->width * 4;   // one fp32 [Mpad][W] buffer: a multiple of 256 bytes
-    size_t off = v.f.total;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += align_up(bytes, 256);
-        return at;
-    };
-    v.xs = take(row * (size_t)c->layers);   // x_l, the input of block l, l = 0 .. layers - 1
-    v.dx = take(row);                       // the gradient of the residual stream
-    v.dh = take(4 * row);                   // the gradient of the MLP's hidden layer
-    v.t = take(row);                        // the gradient of a LayerNorm output / of the attention output
-    v.dqkv = take(3 * row);
-    v.total = off;
+    WsCursor take{v.f.total};
+    v.r = take_sweep_regions(take, (size_t)v.f.Mpad * c->width * 4, c->layers);
+    v.total = take.off;
     return v;
 }
 
@@ -321,7 +288,7 @@ extern "C" int mpreid_text_attention_backward(const float *qkv, const float *d_o
     const int rc = text_check_shape(L, W, heads);
     if (rc) return rc;
     ARG_CHECK((int64_t)B * heads < (int64_t)1 << 31 && (int64_t)B * L * 3 * W < (int64_t)1 << 40);
-    return launch_attention_backward(qkv, d_o, B, L, W, heads, d_qkv, (hipStream_t)stream);
+    return launch_causal_attention_backward(qkv, d_o, B, L, W, heads, d_qkv, (hipStream_t)stream);
 }
 
 extern "C" int mpreid_layernorm_backward_f32(const float *x, const float *dy, const float *gamma, int64_t rows, int width,
@@ -356,46 +323,36 @@ extern "C" int mpreid_text_backward(const mpreid_text_cfg *cfg, const mpreid_tex
     hipStream_t stream = (hipStream_t)stream_;
     const int W = cfg->width, L = cfg->tokens, M = (int)v.f.M, Mpad = (int)v.f.Mpad;
     char *base = (char *)ws;
-    float *x = (float *)(base + v.f.x);
-    _Float16 *a = (_Float16 *)(base + v.f.a);
-    float *qkv = (float *)(base + v.f.qkv);
+    auto f32 = [&](size_t off) { return (float *)(base + off); };
     _Float16 *hbuf = (_Float16 *)(base + v.f.hbuf);
-    float *u = (float *)(base + v.f.hbuf);   // the sweep's use of the region
-    float *xs = (float *)(base + v.xs);
-    float *dx = (float *)(base + v.dx);
-    float *dh = (float *)(base + v.dh);
-    float *t = (float *)(base + v.t);
-    float *dqkv = (float *)(base + v.dqkv);
+    // no parameter gradient: aot, at, bt, stats and red stay NULL and the workspace has no such regions.  u is the sweep's use
+    // of the hbuf region
+    BlockGrad c{};
+    c.s = {W, cfg->heads, B, L, true}; c.Mpad = Mpad; c.stream = stream;
+    c.x = f32(v.f.x); c.a = (_Float16 *)(base + v.f.a); c.qkv = f32(v.f.qkv); c.u = f32(v.f.hbuf);
+    c.dx = f32(v.r.dx); c.dh = f32(v.r.dh); c.t = f32(v.r.t); c.dqkv = f32(v.r.dqkv);
+    float *xs = f32(v.r.xs);
     const size_t xbytes = (size_t)M * W * 4, xstride = (size_t)Mpad * W;
+    const mpreid_vit_layer_grads none{};
 
     // the forward, keeping x_l
-    if ((rc = text_embed(prompts, w->pos_emb, v.f.M, L, W, x, stream))) return rc;
+    if ((rc = text_embed(prompts, w->pos_emb, v.f.M, L, W, c.x, stream))) return rc;
     for (int l = 0; l < cfg->layers; ++l) {
-        HIP_TRY(hipMemcpyAsync(xs + l * xstride, x, xbytes, hipMemcpyDeviceToDevice, stream));
-        if ((rc = text_block(cfg, B, w->layers[l], x, a, qkv, hbuf, M, Mpad, stream))) return rc;
+        HIP_TRY(hipMemcpyAsync(xs + l * xstride, c.x, xbytes, hipMemcpyDeviceToDevice, stream));
+        if ((rc = tower_block(c.s, w->layers[l], c.x, c.a, c.qkv, hbuf, Mpad, stream))) return rc;
     }
     // text_projection and ln_final at the read-out rows -> d/dx_layers; zero everywhere else
-    hipLaunchKernelGGL(text_head_backward_kernel, dim3((unsigned)B), dim3(256), 0, stream, x, eot, grad_out, L, W, cfg->out_dim,
-                       wt->proj_t, w->ln_final_g, dx);
+    hipLaunchKernelGGL(text_head_backward_kernel, dim3((unsigned)B), dim3(256), 0, stream, c.x, eot, grad_out, L, W, cfg->out_dim,
+                       wt->proj_t, w->ln_final_g, c.dx);
     LAUNCH_CHECK();
     for (int l = cfg->layers - 1; l >= 0; --l) {
-        const mpreid_vit_layer &ly = w->layers[l];
-        const mpreid_text_layer_t &lt = wt->layers[l];
         const float *xl = xs + l * xstride;
-        HIP_TRY(hipMemcpyAsync(x, xl, xbytes, hipMemcpyDeviceToDevice, stream));
-        if ((rc = text_block_recompute(cfg, B, ly, x, a, qkv, u, M, Mpad, stream))) return rc;   // x = x_mid from here on
-        // x_{l+1} = x_mid + c_proj(quickgelu(c_fc(ln_2(x_mid))))
-        if ((rc = mpreid_gemm_f32_linear(dx, lt.proj_t, M, 4 * W, W, nullptr, dh, 4 * W, F32_LIN, stream))) return rc;
-        if ((rc = launch_quickgelu_backward(u, dh, (int64_t)M * W, stream))) return rc;   // M * 4W / 4 float4
-        if ((rc = mpreid_gemm_f32_linear(dh, lt.fc_t, M, W, 4 * W, nullptr, t, W, F32_LIN, stream))) return rc;
-        if ((rc = launch_layernorm_backward(x, t, ly.ln2_g, M, W, true, dx, stream))) return rc;   // dx = d/dx_mid
-        // x_mid = x_l + out_proj(attention(in_proj(ln_1(x_l))))
-        if ((rc = mpreid_gemm_f32_linear(dx, lt.out_proj_t, M, W, W, nullptr, t, W, F32_LIN, stream))) return rc;
-        if ((rc = launch_attention_backward(qkv, t, B, L, W, cfg->heads, dqkv, stream))) return rc;
-        if ((rc = mpreid_gemm_f32_linear(dqkv, lt.in_proj_t, M, W, 3 * W, nullptr, t, W, F32_LIN, stream))) return rc;
-        if ((rc = launch_layernorm_backward(xl, t, ly.ln1_g, M, W, true, dx, stream))) return rc;   // dx = d/dx_l
+        HIP_TRY(hipMemcpyAsync(c.x, xl, xbytes, hipMemcpyDeviceToDevice, stream));
+        if ((rc = tower_block_attention(c.s, w->layers[l], c.x, c.a, c.qkv, Mpad, stream))) return rc;
+        if ((rc = block_mlp_backward(c, w->layers[l], wt->layers[l], none))) return rc;
+        if ((rc = block_attention_backward(c, w->layers[l], wt->layers[l], xl, none))) return rc;   // dx = d/dx_l
     }
     // the positional embedding is an added constant: d/dprompts = d/dx_0
-    HIP_TRY(hipMemcpyAsync(grad_prompts, dx, xbytes, hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(grad_prompts, c.dx, xbytes, hipMemcpyDeviceToDevice, stream));
     return MPREID_OK;
 }

@@ -420,7 +420,7 @@ static int block_mid_part(const BlockCtx &c, const mpreid_vit_layer &ly, float *
 // xr += out_proj(ar); xr += mlp(ln_2(xr)) over `rows` rows (rows_pad: the GEMMs' row count; hr: the MLP's hidden buffer).
 // Blocks l < moe->moe_layers of an MoE tower (moe != nullptr; vm places its workspace share behind base) run router and
 // dispatch (l == 0 only), grouped FC1 / FC2 and combine (csrc/moe.hip) in place of FC1 and FC2
-// fc1_f32 (the text tower's backward sweep, text_block_recompute): FC1 leaves its pre-activation there in fp32 [rows_pad][4W]
+// fc1_f32 (the backward sweeps, tower_block_mlp_recompute): FC1 leaves its pre-activation there in fp32 [rows_pad][4W]
 // and the part ends before FC2, with xr = the block's mid-point
 static int block_mlp_part(const BlockCtx &c, const mpreid_vit_layer &ly, float *xr, _Float16 *ar, _Float16 *hr, int rows,
                           int rows_pad, const mpreid_vit_moe *moe, int l, const VitMoeLayout *vm, char *base,
@@ -458,11 +458,8 @@ static int block_mlp_part(const BlockCtx &c, const mpreid_vit_layer &ly, float *
 }
 
 // The embedded sequence, ln_pre's input: patch gather, conv1 (no bias) + positional embedding, the CLS row (+ cv_emb)
-static int vit_embed_tokens_impl(const BlockCtx &ctx, const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w,
-                                 const mpreid_image_in &in, int B, const float *cv_emb, const VitLayout &v, _Float16 *patches,
-                                 float *x) {
-    hipStream_t stream = ctx.stream;
-    const bool split = ctx.split;
+int vit_embed_tokens(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_image_in &in, int B, const float *cv_emb,
+                     const VitLayout &v, _Float16 *patches, float *x, bool split, hipStream_t stream) {
     const int W = cfg->width, L = v.L;
     const int64_t threads = (int64_t)v.MPpad * (v.Kp / 8);
     const dim3 grid((unsigned)((threads + 255) / 256));
@@ -490,7 +487,7 @@ static int vit_embed_tokens_impl(const BlockCtx &ctx, const mpreid_vit_cfg *cfg,
     g.m_valid = B * v.P;
     g.P = v.P;
     g.L = L;
-    const int rc = linear(ctx, g, v.Kp, w->conv_s, GE_PATCH, GE_S_PATCH);
+    const int rc = linear(BlockCtx{stream, split, split ? 2 : 1, W, cfg->heads, B, L}, g, v.Kp, w->conv_s, GE_PATCH, GE_S_PATCH);
     if (rc) return rc;
     hipLaunchKernelGGL(cls_token_kernel, dim3((unsigned)B), dim3(256), 0, stream, w->class_emb, w->pos_emb, cv_emb, B, L, W, x);
     LAUNCH_CHECK();
@@ -549,7 +546,7 @@ static int vit_forward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights 
     if (tr && moe && (tr->logits || tr->l_aux)) vm.logits_dst = (float *)(base + vm.logits);
 
     // patch embedding (conv1, no bias) + positional embedding; CLS row; ln_pre
-    if ((rc = vit_embed_tokens_impl(ctx, cfg, w, in, B, cv_emb, v, patches, x))) return rc;
+    if ((rc = vit_embed_tokens(cfg, w, in, B, cv_emb, v, patches, x, split, stream))) return rc;
     hipLaunchKernelGGL(layernorm_kernel<0>, dim3((unsigned)((v.M + 3) / 4)), dim3(256), 0, stream, x, (int64_t)v.M, W,
                        w->ln_pre_g, w->ln_pre_b, (void *)x, (int64_t)W);
     LAUNCH_CHECK();
@@ -792,28 +789,7 @@ extern "C" int mpreid_vit_forward_f32(const mpreid_vit_cfg *cfg, const mpreid_vi
     return image_head(cfg, w, x, (int64_t)L * W, B, y_cls, out, stream);
 }
 
-// the split mode's blocks (mpreid_vit_forward), causal
-int text_block(const mpreid_text_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *qkv, _Float16 *hbuf,
-               int M, int Mpad, hipStream_t stream) {
-    const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, cfg->tokens};
-    const int rc = block_attention_part(ctx, ly, x, a, qkv, M, Mpad, ATTN_CAUSAL);
-    return rc ? rc : block_mlp_part(ctx, ly, x, a, hbuf, M, Mpad, nullptr, 0, nullptr, nullptr);
-}
-
-int text_block_recompute(const mpreid_text_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *qkv,
-                         float *u, int M, int Mpad, hipStream_t stream) {
-    const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, cfg->tokens};
-    const int rc = block_attention_part(ctx, ly, x, a, qkv, M, Mpad, ATTN_CAUSAL);
-    return rc ? rc : block_mlp_part(ctx, ly, x, a, nullptr, M, Mpad, nullptr, 0, nullptr, nullptr, u);
-}
-
-// the unmasked tower's entry points for the backward sweep (towers.h; csrc/vit_grad.hip)
-int vit_embed_tokens(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_image_in &in, int B, const float *cv_emb,
-                     const VitLayout &v, _Float16 *patches, float *x, hipStream_t stream) {
-    const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, v.L};
-    return vit_embed_tokens_impl(ctx, cfg, w, in, B, cv_emb, v, patches, x);
-}
-
+// fp32 LayerNorm for the backward sweep (towers.h; csrc/vit_grad.hip)
 int vit_layernorm_f32(const float *x, int64_t rows, int W, const float *g, const float *b, float *out, hipStream_t stream) {
     hipLaunchKernelGGL(layernorm_kernel<0>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, rows, W, g, b, (void *)out,
                        (int64_t)W);
@@ -821,27 +797,27 @@ int vit_layernorm_f32(const float *x, int64_t rows, int W, const float *g, const
     return MPREID_OK;
 }
 
-int vit_block(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *qkv, _Float16 *hbuf,
-              int M, int Mpad, hipStream_t stream) {
-    const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, cfg->h_res * cfg->w_res + 1};
-    const int rc = block_attention_part(ctx, ly, x, a, qkv, M, Mpad, ATTN_ALL_ROWS);
-    return rc ? rc : block_mlp_part(ctx, ly, x, a, hbuf, M, Mpad, nullptr, 0, nullptr, nullptr);
+// the split mode's block and its parts for any tower (towers.h)
+static BlockCtx split_ctx(const BlockShape &s, hipStream_t stream) { return BlockCtx{stream, true, 2, s.W, s.heads, s.B, s.L}; }
+static AttnKind attn_kind(const BlockShape &s) { return s.causal ? ATTN_CAUSAL : ATTN_ALL_ROWS; }
+
+int tower_block(const BlockShape &s, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *qkv, _Float16 *hbuf, int Mpad,
+                hipStream_t stream) {
+    const BlockCtx ctx = split_ctx(s, stream);
+    const int rc = block_attention_part(ctx, ly, x, a, qkv, s.M(), Mpad, attn_kind(s));
+    return rc ? rc : block_mlp_part(ctx, ly, x, a, hbuf, s.M(), Mpad, nullptr, 0, nullptr, nullptr);
 }
 
-int vit_block_attention(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer &ly, const float *x, _Float16 *a, float *qkv,
-                        int M, int Mpad, hipStream_t stream) {
-    const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, cfg->h_res * cfg->w_res + 1};
-    return block_attention_part(ctx, ly, x, a, qkv, M, Mpad, ATTN_ALL_ROWS);
+int tower_block_attention(const BlockShape &s, const mpreid_vit_layer &ly, const float *x, _Float16 *a, float *qkv, int Mpad,
+                          hipStream_t stream) {
+    return block_attention_part(split_ctx(s, stream), ly, x, a, qkv, s.M(), Mpad, attn_kind(s));
 }
 
-int vit_block_mid(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, int M, int Mpad,
-                  hipStream_t stream) {
-    const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, cfg->h_res * cfg->w_res + 1};
-    return block_mid_part(ctx, ly, x, a, M, Mpad);
+int tower_block_mid(const BlockShape &s, const mpreid_vit_layer &ly, float *x, _Float16 *a, int Mpad, hipStream_t stream) {
+    return block_mid_part(split_ctx(s, stream), ly, x, a, s.M(), Mpad);
 }
 
-int vit_block_mlp_recompute(const mpreid_vit_cfg *cfg, int B, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *u, int M,
-                            int Mpad, hipStream_t stream) {
-    const BlockCtx ctx{stream, true, 2, cfg->width, cfg->heads, B, cfg->h_res * cfg->w_res + 1};
-    return block_mlp_part(ctx, ly, x, a, nullptr, M, Mpad, nullptr, 0, nullptr, nullptr, u);
+int tower_block_mlp_recompute(const BlockShape &s, const mpreid_vit_layer &ly, float *x, _Float16 *a, float *u, int Mpad,
+                              hipStream_t stream) {
+    return block_mlp_part(split_ctx(s, stream), ly, x, a, nullptr, s.M(), Mpad, nullptr, 0, nullptr, nullptr, u);
 }

@@ -4,16 +4,15 @@
 // over a small workspace of row statistics and streams the other operand through LDS in 64-row blocks, so its LDS request
 // does not depend on which operand is long.  No atomics: every sum has one fixed order, the same bits from run to run and
 // for an image alone or inside a batch.
+// Behind it: the transposing and column-sum kernels of the parameter gradients; the ONE differentiation of a residual block
+// (block_mlp_backward / block_attention_backward, declared in towers.h), which mpreid_text_backward (csrc/text_grad.hip)
+// calls with no parameter gradient and the causal attention kernel, and the sweep of this file with the kernels above; and
+// mpreid_vit_backward / mpreid_vit_backward_moe: the checks and the per-call state in vit_backward_impl, then the kept
+// forward, the head, the layer sweep and the embedding, one file-local function each.
 #include "moe.h"
 #include "towers.h"
 
 namespace {
-
-__device__ __forceinline__ void wave_lds_sync() {   // LDS written by this wave is read by this wave (text_grad.hip's mirror)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 constexpr int VB_NW = 8;      // waves per workgroup = query rows (pass 1) / key rows (pass 2) of a workgroup's tile
 constexpr int VB_BLK = 64;    // rows of the streamed operand per LDS block: one per lane
@@ -24,22 +23,6 @@ static int vb_lpad(int L) { return (L + VB_BLK - 1) / VB_BLK * VB_BLK; }
 static size_t vb_lds_rows(int L) { return ((size_t)2 * VB_BLK * VB_LD + 2 * VB_NW * VB_LD + (size_t)VB_NW * 2 * vb_lpad(L)) * sizeof(float); }
 // pass 2: Q and dO block, the tile's K and V rows, per wave a strip of P and a strip of dS over one block
 static size_t vb_lds_cols() { return ((size_t)2 * VB_BLK * VB_LD + 2 * VB_NW * VB_LD + (size_t)VB_NW * 2 * VB_BLK) * sizeof(float); }
-
-// sum_c a[c] * b[c] over the 64 features of a head, c ascending in one fmaf chain: the SAME bits wherever a score is needed
-// (text_grad.hip's dot64)
-__device__ __forceinline__ float dot64(const float *__restrict__ a, const float *__restrict__ b) {
-    float acc = 0.f;
-#pragma unroll
-    for (int c = 0; c < 64; c += 4) {
-        const float4 x = *reinterpret_cast<const float4 *>(a + c);
-        const float4 y = *reinterpret_cast<const float4 *>(b + c);
-        acc = fmaf(x.x, y.x, acc);
-        acc = fmaf(x.y, y.y, acc);
-        acc = fmaf(x.z, y.z, acc);
-        acc = fmaf(x.w, y.w, acc);
-    }
-    return acc;
-}
 
 // rows j0 .. j0 + 63 of one head of two [rows][ld] matrices -> two LDS blocks [64][VB_LD]; rows at or behind L are zeros
 __device__ __forceinline__ void load_block_pair(const float *__restrict__ a, const float *__restrict__ b, int64_t lda, int64_t ldb,
@@ -434,7 +417,9 @@ __global__ __launch_bounds__(256) void add_cls_rows_kernel(const float *__restri
 struct VitGradLayout {
     VitLayout f;
     int64_t Mp4, Bp4, tw;
-    size_t tok, xs, dx, dh, t, dqkv, aot, at, bt, stats, red, small, total;
+    size_t tok;
+    SweepRegions r;   // xs, dx, dh, t, dqkv (towers.h)
+    size_t aot, at, bt, stats, red, small, total;
     // an MoE tower's share, behind the dense sweep's: the routing of block 0, its logits, d_w summed over the MoE blocks,
     // d_logits, and the routed MLP's gradient workspace (tables of the dispatch, hidden, y, u)
     MoeGradLayout mg;
@@ -453,11 +438,7 @@ VitGradLayout vit_grad_layout(const mpreid_vit_cfg *c, int B, const mpreid_vit_m
     if (c->out_dim > v.tw) v.tw = c->out_dim;
     WsCursor take{v.f.total};
     v.tok = take(row);                             // the embedded sequence, ln_pre's input
-    v.xs = take(row * (size_t)c->layers);          // x_l, the input of block l
-    v.dx = take(row);                              // the gradient of the residual stream
-    v.dh = take(4 * row);                          // the gradient of the MLP's hidden layer
-    v.t = take(row);                               // the gradient of a LayerNorm output / of the attention output; ln_1(x_l)
-    v.dqkv = take(3 * row);
+    v.r = take_sweep_regions(take, row, c->layers);
     v.aot = take((size_t)v.Mp4 * W * 4);           // the attention output, transposed [W][Mp4]
     v.at = take((size_t)v.Mp4 * v.tw * 4);         // dY^T
     v.bt = take((size_t)v.Mp4 * v.tw * 4);         // X^T
@@ -523,13 +504,225 @@ extern "C" size_t mpreid_vit_backward_workspace_bytes(const mpreid_vit_cfg *cfg,
     return vit_grad_layout(cfg, batch).total;
 }
 
-// The sweep of both towers.  moe == nullptr: the dense tower.  Otherwise blocks l < moe->moe_layers (at least one) carry the
-// routed MLP: their MLP half goes through csrc/moe_grad.hip, everything else through the same code as a dense block's.
-static int vit_backward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_weights_t *wt,
-                             const mpreid_vit_moe *moe, const mpreid_vit_moe_t *moe_t, float aux_coef, float *d_gate_w,
-                             float *l_aux_out, const mpreid_image_in *img, int B, const float *cv_emb, const float *d_f_last,
-                             const float *d_f, const float *d_f_proj, const mpreid_vit_grads *grads, float *d_tokens, void *ws,
-                             size_t ws_bytes, mpreid_stream_t stream_) {
+// =====================================================================================================================
+// The one differentiation of a residual block (towers.h): the text tower's sweep (csrc/text_grad.hip, no parameter gradient)
+// and the image towers' below call these two halves.  A NULL member of g launches nothing and touches no buffer.
+// =====================================================================================================================
+// dW [n][k] = sum_m dY[m][n] X[m][k]: c.at = dY^T and c.bt = X^T hold the operands
+static int wgrad(const BlockGrad &c, float *out, int n, int k) {
+    return mpreid_gemm_f32_linear(c.at, c.bt, n, k, (int)c.Mp4, nullptr, out, k, F32_LIN, c.stream);
+}
+
+int block_mlp_backward(const BlockGrad &c, const mpreid_vit_layer &ly, const mpreid_text_layer_t &lt,
+                       const mpreid_vit_layer_grads &g) {
+    const int W = c.s.W, M = c.s.M();
+    hipStream_t stream = c.stream;
+    int rc;
+    if ((rc = tower_block_mlp_recompute(c.s, ly, c.x, c.a, c.u, c.Mpad, stream))) return rc;   // x = x_mid, a = ln_2(x_mid)
+    if (g.proj_w) {   // X = quickgelu(u), the fp32 value the forward's hidden pair is split from
+        if ((rc = launch_transpose(0, c.dx, M, W, W, 0, c.at, c.Mp4, stream))) return rc;
+        if ((rc = launch_transpose(1, c.u, M, 4 * W, 4 * W, 0, c.bt, c.Mp4, stream))) return rc;
+        if ((rc = wgrad(c, g.proj_w, W, 4 * W))) return rc;
+    }
+    if ((rc = launch_colsum(c.dx, W, nullptr, 0, M, W, g.proj_b, nullptr, c.red, stream))) return rc;
+    if ((rc = mpreid_gemm_f32_linear(c.dx, lt.proj_t, M, 4 * W, W, nullptr, c.dh, 4 * W, F32_LIN, stream))) return rc;
+    if ((rc = launch_quickgelu_backward(c.u, c.dh, (int64_t)M * W, stream))) return rc;   // dh = d/du; M * 4W / 4 float4
+    if (g.fc_w) {
+        if ((rc = launch_transpose(0, c.dh, M, 4 * W, 4 * W, 0, c.at, c.Mp4, stream))) return rc;
+        if ((rc = launch_transpose(2, c.a, M, W, 2 * W, 0, c.bt, c.Mp4, stream))) return rc;
+        if ((rc = wgrad(c, g.fc_w, 4 * W, W))) return rc;
+    }
+    if ((rc = launch_colsum(c.dh, 4 * W, nullptr, 0, M, 4 * W, g.fc_b, nullptr, c.red, stream))) return rc;
+    return mpreid_gemm_f32_linear(c.dh, lt.fc_t, M, W, 4 * W, nullptr, c.t, W, F32_LIN, stream);
+}
+
+int block_attention_backward(const BlockGrad &c, const mpreid_vit_layer &ly, const mpreid_text_layer_t &lt, const float *xl,
+                             const mpreid_vit_layer_grads &g) {
+    const int W = c.s.W, M = c.s.M();
+    hipStream_t stream = c.stream;
+    int rc;
+    if ((rc = launch_colsum(c.t, W, c.x, W, M, W, g.ln2_b, g.ln2_g, c.red, stream))) return rc;
+    if ((rc = launch_layernorm_backward(c.x, c.t, ly.ln2_g, M, W, true, c.dx, stream))) return rc;   // dx = d/dx_mid
+    if (g.out_proj_w) {
+        if ((rc = launch_transpose(0, c.dx, M, W, W, 0, c.at, c.Mp4, stream))) return rc;
+        if ((rc = mpreid_gemm_f32_linear(c.at, c.aot, W, W, (int)c.Mp4, nullptr, g.out_proj_w, W, F32_LIN, stream))) return rc;
+    }
+    if ((rc = launch_colsum(c.dx, W, nullptr, 0, M, W, g.out_proj_b, nullptr, c.red, stream))) return rc;
+    if ((rc = mpreid_gemm_f32_linear(c.dx, lt.out_proj_t, M, W, W, nullptr, c.t, W, F32_LIN, stream))) return rc;
+    if ((rc = c.s.causal ? launch_causal_attention_backward(c.qkv, c.t, c.s.B, c.s.L, W, c.s.heads, c.dqkv, stream)
+                         : vit_attention_backward_launch(c.qkv, c.t, c.s.B, c.s.L, W, c.s.heads, c.dqkv, c.stats, stream)))
+        return rc;
+    if (g.in_proj_w) {
+        if ((rc = vit_layernorm_f32(xl, M, W, ly.ln1_g, ly.ln1_b, c.t, stream))) return rc;   // the fp32 value in_proj's pair was split from
+        if ((rc = launch_transpose(0, c.dqkv, M, 3 * W, 3 * W, 0, c.at, c.Mp4, stream))) return rc;
+        if ((rc = launch_transpose(0, c.t, M, W, W, 0, c.bt, c.Mp4, stream))) return rc;
+        if ((rc = wgrad(c, g.in_proj_w, 3 * W, W))) return rc;
+    }
+    if ((rc = launch_colsum(c.dqkv, 3 * W, nullptr, 0, M, 3 * W, g.in_proj_b, nullptr, c.red, stream))) return rc;
+    if ((rc = mpreid_gemm_f32_linear(c.dqkv, lt.in_proj_t, M, W, 3 * W, nullptr, c.t, W, F32_LIN, stream))) return rc;
+    if ((rc = launch_colsum(c.t, W, xl, W, M, W, g.ln1_b, g.ln1_g, c.red, stream))) return rc;
+    return launch_layernorm_backward(xl, c.t, ly.ln1_g, M, W, true, c.dx, stream);   // dx = d/dx_l
+}
+
+// =====================================================================================================================
+// The sweep of both image towers.  moe == nullptr: the dense tower.  Otherwise blocks l < moe->moe_layers (at least one) carry
+// the routed MLP: their MLP half goes through csrc/moe_grad.hip, everything else through the same code as a dense block's.
+// =====================================================================================================================
+namespace {
+
+// dx[:, 0] += d_f_last
+int seed_f_last(const BlockGrad &c, const float *d_f_last) {
+    hipLaunchKernelGGL(add_cls_rows_kernel, dim3((unsigned)(((int64_t)c.s.B * c.s.W + 255) / 256)), dim3(256), 0, c.stream, d_f_last,
+                       c.s.B, c.s.L, c.s.W, c.dx);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
+// the forward, keeping the embedded sequence and every x_l
+int vit_backward_forward(const BlockGrad &c, const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_moe *moe,
+                         const mpreid_image_in &in, const float *cv_emb, const VitGradLayout &v, char *base) {
+    const int W = c.s.W, M = c.s.M(), n_moe = moe ? moe->moe_layers : 0;
+    float *tok = (float *)(base + v.tok), *xs = (float *)(base + v.r.xs);
+    int rc;
+    if ((rc = vit_embed_tokens(cfg, w, in, c.s.B, cv_emb, v.f, (_Float16 *)(base + v.f.patches), tok, true, c.stream)))
+        return rc;
+    if ((rc = vit_layernorm_f32(tok, M, W, w->ln_pre_g, w->ln_pre_b, c.x, c.stream))) return rc;
+    for (int l = 0; l < cfg->layers; ++l) {
+        const mpreid_vit_layer &ly = w->layers[l];
+        HIP_TRY(hipMemcpyAsync(xs + l * (size_t)c.Mpad * W, c.x, (size_t)M * W * 4, hipMemcpyDeviceToDevice, c.stream));
+        if (l >= n_moe) {
+            if ((rc = tower_block(c.s, ly, c.x, c.a, c.qkv, (_Float16 *)(base + v.f.hbuf), c.Mpad, c.stream))) return rc;
+            continue;
+        }
+        // an MoE block, launch for launch what mpreid_vit_forward_moe runs; block 0 keeps its routing and logits
+        if ((rc = tower_block_attention(c.s, ly, c.x, c.a, c.qkv, c.Mpad, c.stream))) return rc;
+        if ((rc = tower_block_mid(c.s, ly, c.x, c.a, c.Mpad, c.stream))) return rc;
+        if (l == 0) {
+            int32_t *sel = (int32_t *)(base + v.sel);
+            float *rw = (float *)(base + v.rw);
+            if ((rc = moe_route_launch(c.x, M, W, ly.ln2_g, ly.ln2_b, moe->layers[0].gate_w, moe->num_experts, moe->top_k, sel, rw,
+                                       (float *)(base + v.logits), c.stream)))
+                return rc;
+            if ((rc = moe_dispatch_launch(sel, rw, v.mg.fwd, base + v.moe, c.stream))) return rc;
+        }
+        if ((rc = moe_mlp_launch(c.a, v.mg.fwd, &moe->layers[l], c.x, base + v.moe, c.stream))) return rc;
+    }
+    return MPREID_OK;
+}
+
+// The head at the CLS rows, f = ln_post(x[:, 0]), f_proj = f @ proj: the gradients of proj and ln_post; dx = the seed of the
+// sweep.  small: CLS rows of x, the head's seed, f, the CLS rows' gradient
+int vit_backward_head(const BlockGrad &c, const mpreid_vit_weights *w, const mpreid_vit_grads *grads, const float *d_f,
+                      const float *d_f_proj, int od, int64_t Bp4, float *small) {
+    const int B = c.s.B, W = c.s.W;
+    hipStream_t stream = c.stream;
+    const size_t sb = align_up((size_t)B * W * 4, 256) / 4, rowb = (size_t)W * 4, seqb = rowb * c.s.L;
+    float *xc = small, *hy = small + sb, *fb = small + 2 * sb, *dxc = small + 3 * sb;
+    int rc;
+    HIP_TRY(hipMemcpy2DAsync(xc, rowb, c.x, seqb, rowb, (size_t)B, hipMemcpyDeviceToDevice, stream));
+    hipLaunchKernelGGL(vit_head_seed_kernel, dim3((unsigned)(((int64_t)B * W + 255) / 256)), dim3(256), 0, stream, d_f, d_f_proj,
+                       w->proj, B, W, od, hy);
+    LAUNCH_CHECK();
+    if (grads && grads->proj) {
+        if (d_f_proj) {
+            if ((rc = vit_layernorm_f32(xc, B, W, w->ln_post_g, w->ln_post_b, fb, stream))) return rc;
+            if ((rc = launch_transpose(0, fb, B, W, W, 0, c.at, Bp4, stream))) return rc;
+            if ((rc = launch_transpose(0, d_f_proj, B, od, od, 0, c.bt, Bp4, stream))) return rc;
+            if ((rc = mpreid_gemm_f32_linear(c.at, c.bt, W, od, (int)Bp4, nullptr, grads->proj, od, F32_LIN, stream))) return rc;
+        } else {
+            HIP_TRY(hipMemsetAsync(grads->proj, 0, (size_t)W * od * 4, stream));
+        }
+    }
+    if (grads && (rc = launch_colsum(hy, W, xc, W, B, W, grads->ln_post_b, grads->ln_post_g, c.red, stream))) return rc;
+    if ((rc = launch_layernorm_backward(xc, hy, w->ln_post_g, B, W, false, dxc, stream))) return rc;
+    HIP_TRY(hipMemsetAsync(c.dx, 0, (size_t)c.s.M() * W * 4, stream));
+    HIP_TRY(hipMemcpy2DAsync(c.dx, seqb, dxc, rowb, rowb, (size_t)B, hipMemcpyDeviceToDevice, stream));
+    return MPREID_OK;
+}
+
+// The layers, last to first: dx = d/dx_layers -> dx = d/dx_0.  An MoE block (l < moe->moe_layers) keeps its own MLP half:
+// x_{l+1} = x_mid + sum_e w_e expert_e(ln_2(x_mid)): t = d/dh through the experts, d_w summed over the MoE blocks
+int vit_backward_layers(const BlockGrad &c, int layers, const mpreid_vit_weights *w, const mpreid_vit_weights_t *wt,
+                        const mpreid_vit_grads *grads, const mpreid_vit_moe *moe, const mpreid_vit_moe_t *moe_t, float aux_coef,
+                        float *d_gate_w, float *l_aux_out, const float *d_f_last, const VitGradLayout &v, char *base) {
+    const int W = c.s.W, M = c.s.M(), n_moe = moe ? moe->moe_layers : 0, E = moe ? moe->num_experts : 0, K = moe ? moe->top_k : 0;
+    hipStream_t stream = c.stream;
+    const mpreid_vit_layer_grads none{};
+    // the MoE share (untouched offsets of a dense tower are never used)
+    int32_t *sel = (int32_t *)(base + v.sel);
+    float *d_w = (float *)(base + v.d_w), *d_logits = (float *)(base + v.d_logits);
+    char *mws = base + v.moe;
+    int rc;
+    for (int l = layers - 1; l >= 0; --l) {
+        const mpreid_vit_layer &ly = w->layers[l];
+        const mpreid_vit_layer_grads &g = grads ? grads->layers[l] : none;
+        const float *xl = (const float *)(base + v.r.xs) + l * (size_t)c.Mpad * W;
+        HIP_TRY(hipMemcpyAsync(c.x, xl, (size_t)M * W * 4, hipMemcpyDeviceToDevice, stream));
+        if ((rc = tower_block_attention(c.s, ly, c.x, c.a, c.qkv, c.Mpad, stream))) return rc;
+        if (g.out_proj_w && (rc = launch_transpose(2, c.a, M, W, 2 * W, 0, c.aot, c.Mp4, stream))) return rc;
+        if (l >= n_moe) {
+            if ((rc = block_mlp_backward(c, ly, wt->layers[l], g))) return rc;
+        } else {
+            if ((rc = tower_block_mid(c.s, ly, c.x, c.a, c.Mpad, stream))) return rc;   // x = x_mid, a = ln_2(x_mid)
+            if ((rc = moe_mlp_backward_launch(c.a, sel, v.mg, &moe->layers[l], &moe_t->layers[l], c.dx, c.t, d_w, l != n_moe - 1, mws,
+                                              stream)))
+                return rc;
+            if (l == 0) {   // every MoE block has added to d_w: the router, its gate, and the gate's share of d/dh
+                if ((rc = moe_route_backward_ws((const float *)(base + v.logits), sel, (const float *)(base + v.rw), d_w, M, E, K,
+                                                aux_coef, d_logits, l_aux_out, (const int *)(mws + v.mg.fwd.meta) + MOE_META_COUNTS,
+                                                mws + v.mg.cnt_blk, stream)))
+                    return rc;
+                if (d_gate_w) {   // d gate = d_logits^T . h, h the fp32 LayerNorm output the router saw
+                    if ((rc = vit_layernorm_f32(c.x, M, W, ly.ln2_g, ly.ln2_b, c.dh, stream))) return rc;
+                    if ((rc = launch_transpose(0, d_logits, M, E, E, 0, c.at, c.Mp4, stream))) return rc;
+                    if ((rc = launch_transpose(0, c.dh, M, W, W, 0, c.bt, c.Mp4, stream))) return rc;
+                    if ((rc = wgrad(c, d_gate_w, E, W))) return rc;
+                }
+                if ((rc = moe_gate_dh_launch(d_logits, moe->layers[0].gate_w, M, W, E, c.t, stream))) return rc;
+            }
+        }
+        if ((rc = block_attention_backward(c, ly, wt->layers[l], xl, g))) return rc;
+        // the dense tower's f_last is the CLS row of the last block's input
+        if (!moe && l == layers - 1 && d_f_last && (rc = seed_f_last(c, d_f_last))) return rc;
+    }
+    return MPREID_OK;
+}
+
+// ln_pre, then the embedding: tokens = [class_emb + cv_emb | conv1(patches)] + pos_emb
+int vit_backward_embed(const BlockGrad &c, const mpreid_vit_weights *w, const mpreid_vit_grads *grads, float *d_tokens,
+                       const VitGradLayout &v, char *base) {
+    const VitLayout &f = v.f;
+    const int B = c.s.B, W = c.s.W, L = c.s.L, M = c.s.M();
+    hipStream_t stream = c.stream;
+    const float *tok = (const float *)(base + v.tok);
+    const size_t rowb = (size_t)W * 4, seqb = rowb * L;
+    int rc;
+    if (grads && (rc = launch_colsum(c.dx, W, tok, W, M, W, grads->ln_pre_b, grads->ln_pre_g, c.red, stream))) return rc;
+    const bool need_tok = d_tokens || (grads && (grads->conv_w || grads->class_emb || grads->pos_emb || grads->cv_emb));
+    if (!need_tok) return MPREID_OK;
+    float *dtok = d_tokens ? d_tokens : c.t;
+    if ((rc = launch_layernorm_backward(tok, c.dx, w->ln_pre_g, M, W, false, dtok, stream))) return rc;
+    if (!grads) return MPREID_OK;
+    if (grads->cv_emb)
+        HIP_TRY(hipMemcpy2DAsync(grads->cv_emb, rowb, dtok, seqb, rowb, (size_t)B, hipMemcpyDeviceToDevice, stream));
+    if ((rc = launch_colsum(dtok, (int64_t)L * W, nullptr, 0, B, W, grads->class_emb, nullptr, c.red, stream))) return rc;
+    if ((rc = launch_colsum(dtok, (int64_t)L * W, nullptr, 0, B, L * W, grads->pos_emb, nullptr, c.red, stream))) return rc;
+    if (grads->conv_w) {   // over the B * P patch rows; X = the patch pairs the forward's GEMM multiplied
+        const int64_t MP = (int64_t)B * f.P, MP4 = (int64_t)align_up((size_t)MP, 4);
+        if ((rc = launch_transpose(0, dtok, MP, W, W, f.P, c.at, MP4, stream))) return rc;
+        if ((rc = launch_transpose(2, base + f.patches, MP, f.Kp, 2 * (int64_t)f.Kp, 0, c.bt, MP4, stream))) return rc;
+        if ((rc = mpreid_gemm_f32_linear(c.at, c.bt, W, f.Kp, (int)MP4, nullptr, grads->conv_w, f.Kp, F32_LIN, stream))) return rc;
+    }
+    return MPREID_OK;
+}
+
+// Both entry points: every refusal in their one order, all before anything is launched; then the per-call state (layout,
+// BlockGrad) and the five steps above
+int vit_backward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_weights_t *wt,
+                      const mpreid_vit_moe *moe, const mpreid_vit_moe_t *moe_t, float aux_coef, float *d_gate_w, float *l_aux_out,
+                      const mpreid_image_in *img, int B, const float *cv_emb, const float *d_f_last, const float *d_f,
+                      const float *d_f_proj, const mpreid_vit_grads *grads, float *d_tokens, void *ws, size_t ws_bytes,
+                      mpreid_stream_t stream_) {
     int rc = vit_backward_check_cfg(cfg);
     if (rc) return rc;
     const int n_moe = moe ? moe->moe_layers : 0;
@@ -580,179 +773,24 @@ static int vit_backward_impl(const mpreid_vit_cfg *cfg, const mpreid_vit_weights
         return MPREID_ERR_WORKSPACE;
     }
     ARG_CHECK(((uintptr_t)ws & 255) == 0);
-    hipStream_t stream = (hipStream_t)stream_;
-    const int W = cfg->width, L = v.f.L, M = v.f.M, Mpad = v.f.Mpad, od = cfg->out_dim;
-    const int64_t Mp4 = v.Mp4;
     char *base = (char *)ws;
-    _Float16 *patches = (_Float16 *)(base + v.f.patches);
-    float *x = (float *)(base + v.f.x);
-    _Float16 *a = (_Float16 *)(base + v.f.a);
-    float *qkv = (float *)(base + v.f.qkv);
-    _Float16 *hbuf = (_Float16 *)(base + v.f.hbuf);
-    float *u = (float *)(base + v.f.hbuf);   // the sweep's use of the region
-    float *tok = (float *)(base + v.tok);
-    float *xs = (float *)(base + v.xs);
-    float *dx = (float *)(base + v.dx);
-    float *dh = (float *)(base + v.dh);
-    float *t = (float *)(base + v.t);
-    float *dqkv = (float *)(base + v.dqkv);
-    float *aot = (float *)(base + v.aot);
-    float *at = (float *)(base + v.at);
-    float *bt = (float *)(base + v.bt);
-    void *stats = base + v.stats;
-    void *red = base + v.red;
-    const size_t sb = align_up((size_t)B * W * 4, 256);
-    float *xc = (float *)(base + v.small), *hy = (float *)(base + v.small + sb), *fb = (float *)(base + v.small + 2 * sb),
-          *dxc = (float *)(base + v.small + 3 * sb);
-    const size_t xbytes = (size_t)M * W * 4, xstride = (size_t)Mpad * W;
-    const size_t rowb = (size_t)W * 4, seqb = (size_t)L * W * 4;
-    const mpreid_vit_layer_grads none{};
-    // the MoE share (untouched offsets of a dense tower are never used)
-    int32_t *sel = (int32_t *)(base + v.sel);
-    float *rw = (float *)(base + v.rw), *logits = (float *)(base + v.logits), *d_w = (float *)(base + v.d_w),
-          *d_logits = (float *)(base + v.d_logits);
-    char *mws = base + v.moe;
-    const int E = moe ? moe->num_experts : 0, K = moe ? moe->top_k : 0;
-    // dW [n][k] = sum_m dY[m][n] X[m][k]: at = dY^T and bt = X^T hold the operands
-    auto wgrad = [&](float *out, int n, int k) {
-        return mpreid_gemm_f32_linear(at, bt, n, k, (int)Mp4, nullptr, out, k, F32_LIN, stream);
-    };
-
-    // the forward, keeping the embedded sequence and every x_l
-    if ((rc = vit_embed_tokens(cfg, w, in, B, cv_emb, v.f, patches, tok, stream))) return rc;
-    if ((rc = vit_layernorm_f32(tok, M, W, w->ln_pre_g, w->ln_pre_b, x, stream))) return rc;
-    for (int l = 0; l < cfg->layers; ++l) {
-        HIP_TRY(hipMemcpyAsync(xs + l * xstride, x, xbytes, hipMemcpyDeviceToDevice, stream));
-        if (l >= n_moe) {
-            if ((rc = vit_block(cfg, B, w->layers[l], x, a, qkv, hbuf, M, Mpad, stream))) return rc;
-            continue;
-        }
-        // an MoE block, launch for launch what mpreid_vit_forward_moe runs; block 0 keeps its routing and logits
-        const mpreid_vit_layer &ly = w->layers[l];
-        if ((rc = vit_block_attention(cfg, B, ly, x, a, qkv, M, Mpad, stream))) return rc;
-        if ((rc = vit_block_mid(cfg, B, ly, x, a, M, Mpad, stream))) return rc;
-        if (l == 0) {
-            if ((rc = moe_route_launch(x, M, W, ly.ln2_g, ly.ln2_b, moe->layers[0].gate_w, E, K, sel, rw, logits, stream))) return rc;
-            if ((rc = moe_dispatch_launch(sel, rw, v.mg.fwd, mws, stream))) return rc;
-        }
-        if ((rc = moe_mlp_launch(a, v.mg.fwd, &moe->layers[l], x, mws, stream))) return rc;
-    }
-    // the head at the CLS rows: f = ln_post(x[:, 0]), f_proj = f @ proj
-    HIP_TRY(hipMemcpy2DAsync(xc, rowb, x, seqb, rowb, (size_t)B, hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(vit_head_seed_kernel, dim3((unsigned)(((int64_t)B * W + 255) / 256)), dim3(256), 0, stream, d_f, d_f_proj,
-                       w->proj, B, W, od, hy);
-    LAUNCH_CHECK();
-    if (grads && grads->proj) {
-        if (d_f_proj) {
-            if ((rc = vit_layernorm_f32(xc, B, W, w->ln_post_g, w->ln_post_b, fb, stream))) return rc;
-            if ((rc = launch_transpose(0, fb, B, W, W, 0, at, v.Bp4, stream))) return rc;
-            if ((rc = launch_transpose(0, d_f_proj, B, od, od, 0, bt, v.Bp4, stream))) return rc;
-            if ((rc = mpreid_gemm_f32_linear(at, bt, W, od, (int)v.Bp4, nullptr, grads->proj, od, F32_LIN, stream))) return rc;
-        } else {
-            HIP_TRY(hipMemsetAsync(grads->proj, 0, (size_t)W * od * 4, stream));
-        }
-    }
-    if (grads && (rc = launch_colsum(hy, W, xc, W, B, W, grads->ln_post_b, grads->ln_post_g, red, stream))) return rc;
-    if ((rc = launch_layernorm_backward(xc, hy, w->ln_post_g, B, W, false, dxc, stream))) return rc;
-    HIP_TRY(hipMemsetAsync(dx, 0, xbytes, stream));
-    HIP_TRY(hipMemcpy2DAsync(dx, seqb, dxc, rowb, rowb, (size_t)B, hipMemcpyDeviceToDevice, stream));
-    auto seed_f_last = [&]() -> int {
-        hipLaunchKernelGGL(add_cls_rows_kernel, dim3((unsigned)(((int64_t)B * W + 255) / 256)), dim3(256), 0, stream, d_f_last, B, L,
-                           W, dx);
-        LAUNCH_CHECK();
-        return MPREID_OK;
-    };
+    auto f32 = [&](size_t off) { return (float *)(base + off); };
+    BlockGrad c{};   // u is the sweep's use of the hbuf region: the same 16 W bytes per row
+    c.s = {cfg->width, cfg->heads, B, v.f.L, false}; c.Mpad = v.f.Mpad; c.Mp4 = v.Mp4; c.stream = (hipStream_t)stream_;
+    c.x = f32(v.f.x); c.a = (_Float16 *)(base + v.f.a); c.qkv = f32(v.f.qkv); c.u = f32(v.f.hbuf);
+    c.dx = f32(v.r.dx); c.dh = f32(v.r.dh); c.t = f32(v.r.t); c.dqkv = f32(v.r.dqkv);
+    c.aot = f32(v.aot); c.at = f32(v.at); c.bt = f32(v.bt); c.stats = base + v.stats; c.red = base + v.red;
+    if ((rc = vit_backward_forward(c, cfg, w, moe, in, cv_emb, v, base))) return rc;
+    if ((rc = vit_backward_head(c, w, grads, d_f, d_f_proj, cfg->out_dim, v.Bp4, f32(v.small)))) return rc;
     // an MoE tower's f_last is the CLS row of the LAST block's OUTPUT (model/clip/model.py:448-454): its seed joins dx in
     // front of the sweep
-    if (moe && d_f_last && (rc = seed_f_last())) return rc;
-
-    for (int l = cfg->layers - 1; l >= 0; --l) {
-        const mpreid_vit_layer &ly = w->layers[l];
-        const mpreid_vit_layer_t &lt = wt->layers[l];
-        const mpreid_vit_layer_grads &g = grads ? grads->layers[l] : none;
-        const float *xl = xs + l * xstride;
-        HIP_TRY(hipMemcpyAsync(x, xl, xbytes, hipMemcpyDeviceToDevice, stream));
-        if ((rc = vit_block_attention(cfg, B, ly, x, a, qkv, M, Mpad, stream))) return rc;
-        if (g.out_proj_w && (rc = launch_transpose(2, a, M, W, 2 * W, 0, aot, Mp4, stream))) return rc;
-        if (l < n_moe) {
-            // x_{l+1} = x_mid + sum_e w_e expert_e(ln_2(x_mid)): t = d/dh through the experts, d_w summed over the MoE blocks
-            if ((rc = vit_block_mid(cfg, B, ly, x, a, M, Mpad, stream))) return rc;   // x = x_mid, a = ln_2(x_mid)
-            if ((rc = moe_mlp_backward_launch(a, sel, v.mg, &moe->layers[l], &moe_t->layers[l], dx, t, d_w, l != n_moe - 1, mws,
-                                              stream)))
-                return rc;
-            if (l == 0) {   // every MoE block has added to d_w: the router, its gate, and the gate's share of d/dh
-                if ((rc = moe_route_backward_ws(logits, sel, rw, d_w, M, E, K, aux_coef, d_logits, l_aux_out,
-                                                (const int *)(mws + v.mg.fwd.meta) + MOE_META_COUNTS, mws + v.mg.cnt_blk, stream)))
-                    return rc;
-                if (d_gate_w) {   // d gate = d_logits^T . h, h the fp32 LayerNorm output the router saw
-                    if ((rc = vit_layernorm_f32(x, M, W, ly.ln2_g, ly.ln2_b, dh, stream))) return rc;
-                    if ((rc = launch_transpose(0, d_logits, M, E, E, 0, at, Mp4, stream))) return rc;
-                    if ((rc = launch_transpose(0, dh, M, W, W, 0, bt, Mp4, stream))) return rc;
-                    if ((rc = wgrad(d_gate_w, E, W))) return rc;
-                }
-                if ((rc = moe_gate_dh_launch(d_logits, moe->layers[0].gate_w, M, W, E, t, stream))) return rc;
-            }
-        } else {
-            if ((rc = vit_block_mlp_recompute(cfg, B, ly, x, a, u, M, Mpad, stream))) return rc;   // x = x_mid, a = ln_2(x_mid)
-            // x_{l+1} = x_mid + c_proj(quickgelu(c_fc(ln_2(x_mid))))
-            if (g.proj_w) {   // X = quickgelu(u), the fp32 value the forward's hidden pair is split from
-                if ((rc = launch_transpose(0, dx, M, W, W, 0, at, Mp4, stream))) return rc;
-                if ((rc = launch_transpose(1, u, M, 4 * W, 4 * W, 0, bt, Mp4, stream))) return rc;
-                if ((rc = wgrad(g.proj_w, W, 4 * W))) return rc;
-            }
-            if ((rc = launch_colsum(dx, W, nullptr, 0, M, W, g.proj_b, nullptr, red, stream))) return rc;
-            if ((rc = mpreid_gemm_f32_linear(dx, lt.proj_t, M, 4 * W, W, nullptr, dh, 4 * W, F32_LIN, stream))) return rc;
-            if ((rc = launch_quickgelu_backward(u, dh, (int64_t)M * W, stream))) return rc;   // dh = d/du
-            if (g.fc_w) {
-                if ((rc = launch_transpose(0, dh, M, 4 * W, 4 * W, 0, at, Mp4, stream))) return rc;
-                if ((rc = launch_transpose(2, a, M, W, 2 * W, 0, bt, Mp4, stream))) return rc;
-                if ((rc = wgrad(g.fc_w, 4 * W, W))) return rc;
-            }
-            if ((rc = launch_colsum(dh, 4 * W, nullptr, 0, M, 4 * W, g.fc_b, nullptr, red, stream))) return rc;
-            if ((rc = mpreid_gemm_f32_linear(dh, lt.fc_t, M, W, 4 * W, nullptr, t, W, F32_LIN, stream))) return rc;
-        }
-        if ((rc = launch_colsum(t, W, x, W, M, W, g.ln2_b, g.ln2_g, red, stream))) return rc;
-        if ((rc = launch_layernorm_backward(x, t, ly.ln2_g, M, W, true, dx, stream))) return rc;   // dx = d/dx_mid
-        // x_mid = x_l + out_proj(attention(in_proj(ln_1(x_l))))
-        if (g.out_proj_w) {
-            if ((rc = launch_transpose(0, dx, M, W, W, 0, at, Mp4, stream))) return rc;
-            if ((rc = mpreid_gemm_f32_linear(at, aot, W, W, (int)Mp4, nullptr, g.out_proj_w, W, F32_LIN, stream))) return rc;
-        }
-        if ((rc = launch_colsum(dx, W, nullptr, 0, M, W, g.out_proj_b, nullptr, red, stream))) return rc;
-        if ((rc = mpreid_gemm_f32_linear(dx, lt.out_proj_t, M, W, W, nullptr, t, W, F32_LIN, stream))) return rc;
-        if ((rc = vit_attention_backward_launch(qkv, t, B, L, W, cfg->heads, dqkv, stats, stream))) return rc;
-        if (g.in_proj_w) {
-            if ((rc = vit_layernorm_f32(xl, M, W, ly.ln1_g, ly.ln1_b, t, stream))) return rc;   // the fp32 value in_proj's pair was split from
-            if ((rc = launch_transpose(0, dqkv, M, 3 * W, 3 * W, 0, at, Mp4, stream))) return rc;
-            if ((rc = launch_transpose(0, t, M, W, W, 0, bt, Mp4, stream))) return rc;
-            if ((rc = wgrad(g.in_proj_w, 3 * W, W))) return rc;
-        }
-        if ((rc = launch_colsum(dqkv, 3 * W, nullptr, 0, M, 3 * W, g.in_proj_b, nullptr, red, stream))) return rc;
-        if ((rc = mpreid_gemm_f32_linear(dqkv, lt.in_proj_t, M, W, 3 * W, nullptr, t, W, F32_LIN, stream))) return rc;
-        if ((rc = launch_colsum(t, W, xl, W, M, W, g.ln1_b, g.ln1_g, red, stream))) return rc;
-        if ((rc = launch_layernorm_backward(xl, t, ly.ln1_g, M, W, true, dx, stream))) return rc;   // dx = d/dx_l
-        // the dense tower's f_last is the CLS row of the last block's input
-        if (!moe && l == cfg->layers - 1 && d_f_last && (rc = seed_f_last())) return rc;
-    }
-    // ln_pre, then the embedding: tokens = [class_emb + cv_emb | conv1(patches)] + pos_emb
-    if (grads && (rc = launch_colsum(dx, W, tok, W, M, W, grads->ln_pre_b, grads->ln_pre_g, red, stream))) return rc;
-    const bool need_tok = d_tokens || (grads && (grads->conv_w || grads->class_emb || grads->pos_emb || grads->cv_emb));
-    if (!need_tok) return MPREID_OK;
-    float *dtok = d_tokens ? d_tokens : t;
-    if ((rc = launch_layernorm_backward(tok, dx, w->ln_pre_g, M, W, false, dtok, stream))) return rc;
-    if (!grads) return MPREID_OK;
-    if (grads->cv_emb)
-        HIP_TRY(hipMemcpy2DAsync(grads->cv_emb, rowb, dtok, seqb, rowb, (size_t)B, hipMemcpyDeviceToDevice, stream));
-    if ((rc = launch_colsum(dtok, (int64_t)L * W, nullptr, 0, B, W, grads->class_emb, nullptr, red, stream))) return rc;
-    if ((rc = launch_colsum(dtok, (int64_t)L * W, nullptr, 0, B, L * W, grads->pos_emb, nullptr, red, stream))) return rc;
-    if (grads->conv_w) {   // over the B * P patch rows; X = the patch pairs the forward's GEMM multiplied
-        const int64_t MP = (int64_t)B * v.f.P, MP4 = (int64_t)align_up((size_t)MP, 4);
-        if ((rc = launch_transpose(0, dtok, MP, W, W, v.f.P, at, MP4, stream))) return rc;
-        if ((rc = launch_transpose(2, patches, MP, v.f.Kp, 2 * (int64_t)v.f.Kp, 0, bt, MP4, stream))) return rc;
-        if ((rc = mpreid_gemm_f32_linear(at, bt, W, v.f.Kp, (int)MP4, nullptr, grads->conv_w, v.f.Kp, F32_LIN, stream))) return rc;
-    }
-    return MPREID_OK;
+    if (moe && d_f_last && (rc = seed_f_last(c, d_f_last))) return rc;
+    if ((rc = vit_backward_layers(c, cfg->layers, w, wt, grads, moe, moe_t, aux_coef, d_gate_w, l_aux_out, d_f_last, v, base)))
+        return rc;
+    return vit_backward_embed(c, w, grads, d_tokens, v, base);
 }
+
+}   // namespace
 
 extern "C" int mpreid_vit_backward(const mpreid_vit_cfg *cfg, const mpreid_vit_weights *w, const mpreid_vit_weights_t *wt,
                                    const mpreid_image_in *img, int B, const float *cv_emb, const float *d_f_last,

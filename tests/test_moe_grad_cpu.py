@@ -205,6 +205,27 @@ def test_tower_workspace_queries_answer_without_a_device_and_exceed_the_dense_on
         assert L.mpreid_vit_backward_moe_workspace_bytes(C.byref(c), C.byref(none), 3) == 0
 
 
+# mpreid_vit_backward_moe_workspace_bytes with (E, K, moe_layers) = (2, 1, 1) and (4, 2, 2), as the library answered before both
+# sweeps took their shared regions (x_l, dx, dh, t, dqkv) through one definition.  "small" is SMALL of
+# tests/test_gpu_tower_launches.py at 64 x 32, "full" ViT-B/16 at 256 x 128; both in the split precision
+SMALL_VIT = dict(h_res=4, w_res=2, patch=16, stride=16, width=128, layers=2, heads=2, out_dim=64)
+BACKWARD_MOE_WORKSPACE_BYTES = {("small", 1): (5866240, 7047936), ("small", 3): (5977344, 7159552), ("small", 64): (18457088, 22022912),
+                                ("full", 1): (46566400, 57190912), ("full", 3): (85973760, 103687424),
+                                ("full", 64): (1302221312, 1536156928)}
+
+
+@pytest.mark.parametrize("size,batch", sorted(BACKWARD_MOE_WORKSPACE_BYTES))
+def test_tower_backward_workspace_bytes(size, batch):
+    from mpreid import synth
+    L = _lib.load()
+    cfg, hw = (SMALL_VIT, (64, 32)) if size == "small" else (synth.VIT_B16, (256, 128))
+    got = []
+    for E, K, n_moe in ((2, 1, 1), (4, 2, 2)):
+        c, moe, keep = _vit_cfg_structs(dict(cfg, num_experts=E, top_k=K, moe_layers=n_moe), hw)
+        got.append(L.mpreid_vit_backward_moe_workspace_bytes(C.byref(c), C.byref(moe), batch))
+    assert tuple(got) == BACKWARD_MOE_WORKSPACE_BYTES[(size, batch)]
+
+
 def test_masters_of_an_moe_tower_and_the_host_refusals():
     """the masters are the dense parameters and block 0's gate: no later gate, no expert, no mlp.* of an MoE block; an expert
     that requires grad is refused by name; the model's opt-in refuses a dense tower"""

@@ -74,6 +74,20 @@ def test_backward_workspace_query_needs_no_device():
     assert bwd(ctypes.byref(_lib.TextCfg(21, 128, -1, 2, 64)), 2) == 0
 
 
+# mpreid_text_backward_workspace_bytes as the library answered before both sweeps took their shared regions (x_l, dx, dh, t,
+# dqkv) through one definition: (tower, batch) -> bytes.  "small" is TEXT of tests/test_gpu_tower_launches.py
+SMALL_TEXT = dict(tokens=17, width=128, layers=2, heads=2, out_dim=64)
+BACKWARD_WORKSPACE_BYTES = {("small", 1): 2621952, ("small", 3): 2622976, ("small", 64): 13139968,
+                            ("full", 1): 15730688, ("full", 3): 15734784, ("full", 64): 314703872}
+
+
+@pytest.mark.parametrize("size,batch", sorted(BACKWARD_WORKSPACE_BYTES))
+def test_backward_workspace_bytes(size, batch):
+    c = SMALL_TEXT if size == "small" else synth.CLIP_TEXT
+    cfg = _lib.TextCfg(*(c[k] for k in ("tokens", "width", "layers", "heads", "out_dim")))
+    assert _lib.load().mpreid_text_backward_workspace_bytes(ctypes.byref(cfg), batch) == BACKWARD_WORKSPACE_BYTES[(size, batch)]
+
+
 def test_text_backward_checks_its_arguments_before_any_launch():
     """no device here: every refusal below happens before the first HIP call"""
     L = _lib.load()

@@ -195,6 +195,25 @@ def test_backward_workspace_bytes_and_argument_errors_before_any_launch():
     assert run(good) == _lib.ERR_ARG
 
 
+# (mpreid_vit_backward_workspace_bytes, mpreid_vit_attention_backward_workspace_bytes) as the library answered before both
+# sweeps took their shared regions (x_l, dx, dh, t, dqkv) through one definition.  "small" is SMALL of
+# tests/test_gpu_tower_launches.py at 64 x 32, "full" ViT-B/16 at 256 x 128; both in the split precision
+SMALL_VIT = dict(h_res=4, w_res=2, patch=16, stride=16, width=128, layers=2, heads=2, out_dim=64)
+BACKWARD_WORKSPACE_BYTES = {("small", 1): (4089600, 512), ("small", 3): (4200704, 1024), ("small", 64): (14297600, 18432),
+                            ("full", 1): (32397824, 24832), ("full", 3): (64715776, 74496), ("full", 64): (1064735232, 1585152)}
+
+
+@pytest.mark.parametrize("size,batch", sorted(BACKWARD_WORKSPACE_BYTES))
+def test_backward_workspace_bytes(size, batch):
+    L = _lib.load()
+    c, hw = (SMALL_VIT, (64, 32)) if size == "small" else (synth.VIT_B16, (256, 128))
+    cfg = _lib.VitCfg(hw[0], hw[1], c["patch"], c["stride"], c["h_res"], c["w_res"], c["width"], c["layers"], c["heads"],
+                      c["out_dim"], 0, 1, _lib.VIT_SPLIT)
+    got = (L.mpreid_vit_backward_workspace_bytes(ctypes.byref(cfg), batch),
+           L.mpreid_vit_attention_backward_workspace_bytes(batch, c["h_res"] * c["w_res"] + 1, c["heads"]))
+    assert got == BACKWARD_WORKSPACE_BYTES[(size, batch)]
+
+
 def test_transpose_and_colsum_check_their_arguments():
     L = _lib.load()
     d = ctypes.c_void_p(0x1000)

@@ -6,7 +6,12 @@ with and without the CLS-only tail, all-fp32, MoE with E = 2 / K = 1 / one MoE b
 of tests/test_gpu_rn50.py in its three precisions, plus ViT-B/16 split at B = 16 and CLIP's text tower at B = 8, and runs
 one forward each.  The image towers also take the same images as uint8 and every test-time-augmentation view from fp32 and
 from uint8 input: every instance of the patch gather, the stems and the head is in the listing.  The library and the Python packer are those of the checkout this file sits in: run it
-once in each tree and diff the two listings.  Usage: python tools/tower_bits.py"""
+once in each tree and diff the two listings.
+Then the gradients, one line per returned tensor: TextEncoder.backward on the two text towers; VitEncoder.backward on the small
+dense tower asking for everything, for the bias and LayerNorm names only (column sums without a weight-gradient GEMM) and for
+"tokens" alone (no parameter gradient at all: the path the text sweep shares); on a dense tower of 73 tokens (more than one
+64-row block of the attention gradient); on MoE towers with (E, K, MoE blocks) = (2, 1, 1) and (4, 2, 2), aux_coef 0.01 and
+the gate's gradient; and on ViT-B/16 split at B = 16 with every parameter.  Usage: python tools/tower_bits.py"""
 import hashlib
 import os
 import sys
@@ -62,6 +67,50 @@ def text_tower(name, cfg, batch):
     ops.release_workspaces()
 
 
+def text_grads(name, cfg, batch):
+    enc = ops.TextEncoder(cfg, synth.text_state_dict(cfg, seed=21), ws_tag="bits_" + name)
+    gen = torch.Generator().manual_seed(2)
+    prompts = (torch.randn((batch, cfg["tokens"], cfg["width"]), generator=gen) * 0.02).cuda()
+    grad_out = torch.randn((batch, cfg["out_dim"]), generator=gen).cuda()
+    show(name + " d prompts", enc.backward(prompts, [(5 * i + 3) % cfg["tokens"] for i in range(batch)], grad_out))
+    del enc
+    ops.release_workspaces()
+
+
+def image_grads(name, cfg, sd, hw, batch, wants=(("", None),), aux_coef=0.0):
+    """VitEncoder.backward with all three seeds and a cv_emb; wants: (label, names or None = every parameter + cv_emb + tokens)"""
+    enc = ops.VitEncoder(cfg, sd, hw, ws_tag="bits_" + name)
+    enc.enable_training()
+    gen = torch.Generator().manual_seed(4)
+    w, od = cfg["width"], cfg["out_dim"]
+    x = torch.from_numpy(synth.synthetic_images(batch, hw[0], hw[1], seed=3)).cuda()
+    cv = (torch.randn((batch, w), generator=gen) * 0.02).cuda()
+    seeds = [torch.randn((batch, d), generator=gen).cuda() for d in (w, w, od)]
+    every = [key for key, _, _ in enc._param_fields()]
+    for label, names in wants:
+        want = every + ["cv_emb", "tokens"] if names is None else [k for k in every + ["cv_emb", "tokens"] if names(k)]
+        got = enc.backward(x, cv, *seeds, want=want, aux_coef=aux_coef)
+        assert list(got) == want
+        for key in want:
+            show(name + label + " d " + key.replace("transformer.resblocks.", ""), got[key])
+    del enc
+    ops.release_workspaces()
+
+
+def gradients():
+    text_grads("small text", TEXT, 3)
+    text_grads("clip_text", synth.CLIP_TEXT, 8)
+    sd = synth.vit_state_dict(SMALL, seed=7, std=0.05, ln_jitter=0.1)
+    image_grads("small", SMALL, sd, (64, 32), 3, wants=(
+        (" all", None), (" bias+ln", lambda k: k.endswith("bias") or "ln_" in k), (" tokens", lambda k: k == "tokens")))
+    long = dict(h_res=9, w_res=8, patch=16, stride=16, width=128, layers=2, heads=2, out_dim=64)
+    image_grads("73 tokens", long, synth.vit_state_dict(long, seed=7, std=0.05, ln_jitter=0.1), (144, 128), 2)
+    for E, K, n_moe in ((2, 1, 1), (4, 2, 2)):
+        moe = dict(SMALL, num_experts=E, top_k=K, moe_layers=n_moe)
+        image_grads("moe %d/%d/%d" % (E, K, n_moe), moe, synth.vit_moe_state_dict(moe, seed=7), (64, 32), 3, aux_coef=0.01)
+    image_grads("vit_b16", synth.VIT_B16, synth.vit_state_dict(synth.VIT_B16, seed=7), (256, 128), 16)
+
+
 def main():
     sd = synth.vit_state_dict(SMALL, seed=7, std=0.05, ln_jitter=0.1)
     image_tower("small fp16", SMALL, sd, (64, 32), 3, precision="fp16")
@@ -76,6 +125,7 @@ def main():
     rn50_tower("rn50 split", "split", VIEWS)
     image_tower("vit_b16 split", synth.VIT_B16, synth.vit_state_dict(synth.VIT_B16, seed=7), (256, 128), 16, views=VIEWS[:1])
     text_tower("clip_text", synth.CLIP_TEXT, 8)
+    gradients()
 
 
 if __name__ == "__main__":
