@@ -192,13 +192,15 @@ _WIDE = dict(h_res=8, w_res=4, patch=16, stride=16, width=128, layers=2, heads=2
 #: name -> (tower cfg, image (h, w), images, base seed, weight std).  The first three are moe_cases' shapes (2 of 3 blocks MoE;
 #: every block MoE with K = 1, where the routing gradient is exactly zero; 33 tokens and 8 experts); `full`: CLIP's width, heads
 #: and depth at 9 tokens, 27 rows; `rows1320`: 40 images of 33 tokens, more than one 1024-row dispatch workgroup and several
-#: 128-row tiles per expert.
+#: 128-row tiles per expert; `aligned`: `reduced` with 16 images, 144 token rows: align4(M) = 144, align4(B) = 16 and B P = 128 are
+#: multiples of 16, the fast staging of every weight-gradient GEMM (28 / 100 / 260 rows in the other cases: none is).
 TOWER_CASES = {
     "reduced": mc.CASES["reduced"],
     "reduced_all": mc.CASES["reduced_all"],
     "reduced_wide": mc.CASES["reduced_wide"],
     "full": (dict(synth.VIT_B16, h_res=4, w_res=2, num_experts=4, top_k=2, moe_layers=2), (64, 32), 3, 5400, 0.02),
     "rows1320": (dict(_WIDE, num_experts=4, top_k=2, moe_layers=1), (128, 64), 40, 5500, 0.05),
+    "aligned": (dict(mc._RED, num_experts=4, top_k=2, moe_layers=2), (64, 32), 16, 5600, 0.05),
 }
 #: what a wrong sweep could compute instead.  Relative L2 from the right gradient on (gate.weight, tokens), float64 on the CPU
 #: (tests/test_moe_grad_cpu.py prints them); the case on which each variant is judged is the one where it is farthest:

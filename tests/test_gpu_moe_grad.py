@@ -311,7 +311,8 @@ def test_tower_training_forward(towers, name):
 def test_tower_gradients_against_float64(towers, name):
     """every master (block 0's gate among them), cv_emb and tokens within 2e-5 per tensor of float64 autograd of
     sum(f_last o d1) + sum(f o d2) + sum(f_proj o d3) + 0.01 l_aux; fp32 autograd on the host beside it; a second call gives the
-    same bits"""
+    same bits.  `aligned` (16 images, 144 token rows: every weight-gradient GEMM on the exact fp32 GEMM's fast staging), measured
+    on an MI355X: device worst 8.6e-7 (block 0's gate), fp32 autograd on the host 2.0e-6"""
     c, enc, imgs, cv = towers(name)
     want = gc.tower_grads(name)
     out = enc.backward(imgs, cv, *_seeds(c), want=_all_names(enc), aux_coef=gc.AUX_COEF)

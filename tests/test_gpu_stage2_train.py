@@ -354,6 +354,31 @@ def test_one_fused_step_against_float64_and_the_single_tensor_kernel(sie):
     assert np.array_equal(_bits(torch.cat(f_new[1:], 1)), _bits(fresh(img, cv)))
 
 
+def test_one_fused_step_on_uint8_pixels_has_the_bits_of_the_step_on_the_normalised_tensor():
+    """step() takes uint8 [B, H, W, 3] as the loader has it after Resize: the forward and the recomputed patch operands of the
+    conv1.weight gradient normalise the pixels in their first kernel.  The loss, every gradient buffer and every trained tensor
+    after the update carry the bits of a twin trainer stepped on the fp32 tensor ((u8 / 255) - 0.5) / 0.5 made with the same two
+    fp32 divisions on the host; and the step moved the parameters"""
+    s, enc, head, opt, tr, tensors, _ = _trainer(True, "Adam", "s2_u8")
+    _, _, _, _, twin, twin_tensors, _ = _trainer(True, "Adam", "s2_u8_twin")
+    img, target, idx = _batch(s, True)
+    rng = np.random.default_rng(23)
+    u8 = torch.from_numpy(rng.integers(0, 256, size=(img.shape[0], img.shape[2], img.shape[3], 3), dtype=np.uint8))
+    x = ((u8.permute(0, 3, 1, 2).float() / 255) - 0.5) / 0.5
+    before = {k: t.detach().clone() for k, t in tensors.items()}
+    st = tr.step(u8.cuda(), target, idx, validate=True)
+    want = twin.step(x.contiguous().cuda(), target, idx, validate=True)
+    assert bool(torch.isfinite(st.loss).all())
+    assert np.array_equal(_bits(st.loss), _bits(want.loss))
+    for k in tr.grads:
+        assert np.array_equal(_bits(tr.grads[k]), _bits(twin.grads[k])), k
+    assert bool(tr.grads["conv1.weight"].any())
+    for k in tensors:
+        assert np.array_equal(_bits(tensors[k]), _bits(twin_tensors[k])), k
+    for k in s2.trained_names(True):
+        assert not np.array_equal(_bits(tensors[k]), _bits(before[k])), k
+
+
 @pytest.mark.parametrize("algo", ["SGD", "Adam"])
 def test_ten_fused_steps_follow_the_float64_curve(algo):
     """ten steps with the SIE table: the loss before each update within 2e-5 (relative) of the float64 loop's; after ten steps of

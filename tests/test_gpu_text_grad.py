@@ -46,6 +46,36 @@ def test_attention_backward_against_float64(width, heads, tokens):
     assert fig <= tc.BOUND_SPLIT
 
 
+SAT_CASES = [(w, h, t, False) for w, h in tc.ATT_SHAPES for t in tg.SAT_TOKENS] + [(128, 2, tg.TIED_TOKENS, True)]
+
+
+@pytest.mark.parametrize("width,heads,tokens,tied", SAT_CASES)
+def test_attention_backward_on_saturated_slabs(width, heads, tokens, tied):
+    """slab (prompt 0, head 0) saturated on every row, row i's strongest key (37 i + 5) mod (i + 1): on both lane halves at 128
+    tokens (text_grad_cases.saturate; premises in test_clip_like_premises_cpu.py: the kernel's expressions in fp32 are within
+    1e-5, plain fp32 autograd is 1.4e-3 .. 0.56 away on that slab).  tied: slab (1, 0) holds exact copies of key 63 at 64 and
+    of key 0 at L - 1, and every fourth row (and the last) is pointed at one of them: two keys hold the maximum to the bit.
+    Finite; the slab-relative figure <= 2e-5 (its scale is per slab, so the saturated slab is judged on its own); a second call
+    gives the same bits; prompt 0 alone has the bits it has inside the batch.
+    Measured on an MI355X over the 11 cases: 1.3e-6 .. 5.0e-6 (largest (128, 2), L = 77), the tied case 1.7e-6; fp32 autograd on
+    the host 1.4e-3 .. 0.56"""
+    qkv, d_o, want = tg.saturated_case(width, heads, tokens, tied)
+    B = tc.ATT_BATCH
+    q, g = qkv.cuda(), d_o.cuda()
+    got = ops.text_attention_backward(q, g, B, tokens, heads).clone()
+    assert bool(torch.isfinite(got).all())
+    fig = tg.grad_figure(got, want, B, heads)
+    host = tg.attention_grad(qkv, d_o, B, heads, dtype=torch.float32)
+    on_slab = [tg.grad_figure(tg.slab(x, B, heads, 0, 0), tg.slab(want, B, heads, 0, 0), 1, 1) for x in (got, host)]
+    print("attention backward, saturated%s (%d, %d) L = %d: %.3e (slab (0, 0) %.3e); fp32 autograd on the host %.3e (slab (0, 0) %.3e)"
+          % (" and tied" if tied else "", width, heads, tokens, fig, on_slab[0], tg.grad_figure(host, want, B, heads), on_slab[1]))
+    assert fig <= tc.BOUND_SPLIT
+    again = ops.text_attention_backward(q, g, B, tokens, heads)
+    assert torch.equal(again.view(torch.int32), got.view(torch.int32))
+    alone = ops.text_attention_backward(q[:tokens].contiguous(), g[:tokens].contiguous(), 1, tokens, heads)
+    assert torch.equal(alone.view(torch.int32), got[:tokens].view(torch.int32))
+
+
 # ---- 2. poison, and the same bits twice ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("tokens", [17, 77])
 def test_attention_backward_writes_d_qkv_and_nothing_else(tokens):
@@ -79,16 +109,38 @@ def _ln_grad64(x, dy, gamma):
     return torch.autograd.grad(y, x64, grad_outputs=dy.double())[0]
 
 
-@pytest.mark.parametrize("width", [128, 512, 1024])
+def massive_rows(rows, width, seed):
+    """(x, gamma) of a trained CLIP tower's residual stream: N(0, 1) rows with channel 5 at +1900 and channel W / 2 + 3 at -1900
+    (in every third row only channel 5 is massive, at 2100), four gammas x30-100 and the massive channels' gamma 0.02"""
+    g = torch.Generator().manual_seed(seed)
+    c0, c1 = 5, width // 2 + 3
+    x = torch.randn(rows, width, generator=g)
+    x[:, c0] += 1900.0
+    x[:, c1] -= 1900.0
+    x[::3, c0] += 200.0
+    x[::3, c1] += 1900.0
+    gamma = 1.0 + 0.05 * torch.randn(width, generator=g)
+    big = [c for c in torch.randperm(width, generator=g).tolist() if c not in (c0, c1)][:4]
+    gamma[big] *= 30.0 + 70.0 * torch.rand(4, generator=g)
+    gamma[[c0, c1]] = 0.02
+    return x, gamma
+
+
+@pytest.mark.parametrize("width", [128, 512, 768, 1024])
 def test_layernorm_backward_against_float64(width):
-    """rows of tiny variance (far below eps: sigma is eps's), of ordinary and of large variance; the plain and the accumulate
-    form; relative L2 <= 2e-5 per group of rows"""
+    """rows of tiny variance (far below eps: sigma is eps's), of ordinary and of large variance, and rows with the massive
+    channels of a trained CLIP tower under gammas of x30-100 and 0.02 (massive_rows; the kernel's expressions in fp32 on the
+    host give 6e-8 .. 1e-7 there); the plain and the accumulate form; relative L2 <= 2e-5 per group of rows.
+    Measured on an MI355X on the massive rows: 6.2e-8 .. 9.5e-8 plain, 6.2e-8 .. 1.0e-7 accumulate"""
     g = torch.Generator().manual_seed(width)
     rows = 37   # not a multiple of the four rows of a workgroup
     groups = {"tiny": 0.5 + 1e-4 * torch.randn(rows, width, generator=g), "unit": torch.randn(rows, width, generator=g),
               "large": 100.0 + 1e3 * torch.randn(rows, width, generator=g)}
-    gamma = 1.0 + 0.05 * torch.randn(width, generator=g)
+    gamma_plain = 1.0 + 0.05 * torch.randn(width, generator=g)
+    x_massive, gamma_massive = massive_rows(rows, width, 1000 + width)
+    groups["massive"] = x_massive
     for name, x in groups.items():
+        gamma = gamma_massive if name == "massive" else gamma_plain
         dy = torch.randn(rows, width, generator=g)
         want = _ln_grad64(x, dy, gamma)
         got = ops.layernorm_backward(x.cuda(), dy.cuda(), gamma.cuda())

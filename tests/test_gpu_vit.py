@@ -351,31 +351,7 @@ def test_encoders_do_not_depend_on_stale_workspace(n):
 
 
 # ---- the split mode where real CLIP checkpoints will stress it (hard part 5) ---------------------
-def outlier_state_dict(cfg, seed=31):
-    """seeded ViT weights with the outlier structure of trained CLIP towers (reference model/clip/model.py:150-161 LayerNorm,
-    :260-281 block): ONE residual channel carried at about -2000 / +2000 through every block (a 'massive activation'
-    channel: written by ln_pre with gamma 100 on a channel that dominates the embedding), LayerNorm gammas with a few
-    channels x30-100, and FC1 units whose pre-activations sit at +-60."""
-    from mpreid import synth
-    sd = synth.vit_state_dict(cfg, seed=seed, std=0.02, ln_jitter=0.05)
-    rng = np.random.default_rng(seed)
-    w = cfg["width"]
-    c0, c1 = 5, w // 2 + 3
-    sd["positional_embedding"][:, c0] += 40.0          # dominates every token's embedding ...
-    sd["positional_embedding"][:, c1] -= 40.0
-    sd["ln_pre.weight"][c0] = 100.0                    # ... ln_pre turns it into ~ +-1900 in the residual stream
-    sd["ln_pre.weight"][c1] = 100.0
-    for i in range(cfg["layers"]):
-        b = f"transformer.resblocks.{i}"
-        for ln in ("ln_1", "ln_2"):
-            big = rng.choice(w, 4, replace=False)
-            big = big[(big != c0) & (big != c1)]
-            sd[f"{b}.{ln}.weight"][big] *= rng.uniform(30.0, 100.0, big.size).astype(np.float32)
-            sd[f"{b}.{ln}.weight"][[c0, c1]] = 0.02     # trained towers damp the massive channels inside the blocks
-        units = rng.choice(4 * w, 6, replace=False)
-        sd[f"{b}.mlp.c_fc.bias"][units[:3]] = 60.0
-        sd[f"{b}.mlp.c_fc.bias"][units[3:]] = -60.0
-    return sd
+from clip_like_cases import outlier_state_dict  # noqa: E402  (shared with the gradient tests)
 
 
 def test_split_mode_on_clip_like_outliers():

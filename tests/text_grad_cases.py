@@ -101,6 +101,67 @@ def attention_grad_case(width, heads, tokens, batch=tc.ATT_BATCH):
     return qkv, d_o, attention_grad(qkv, d_o, batch, heads)
 
 
+# ----------------------------------------------------------------------------------------------
+# saturated slabs of more than one 64-key block (both attention-gradient kernels; vit_grad_cases uses the same construction)
+# ----------------------------------------------------------------------------------------------
+SAT_SCORE = 18.0
+#: the minimum above two tokens, both sides of the 16-key tile and of the second lane half (keys 64 ..), CLIP's count, the limit
+SAT_TOKENS = [3, 17, 65, 77, 128]
+TIED_TOKENS = 128
+
+
+def strongest_keys(L, causal):
+    """the key row i of the saturated slab is pointed at: (37 i + 5) mod L unmasked, mod (i + 1) under the causal mask"""
+    i = torch.arange(L)
+    return (37 * i + 5) % ((i + 1) if causal else torch.full_like(i, L))
+
+
+def tied_targets(L, causal):
+    """{query row: key} of the tied slab: every fourth row is pointed at key 63 (whose copy is key 64) or at key 0 (whose copy
+    is key L - 1), in turn.  Under the causal mask a row sees both copies of key 63 from row 64 on, so earlier rows take key 0;
+    the last row is the only one that sees key L - 1, so it is pointed at key 0 too."""
+    out = {}
+    for n, i in enumerate(range(0, L, 4)):
+        want63 = L >= 65 and n % 2 == 0 and (not causal or i >= 64)
+        out[i] = 63 if want63 else 0
+    if causal:
+        out[L - 1] = 0
+    return out
+
+
+def saturate(qkv, batch, heads, causal, tied=False):
+    """In place on make_qkv's tensor.  Slab (image 0, head 0): q_i = k_j * 8 * SAT_SCORE / |k_j|^2 with j = strongest_keys: every
+    row's score of that key is SAT_SCORE, of any other a few units, so the row puts all but ~1e-6 of its probability on it, and
+    the strongest keys visit every 64-key block and the ragged tail.  tied: in slab (1, 0) key rows 63 and 64, and key rows 0 and
+    L - 1, are exact copies of each other and the rows of tied_targets are pointed at one of them: two keys hold the row's
+    maximum to the bit.  The other slabs stay ordinary."""
+    t = qkv.view(batch, -1, 3, heads, 64)
+    L = t.shape[1]
+    k = t[0, :, 1, 0][strongest_keys(L, causal)]
+    t[0, :, 0, 0] = k * (8.0 * SAT_SCORE / (k * k).sum(dim=1, keepdim=True))
+    if tied:
+        if L >= 65:
+            t[1, 64, 1, 0] = t[1, 63, 1, 0]
+        t[1, L - 1, 1, 0] = t[1, 0, 1, 0]
+        for i, j in tied_targets(L, causal).items():
+            kj = t[1, j, 1, 0]
+            t[1, i, 0, 0] = kj * (8.0 * SAT_SCORE / (kj * kj).sum())
+    return qkv
+
+
+def slab(x, batch, heads, b, h):
+    """the (image b, head h) slab of a [batch * L, 3 * width] gradient as a [L, 3 * 64] tensor (grad_figure(.., 1, 1) judges it)"""
+    return x.detach().cpu().view(batch, -1, 3, heads, 64)[b, :, :, h].reshape(-1, 3 * 64)
+
+
+@functools.lru_cache(maxsize=None)
+def saturated_case(width, heads, tokens, tied=False, batch=tc.ATT_BATCH):
+    """(qkv, d_o, float64 gradient) of a causal case whose slab (0, 0) is saturated (and whose slab (1, 0) is tied)"""
+    qkv = saturate(tc.make_qkv(width, heads, batch, tokens), batch, heads, True, tied)
+    d_o = make_d_o(width, batch, tokens)
+    return qkv, d_o, attention_grad(qkv, d_o, batch, heads)
+
+
 def make_grad_out(batch, out_dim, seed):
     rng = np.random.default_rng(seed)
     return rng.standard_normal((batch, out_dim)).astype(np.float32)

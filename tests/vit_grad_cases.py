@@ -57,6 +57,21 @@ def attention_grad_case(width, heads, tokens, batch=ATT_BATCH):
     return qkv, d_o, tg.attention_grad(qkv, d_o, batch, heads, all_keys(tokens))
 
 
+#: saturated slabs of more than one block (text_grad_cases.saturate, unmasked): the minimum above two tokens, one key past the
+#: first 64-key block, past the second, past the fourth, and the longest shipped geometry (a ragged tail of 58 keys)
+SAT_TOKENS = [3, 65, 129, 257, 442]
+TIED_TOKENS = 129
+
+
+@functools.lru_cache(maxsize=None)
+def saturated_case(width, heads, tokens, tied=False, batch=ATT_BATCH):
+    """(qkv, d_o, float64 gradient) of an unmasked case whose slab (0, 0) is saturated with the strongest keys spread over every
+    64-key block (and whose slab (1, 0) holds two exact copies of the strongest key in every fourth row)"""
+    qkv = tg.saturate(tc.make_qkv(width, heads, batch, tokens), batch, heads, False, tied)
+    d_o = tg.make_d_o(width, batch, tokens)
+    return qkv, d_o, tg.attention_grad(qkv, d_o, batch, heads, all_keys(tokens))
+
+
 # ----------------------------------------------------------------------------------------------
 # the tower
 # ----------------------------------------------------------------------------------------------
@@ -91,6 +106,8 @@ def tower(cfg, g, imgs, cv_emb=None, taps=None):
             x.retain_grad()
         taps["tokens"] = x
     x = F.layer_norm(x, (w,), g["ln_pre.weight"], g["ln_pre.bias"], 1e-5)
+    if taps is not None:   # what clip_like_cases' premises look at: ln_pre's output, every block's probabilities and FC1 pre-activations
+        taps["ln_pre"], taps["probs"], taps["fc1_pre"] = x.detach(), [], []
     L = x.shape[1]
     f_last = x[:, 0]
     for i in range(cfg["layers"]):
@@ -99,10 +116,14 @@ def tower(cfg, g, imgs, cv_emb=None, taps=None):
         h = F.layer_norm(x, (w,), g[b + ".ln_1.weight"], g[b + ".ln_1.bias"], 1e-5)
         qkv = h @ g[b + ".attn.in_proj_weight"].t() + g[b + ".attn.in_proj_bias"]
         q, k, v = (t.reshape(B, L, heads, 64).transpose(1, 2) for t in qkv.split(w, dim=2))
-        a = (torch.softmax((q @ k.transpose(2, 3)) * 0.125, dim=-1) @ v).transpose(1, 2).reshape(B, L, w)
+        pr = torch.softmax((q @ k.transpose(2, 3)) * 0.125, dim=-1)
+        a = (pr @ v).transpose(1, 2).reshape(B, L, w)
         x = x + a @ g[b + ".attn.out_proj.weight"].t() + g[b + ".attn.out_proj.bias"]
         h = F.layer_norm(x, (w,), g[b + ".ln_2.weight"], g[b + ".ln_2.bias"], 1e-5)
         h = h @ g[b + ".mlp.c_fc.weight"].t() + g[b + ".mlp.c_fc.bias"]
+        if taps is not None:
+            taps["probs"].append(pr.detach())
+            taps["fc1_pre"].append(h.detach())
         h = h * torch.sigmoid(1.702 * h)
         x = x + h @ g[b + ".mlp.c_proj.weight"].t() + g[b + ".mlp.c_proj.bias"]
     f = F.layer_norm(x[:, 0], (w,), g["ln_post.weight"], g["ln_post.bias"], 1e-5)
@@ -148,7 +169,12 @@ def make_seeds(name):
 def tower_grads(name, use=(True, True, True), with_cv=True, dtype=torch.float64):
     """{reference key name | "cv_emb" | "tokens": gradient} of sum(f_last o d_f_last) + sum(f o d_f) + sum(f_proj o d_f_proj)
     under torch autograd in `dtype` (seeds with use[i] False are left out), computed once and shared"""
-    cfg, _, sd, imgs, cv, _ = tower_case(name)
+    return tower_grads_on(name, tower_case(name)[3], use, with_cv, dtype)
+
+
+def tower_grads_on(name, imgs, use=(True, True, True), with_cv=True, dtype=torch.float64):
+    """tower_grads of a case on other images of its size (a materialised view, host-normalised uint8 pixels); not cached"""
+    cfg, _, sd, _, cv, _ = tower_case(name)
     g = {k: v.clone().requires_grad_(True) for k, v in weights(sd, dtype).items()}
     cv_t = tc._t64(cv).to(dtype).requires_grad_(True) if with_cv else None
     taps = {}
@@ -187,6 +213,31 @@ def kernel_inputs(rows, cols):
     dy = rng.standard_normal((rows, cols)).astype(np.float32)
     x = (rng.standard_normal((rows, cols)) * 3.0 + 0.5).astype(np.float32)
     return dy, x
+
+
+MASSIVE_ROWS = 1033
+MASSIVE_COLS = [128, 768, 3072]
+
+
+def massive_inputs(rows, cols):
+    """(dy, x) with the residual stream's massive channels of a trained CLIP tower: x ~ N(0, 1) with channel 5 at +1900 and
+    channel cols / 2 + 3 at -1900; in every third row only channel 5 is massive, at 2100"""
+    rng = np.random.default_rng(rows * 10007 + cols + 1)
+    dy = rng.standard_normal((rows, cols)).astype(np.float32)
+    x = rng.standard_normal((rows, cols)).astype(np.float32)
+    c0, c1 = 5, cols // 2 + 3
+    x[:, c0] += np.float32(1900.0)
+    x[:, c1] -= np.float32(1900.0)
+    x[::3, c0] += np.float32(200.0)
+    x[::3, c1] += np.float32(1900.0)
+    return dy, x
+
+
+def colsum_f64(dy, x):
+    """(sum_m dy, sum_m dy * xhat) in float64, xhat of LayerNorm (biased variance, eps 1e-5)"""
+    dy64, x64 = dy.astype(np.float64), x.astype(np.float64)
+    xhat = (x64 - x64.mean(1, keepdims=True)) / np.sqrt(x64.var(1, keepdims=True) + 1e-5)
+    return dy64.sum(0), (dy64 * xhat).sum(0)
 
 
 def transpose_pad_ref(src, rows_pad):
