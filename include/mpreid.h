@@ -746,6 +746,34 @@ int mpreid_text_attention_backward(const float *qkv_dev, const float *d_o_dev, i
  * dx_dev must not overlap the inputs. */
 int mpreid_layernorm_backward_f32(const float *x_dev, const float *dy_dev, const float *gamma_dev, int64_t rows, int width,
                                   int accumulate, float *dx_dev, mpreid_stream_t stream);
+/* Three row kernels of every tower alone, for unit tests and tools; each goes through the launcher the towers call.
+ * Errors, all before anything is launched: a NULL pointer, a misaligned one, form outside 0..2, n % 4 != 0, a negative
+ * count: MPREID_ERR_ARG; a width that is not a multiple of 128 in 128..1024: MPREID_ERR_UNSUPPORTED.  rows, batch or n
+ * of 0 is MPREID_OK and launches nothing.
+ *
+ * mpreid_layernorm_f32: LayerNorm over rows of `width` fp32 values (biased variance, eps 1e-5, fp32 statistics), in the
+ * three output forms of the towers.  form 0: fp32 [rows][width], out_dev may be x_dev (ln_pre runs in place); form 1: fp16
+ * [rows][width]; form 2: the fp16 pair [rows][hi(width) | lo(width)] of the split precision.  All four pointers 16-byte
+ * aligned.  Every element of the output is written and no other byte. */
+int mpreid_layernorm_f32(const float *x_dev, int64_t rows, int width, const float *gamma_dev, const float *beta_dev,
+                         int form /* 0 fp32 [rows][W] (out_dev may be x_dev), 1 fp16 [rows][W], 2 fp16 pairs [rows][2W] */,
+                         void *out_dev, mpreid_stream_t stream);
+/* The head of every tower: LayerNorm of ONE row per item, that row @ proj, optional eval-BatchNorm necks.  Item b is at
+ * x_dev + b * item_stride floats; its row is row 0 (row_of_dev NULL: the CLS row) or row row_of_dev[b] clamped into
+ * [0, tokens - 1]; rows are `width` wide.  y_dev [batch][width] receives the normalised rows (before any neck);
+ * out_dev[b][out_col + o] = sum_k y[b][k] * proj_dev[k][o] (proj_dev [width][out_dim]), through y * bnp_scale[o] +
+ * bnp_shift[o] when that neck is given; with ln_to_out != 0 out_dev[b][0 : width] = y[b], through y * bn_scale[k] +
+ * bn_shift[k] when that neck is given.  Rows of out_dev are out_stride floats apart.  A neck is both of its pointers or
+ * neither.  x_dev 16-byte aligned, everything else 4.  out_stride >= out_col + out_dim, and out_col >= width with
+ * ln_to_out.  No element of out_dev outside the columns named is written. */
+int mpreid_tower_head_f32(const float *x_dev, int64_t item_stride, const int32_t *row_of_dev /* NULL: row 0 */, int tokens,
+                          int batch, int width, int out_dim, const float *ln_g_dev, const float *ln_b_dev, const float *proj_dev,
+                          const float *bn_scale_dev, const float *bn_shift_dev, const float *bnp_scale_dev,
+                          const float *bnp_shift_dev, float *y_dev, float *out_dev, int out_stride, int out_col, int ln_to_out,
+                          mpreid_stream_t stream);
+/* QuickGELU's backward, in place: d[i] *= s + 1.702 u[i] s (1 - s), s = sigmoid(1.702 u[i]); n a multiple of 4, both
+ * pointers 16-byte aligned. */
+int mpreid_quickgelu_backward_f32(const float *u_dev, float *d_dev /* in place */, int64_t n, mpreid_stream_t stream);
 
 /* ---- The image tower's gradient (stage 2): training forward, attention gradient, the sweep and the parameter gradients ----
  * The three features stage 2 differentiates, the one backward kernel the image tower cannot borrow from the text tower, and

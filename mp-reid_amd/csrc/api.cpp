@@ -83,7 +83,7 @@ int mpreid_device_cus(int *cus) {
     return MPREID_OK;
 }
 
-extern "C" int mpreid_version(void) { return 101; } /* 0.1.1: mpreid/_lib.py (VERSION) loads exactly this one */
+extern "C" int mpreid_version(void) { return 102; } /* 0.1.2: mpreid/_lib.py (VERSION) loads exactly this one */
 
 // 1 for a library compiled with -DMPREID_ABLATION (timing-ablation switches honoured: WRONG RESULTS by design), else 0
 extern "C" int mpreid_is_ablation_build(void) {

@@ -299,6 +299,14 @@ extern "C" int mpreid_layernorm_backward_f32(const float *x, const float *dy, co
     return launch_layernorm_backward(x, dy, gamma, rows, width, accumulate != 0, dx, (hipStream_t)stream);
 }
 
+extern "C" int mpreid_quickgelu_backward_f32(const float *u, float *d, int64_t n, mpreid_stream_t stream) {
+    ARG_CHECK(u && d && n >= 0 && n % 4 == 0);
+    ARG_CHECK((((uintptr_t)u | (uintptr_t)d) & 15) == 0);
+    ARG_CHECK(n < (int64_t)1 << 40);
+    if (n == 0) return MPREID_OK;
+    return launch_quickgelu_backward(u, d, n / 4, (hipStream_t)stream);
+}
+
 extern "C" int mpreid_text_backward(const mpreid_text_cfg *cfg, const mpreid_text_weights *w, const mpreid_text_weights_t *wt,
                                     const float *prompts, const int32_t *eot, const float *grad_out, int B, float *grad_prompts,
                                     void *ws, size_t ws_bytes, mpreid_stream_t stream_) {

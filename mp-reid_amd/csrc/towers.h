@@ -16,9 +16,16 @@ struct WsCursor {
 // What every tower's kernels ask of (width, heads): 64-wide heads (the attention kernels), a width that is a multiple of
 // 128 up to 1024 (LayerNorm, the GEMM tiles).  Each caller words its own error.
 enum { SHAPE_OK = 0, SHAPE_HEAD_DIM, SHAPE_WIDTH };
+static inline bool row_width_ok(int width) { return width >= 128 && width % 128 == 0 && width <= 1024; }
 static inline int check_width_heads(int width, int heads) {
     if (heads <= 0 || width != heads * 64) return SHAPE_HEAD_DIM;
-    return (width % 128 != 0 || width > 1024) ? SHAPE_WIDTH : SHAPE_OK;
+    return row_width_ok(width) ? SHAPE_OK : SHAPE_WIDTH;
+}
+// the width rule alone, for the row kernels' own entry points: MPREID_ERR_UNSUPPORTED with the error text set
+static inline int check_row_width(const char *who, int width) {
+    if (row_width_ok(width)) return MPREID_OK;
+    mpreid_set_error("%s: width %d is not a multiple of 128 in 128..1024", who, width);
+    return MPREID_ERR_UNSUPPORTED;
 }
 
 // the workspace of mpreid_text_forward (byte offsets; every region 256-byte aligned)

@@ -797,6 +797,43 @@ int vit_layernorm_f32(const float *x, int64_t rows, int W, const float *g, const
     return MPREID_OK;
 }
 
+// The forward LayerNorm and the head alone, for unit tests and tools (include/mpreid.h): the checks, then the launchers the
+// towers call (vit_layernorm_f32: the instantiation ln_pre runs in place; block_layernorm: a block's GEMM operand)
+extern "C" int mpreid_layernorm_f32(const float *x, int64_t rows, int width, const float *gamma, const float *beta, int form,
+                                    void *out, mpreid_stream_t stream) {
+    ARG_CHECK(x && gamma && beta && out && rows >= 0);
+    ARG_CHECK(form >= 0 && form <= 2);
+    const int rc = check_row_width("mpreid_layernorm_f32", width);
+    if (rc) return rc;
+    ARG_CHECK((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out) & 15) == 0);
+    ARG_CHECK(rows <= ((int64_t)1 << 31) - 256);   // block_layernorm's row count is an int
+    if (rows == 0) return MPREID_OK;
+    if (form == 0) return vit_layernorm_f32(x, rows, width, gamma, beta, (float *)out, (hipStream_t)stream);
+    const bool split = form == 2;
+    const BlockCtx ctx{(hipStream_t)stream, split, split ? 2 : 1, width, width / 64, 1, (int)rows};
+    block_layernorm(ctx, x, (int)rows, gamma, beta, (_Float16 *)out);
+    LAUNCH_CHECK();
+    return MPREID_OK;
+}
+
+extern "C" int mpreid_tower_head_f32(const float *x, int64_t item_stride, const int32_t *row_of, int tokens, int batch, int width,
+                                     int out_dim, const float *ln_g, const float *ln_b, const float *proj, const float *bn_scale,
+                                     const float *bn_shift, const float *bnp_scale, const float *bnp_shift, float *y, float *out,
+                                     int out_stride, int out_col, int ln_to_out, mpreid_stream_t stream) {
+    ARG_CHECK(x && ln_g && ln_b && proj && y && out);
+    ARG_CHECK((bn_scale != nullptr) == (bn_shift != nullptr) && (bnp_scale != nullptr) == (bnp_shift != nullptr));
+    ARG_CHECK(batch >= 0 && batch <= 1 << 24 && tokens >= 1 && item_stride >= 0 && out_dim >= 1 && out_dim <= 1 << 20);
+    const int rc = check_row_width("mpreid_tower_head_f32", width);
+    if (rc) return rc;
+    ARG_CHECK(out_col >= 0 && (int64_t)out_stride >= (int64_t)out_col + out_dim && (!ln_to_out || out_col >= width));
+    ARG_CHECK(((uintptr_t)x & 15) == 0);
+    ARG_CHECK((((uintptr_t)row_of | (uintptr_t)ln_g | (uintptr_t)ln_b | (uintptr_t)proj | (uintptr_t)bn_scale | (uintptr_t)bn_shift |
+                (uintptr_t)bnp_scale | (uintptr_t)bnp_shift | (uintptr_t)y | (uintptr_t)out) & 3) == 0);
+    if (batch == 0) return MPREID_OK;
+    return tower_head(x, item_stride, row_of, tokens, batch, width, out_dim, ln_g, ln_b, proj, bn_scale, bn_shift, bnp_scale,
+                      bnp_shift, y, out, out_stride, out_col, ln_to_out != 0, (hipStream_t)stream);
+}
+
 // the split mode's block and its parts for any tower (towers.h)
 static BlockCtx split_ctx(const BlockShape &s, hipStream_t stream) { return BlockCtx{stream, true, 2, s.W, s.heads, s.B, s.L}; }
 static AttnKind attn_kind(const BlockShape &s) { return s.causal ? ATTN_CAUSAL : ATTN_ALL_ROWS; }

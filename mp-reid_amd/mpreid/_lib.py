@@ -211,7 +211,7 @@ GEMM_EPILOGUE_NAMES = {0: "f32", 1: "qkv_bias_f16", 2: "bias_residual", 3: "fc_b
 VIT_F16, VIT_SPLIT = 0, 1
 
 #: mpreid_version() of the library this binding was written for: signatures change under unchanged names, so no other loads
-VERSION = 101
+VERSION = 102
 
 vp, i64, i32, f32, f64, sz, P = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_size_t, C.POINTER
 _DIST = [vp, vp, i64, i64, i32, vp, i64, i32, vp, sz, vp]
@@ -291,6 +291,12 @@ PROTOTYPES = {
     "mpreid_text_backward": (i32, [P(TextCfg), P(TextWeights), P(TextWeightsT), vp, vp, vp, i32, vp, vp, sz, vp]),
     "mpreid_text_attention_backward": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "mpreid_layernorm_backward_f32": (i32, [vp, vp, vp, i64, i32, i32, vp, vp]),
+    # three row kernels alone: (x, rows, width, gamma, beta, form, out, stream); (x, item_stride, row_of, tokens, batch, width,
+    # out_dim, ln_g, ln_b, proj, bn_scale, bn_shift, bnp_scale, bnp_shift, y, out, out_stride, out_col, ln_to_out, stream);
+    # (u, d, n, stream)
+    "mpreid_layernorm_f32": (i32, [vp, i64, i32, vp, vp, i32, vp, vp]),
+    "mpreid_tower_head_f32": (i32, [vp, i64, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "mpreid_quickgelu_backward_f32": (i32, [vp, vp, i64, vp]),
     # the image tower's gradient: the training forward (cfg, weights, image batch, B, cv_emb, f_last, f, f_proj, workspace,
     # workspace bytes, stream) and the unmasked attention gradient (qkv, d_o, B, tokens, width, heads, d_qkv, workspace, bytes, stream)
     "mpreid_vit_forward_train": (i32, [P(VitCfg), P(VitWeights), P(ImageIn), i32, vp, vp, vp, vp, vp, sz, vp]),

@@ -1641,6 +1641,74 @@ def layernorm_backward(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, o
     return out
 
 
+def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, form: int = 0,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the towers' forward LayerNorm alone (mpreid_layernorm_f32).  x: fp32 [rows, width] on the device, used as it is (it may
+    be a view into a larger buffer).  form 0 -> fp32 [rows, width], and `out` may be x itself (ln_pre's in-place call); form 1
+    -> fp16 [rows, width]; form 2 -> the fp16 pair [rows, 2 * width] = [hi | lo].  `out` is allocated when not passed."""
+    dev = _lib.require_gpu()
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()
+    gamma, beta = _dev_f32(gamma, dev), _dev_f32(beta, dev)
+    rows, width = x.shape
+    assert tuple(gamma.shape) == (width,) and tuple(beta.shape) == (width,)
+    shape, dtype = ((rows, width), torch.float32) if form == 0 else ((rows, width * (2 if form == 2 else 1)), torch.float16)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=dev)
+    assert out.is_cuda and out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == shape
+    _lib.check(_lib.load().mpreid_layernorm_f32(_ptr(x), rows, width, _ptr(gamma), _ptr(beta), int(form), _ptr(out),
+                                                _lib.stream_ptr()), "mpreid_layernorm_f32")
+    return out
+
+
+def tower_head(x: torch.Tensor, item_stride: int, row_of: Optional[torch.Tensor], tokens: int, batch: int, ln_g: torch.Tensor,
+               ln_b: torch.Tensor, proj: torch.Tensor, bn=None, bnp=None, ln_to_out: bool = True,
+               out: Optional[torch.Tensor] = None, out_col: Optional[int] = None):
+    """the head of every tower alone (mpreid_tower_head_f32) -> (y [batch, width], out).  x: fp32 on the device, item b at
+    b * item_stride floats; its row is row 0, or row row_of[b] (int32, clamped into the item's `tokens` rows by the kernel).
+    proj: [width, out_dim]; bn / bnp: optional (scale, shift) of the eval-BatchNorm necks on the two halves.  ln_to_out: out is
+    [batch, width + out_dim] = [ln | ln @ proj] (the image towers), else [batch, out_dim] (the text tower); a passed `out` may
+    be a view whose rows are out.stride(0) apart, with the projection at column out_col."""
+    dev = _lib.require_gpu()
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+    ln_g, ln_b, proj = _dev_f32(ln_g, dev), _dev_f32(ln_b, dev), _dev_f32(proj, dev)
+    width, out_dim = proj.shape
+    assert tuple(ln_g.shape) == (width,) and tuple(ln_b.shape) == (width,)
+    reach = (tokens if row_of is not None else 1) * width
+    assert batch == 0 or (batch - 1) * int(item_stride) + reach <= x.numel(), "x is too short for the rows the head may read"
+    if row_of is not None:
+        row_of = row_of.to(device=dev, dtype=torch.int32).contiguous()
+        assert tuple(row_of.shape) == (batch,)
+    necks = []
+    for neck, n in ((bn, width), (bnp, out_dim)):
+        pair = [None, None] if neck is None else [_dev_f32(t, dev) for t in neck]
+        assert all(t is None or tuple(t.shape) == (n,) for t in pair)
+        necks += pair
+    if out_col is None:
+        out_col = width if ln_to_out else 0
+    if out is None:
+        out = torch.empty((batch, out_col + out_dim), dtype=torch.float32, device=dev)
+    assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == batch
+    assert out.shape[1] >= out_col + out_dim and (batch == 0 or out.stride(1) == 1)
+    y = torch.empty((batch, width), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().mpreid_tower_head_f32(_ptr(x), int(item_stride), _ptr(row_of), int(tokens), int(batch), width, out_dim,
+                                                 _ptr(ln_g), _ptr(ln_b), _ptr(proj), *[_ptr(t) for t in necks], _ptr(y), _ptr(out),
+                                                 int(out.stride(0)) if batch else out_col + out_dim, int(out_col), int(ln_to_out),
+                                                 _lib.stream_ptr()), "mpreid_tower_head_f32")
+    return y, out
+
+
+def quickgelu_backward(u: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
+    """QuickGELU's backward in place (mpreid_quickgelu_backward_f32): d *= s + 1.702 u s (1 - s), s = sigmoid(1.702 u); u, d fp32
+    on the device with the same number of elements, a multiple of 4; d is returned."""
+    _lib.require_gpu()
+    for t in (u, d):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    assert u.numel() == d.numel()
+    _lib.check(_lib.load().mpreid_quickgelu_backward_f32(_ptr(u), _ptr(d), u.numel(), _lib.stream_ptr()),
+               "mpreid_quickgelu_backward_f32")
+    return d
+
+
 def check_eot(eot, batch: int, tokens: int) -> np.ndarray:
     """the read-out rows of a prompt batch as int32 [batch], validated on the host (the library does not look at them):
     integers with 0 <= eot < tokens, else ValueError"""

@@ -190,7 +190,7 @@ def test_library_of_another_version_is_refused(tmp_path):
     load() refuses a library that reports another one, before it declares anything"""
     import subprocess
     import sys
-    assert _lib.load().mpreid_version() == _lib.VERSION == 101
+    assert _lib.load().mpreid_version() == _lib.VERSION == 102
     (tmp_path / "old.c").write_text("int mpreid_is_ablation_build(void) { return 0; }\nint mpreid_version(void) { return 100; }\n")
     old = tmp_path / "libfake_v100.so"
     subprocess.run(["gcc", "-shared", "-fPIC", "-o", str(old), str(tmp_path / "old.c")], check=True)

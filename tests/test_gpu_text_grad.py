@@ -10,6 +10,7 @@ import torch
 
 import text_cases as tc
 import text_grad_cases as tg
+from row_kernel_cases import massive_rows
 from mpreid import _lib, ops, synth
 
 pytestmark = pytest.mark.gpu
@@ -107,23 +108,6 @@ def _ln_grad64(x, dy, gamma):
     x64 = x.double().requires_grad_(True)
     y = tc._ln64(x64, gamma.double(), torch.zeros_like(gamma).double())
     return torch.autograd.grad(y, x64, grad_outputs=dy.double())[0]
-
-
-def massive_rows(rows, width, seed):
-    """(x, gamma) of a trained CLIP tower's residual stream: N(0, 1) rows with channel 5 at +1900 and channel W / 2 + 3 at -1900
-    (in every third row only channel 5 is massive, at 2100), four gammas x30-100 and the massive channels' gamma 0.02"""
-    g = torch.Generator().manual_seed(seed)
-    c0, c1 = 5, width // 2 + 3
-    x = torch.randn(rows, width, generator=g)
-    x[:, c0] += 1900.0
-    x[:, c1] -= 1900.0
-    x[::3, c0] += 200.0
-    x[::3, c1] += 1900.0
-    gamma = 1.0 + 0.05 * torch.randn(width, generator=g)
-    big = [c for c in torch.randperm(width, generator=g).tolist() if c not in (c0, c1)][:4]
-    gamma[big] *= 30.0 + 70.0 * torch.rand(4, generator=g)
-    gamma[[c0, c1]] = 0.02
-    return x, gamma
 
 
 @pytest.mark.parametrize("width", [128, 512, 768, 1024])

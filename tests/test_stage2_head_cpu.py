@@ -216,7 +216,7 @@ def test_the_new_symbols_are_declared_and_exported():
     for name in ("mpreid_xent_rows_f32", "mpreid_triplet_workspace_bytes", "mpreid_triplet_hard_f32", "mpreid_bn1d_train_forward_f32",
                  "mpreid_bn1d_train_backward_f32", "mpreid_matmul_f32", "mpreid_stage2_total_f32"):
         assert name in _lib.PROTOTYPES and hasattr(L, name)
-    assert _lib.VERSION == 101
+    assert _lib.VERSION == 102
 
 
 def test_argument_errors_are_found_before_anything_is_launched():
