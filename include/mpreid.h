@@ -1067,6 +1067,40 @@ size_t mpreid_resize_workspace_bytes(int batch, int max_in_h, int out_w);
 int mpreid_resize_bilinear_u8(const uint8_t *src_dev, const int64_t *offsets_dev, const int32_t *hw_dev, int batch,
                               int max_in_h, int out_h, int out_w, uint8_t *dst_dev, void *ws_dev, size_t ws_bytes,
                               mpreid_stream_t stream);
+/* The same resample with a filter argument: MPREID_RESIZE_BILINEAR is mpreid_resize_bilinear_u8 bit for bit;
+ * MPREID_RESIZE_BICUBIC is T.Resize(cfg.INPUT.SIZE_TRAIN, interpolation=3) of train_transforms
+ * (datasets/make_dataloader_uniprompt.py:54), bit-exact with PIL.Image.resize((out_w, out_h), BICUBIC): bicubic_filter with
+ * a = -0.5, support 2 x filterscale, a negative coefficient rounded as (int)(-0.5 + w * 2^22), overshoot clamped to 0 .. 255.
+ * Any other filter is MPREID_ERR_ARG; the workspace is the one of mpreid_resize_workspace_bytes. */
+#define MPREID_RESIZE_BILINEAR 0
+#define MPREID_RESIZE_BICUBIC 1
+int mpreid_resize_u8(const uint8_t *src_dev, const int64_t *offsets_dev, const int32_t *hw_dev, int batch, int max_in_h,
+                     int out_h, int out_w, int filter, uint8_t *dst_dev, void *ws_dev, size_t ws_bytes, mpreid_stream_t stream);
+
+/* ---- The random part of train_transforms (datasets/make_dataloader_uniprompt.py:55-60) on a batch that is already resized:
+ * RandomHorizontalFlip, Pad(pad), RandomCrop(H x W), ToTensor, Normalize and timm's RandomErasing(mode='pixel', max_count=1)
+ * in ONE kernel.  Every random decision is taken on the host and arrives in params (HOST, int32 [batch][8]):
+ *   {flip, crop_top, crop_left, erase_top, erase_left, erase_h, erase_w, 0}        erase_h == 0: no erasing
+ * The value of out[b][c][y][x]:
+ *   (y, x) in the erase box   a standard normal: Philox4x32-10 with key (seed lo, seed hi) and counter (q lo, q hi,
+ *                             sample_id[b] lo, sample_id[b] hi), e = (c * erase_h + (y - erase_top)) * erase_w + (x - erase_left)
+ *                             the element's index in the (3, erase_h, erase_w) box, q = e >> 2, output word e & 3.  Words 0/1 and
+ *                             2/3 are Box-Muller pairs: u1 = ((w_a >> 8) + 1) * 2^-24, u2 = (w_b >> 8) * 2^-24, the even word
+ *                             takes sqrt(-2 ln u1) * cos(2 pi u2), the odd word the sine.  The noise depends on (seed, sample_id,
+ *                             box) only, not on the batch or the position in it.  (timm fills the box from torch's CPU generator:
+ *                             these are i.i.d. N(0, 1) values, not those bits.)
+ *   otherwise                 sy = y + crop_top - pad, sx = x + crop_left - pad; outside the image the padded pixel, uint8 0;
+ *                             inside img[b][sy][flip ? W - 1 - sx : sx][c]; then ((v / 255) - mean[c]) / std[c] in fp32 with two
+ *                             correctly rounded divisions, the rule of mpreid_image_in's uint8 input.
+ * img_hwc_dev uint8 [batch][H][W][3], out_dev fp32 [batch][3][H][W]; sample_id, mean[3] and std[3] are HOST arrays.  Every row
+ * is checked before the first launch -- flip in {0, 1}; 0 <= crop_top, crop_left <= 2 pad; erase_h in [0, H), erase_w in
+ * [0, W), both zero or neither, the box inside the image; the last field 0 -- and a violation is MPREID_ERR_ARG with a message
+ * that names the image and the field; nothing is launched then.  The table travels by value in the kernel arguments,
+ * MPREID_AUG_IMAGES_PER_LAUNCH images per launch (no upload, no workspace); stream-ordered, no host synchronisation. */
+#define MPREID_AUG_IMAGES_PER_LAUNCH 64
+int mpreid_train_augment_f32(const uint8_t *img_hwc_dev, int batch, int H, int W, int pad, const int32_t *params,
+                             const int64_t *sample_id, uint64_t seed, const float *mean, const float *std, float *out_dev,
+                             mpreid_stream_t stream);
 
 /* ---- CLIP "RN50" image encoder (MODEL.NAME == 'RN50': model/clip/model.py:10-148 ModifiedResNet, Bottleneck,
  * AttentionPool2d) + the RN50 eval branch of build_transformer.forward (model/make_model.py:82-86, 102-115):

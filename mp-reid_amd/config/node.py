@@ -113,12 +113,18 @@ def make_defaults():
                   # and unused at eval
                   "MOE": {"ENABLED": False, "NUM_EXPERTS": 0, "TOP_K": 0, "MOE_LAYERS": 0, "DROPOUT": 0.0}},
         "INPUT": {"SIZE_TRAIN": [256, 128], "SIZE_TEST": [256, 128], "PIXEL_MEAN": [0.5, 0.5, 0.5],
-                  "PIXEL_STD": [0.5, 0.5, 0.5]},
+                  "PIXEL_STD": [0.5, 0.5, 0.5],
+                  # train_transforms (reference config/defaults.py:83-91): the probability of the horizontal flip, the zero
+                  # padding in front of the random crop, the probability of random erasing
+                  "PROB": 0.5, "PADDING": 10, "RE_PROB": 0.5},
         "DATASETS": {"NAMES": "synthetic", "ROOT_DIR": "", "EXP_SETTING": "", "SYNTH_QUERY": 3368,
                      "SYNTH_GALLERY": 15913, "SYNTH_IDS": 751, "SYNTH_SEED": 1234,
                      # SYNTH_RAW: the loader hands over DECODED uint8 images of ragged sizes (what PIL gives before
                      # val_transforms) and Resize + ToTensor + Normalize run on the GPU
                      "SYNTH_RAW": False,
+                     # SYNTH_TRAIN > 0: that many synthetic TRAINING images of SYNTH_IDS identities; make_dataloader then
+                     # returns the two training loaders (0: None, None -- evaluation only)
+                     "SYNTH_TRAIN": 0,
                      # PROTOCOL 'vehicleid' (not a reference key; the reference branches on NAMES == 'VehicleID', test.py:46):
                      # TEST.TRIALS trials over ONE encoded pool, in each of them one random image per identity is the
                      # gallery and all the others are queries (datasets/make_dataloader.py:vehicleid_trial_splits, drawn

@@ -15,11 +15,17 @@
 // from the descriptor (the fp32-mode kernels).
 enum ImageSrc { IMAGE_SRC_F32, IMAGE_SRC_U8, IMAGE_SRC_ANY };
 
+// ToTensor (x / 255) then Normalize ((x - mean) / std) of one uint8 value: fp32, two correctly rounded divisions.  THE rounding
+// rule of uint8 input, shared by the encoders' pixel fetch below and the training augmentation kernel (train_aug.hip).  A macro,
+// not a function: the encoders' first kernels keep the device code they had when the expression stood in image_px_raw itself
+// (tools/device_code_diff.py; an inline function moved the stems' instruction schedule).
+#define IMAGE_U8_NORM(v, mean, std) __fdiv_rn(__fdiv_rn((float)(v), 255.0f) - (mean), (std))
+
 // the pixel (b, c, y, x) of the batch, before any view
 template <ImageSrc SRC = IMAGE_SRC_ANY>
 __device__ __forceinline__ float image_px_raw(const mpreid_image_in &in, int b, int c, int y, int x, int H, int W) {
     if (SRC == IMAGE_SRC_U8 || (SRC == IMAGE_SRC_ANY && in.u8_hwc_dev))
-        return __fdiv_rn(__fdiv_rn((float)in.u8_hwc_dev[(((int64_t)b * H + y) * W + x) * 3 + c], 255.0f) - in.mean[c], in.std[c]);
+        return IMAGE_U8_NORM(in.u8_hwc_dev[(((int64_t)b * H + y) * W + x) * 3 + c], in.mean[c], in.std[c]);
     return in.f32_dev[(((int64_t)b * 3 + c) * H + y) * W + x];
 }
 

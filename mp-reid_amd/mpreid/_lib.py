@@ -85,6 +85,8 @@ TRIPLET_MAX_BATCH = 1024  # MPREID_TRIPLET_MAX_BATCH
 
 OPTIM_SGD, OPTIM_ADAM, OPTIM_ADAMW = 0, 1, 2   # MPREID_OPTIM_*
 OPTIM_MAX_CLASSES, OPTIM_CHUNK, OPTIM_TENSORS_PER_LAUNCH = 8, 4096, 64
+RESIZE_BILINEAR, RESIZE_BICUBIC = 0, 1   # MPREID_RESIZE_*
+AUG_IMAGES_PER_LAUNCH = 64               # MPREID_AUG_IMAGES_PER_LAUNCH
 
 
 class OptimEntry(C.Structure):
@@ -340,6 +342,10 @@ PROTOTYPES = {
     "mpreid_tta_mean_f32": (i32, [vp, i32, i64, i32, i32, vp, vp]),
     "mpreid_resize_workspace_bytes": (sz, [i32, i32, i32]),
     "mpreid_resize_bilinear_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
+    # (src, offsets, hw, batch, max_in_h, out_h, out_w, filter, dst, workspace, bytes, stream); the training augmentation
+    # (img_hwc, batch, H, W, pad, params HOST int32 [B][8], sample_id HOST int64 [B], seed, mean HOST [3], std HOST [3], out, stream)
+    "mpreid_resize_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
+    "mpreid_train_augment_f32": (i32, [vp, i32, i32, i32, i32, vp, vp, C.c_uint64, vp, vp, vp, vp]),
     "mpreid_rn50_workspace_bytes": (sz, [P(Rn50Cfg), i32]),
     "mpreid_rn50_forward": (i32, [P(Rn50Cfg), P(Rn50Weights), P(ImageIn), i32, vp, vp, sz, vp]),
     "mpreid_rn50_workspace_bytes_f32": (sz, [P(Rn50Cfg), i32]),

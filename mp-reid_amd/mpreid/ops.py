@@ -598,16 +598,39 @@ class PackedRawImages:
         return self.count
 
 
-def resize_packed_u8(packed: PackedRawImages, out_hw) -> torch.Tensor:
-    """the two resize kernels on images that are already packed in device memory (no host work, no copy)"""
+RESIZE_FILTERS = {"bilinear": _lib.RESIZE_BILINEAR, "bicubic": _lib.RESIZE_BICUBIC}
+
+
+def resize_packed_u8(packed: PackedRawImages, out_hw, filter: Optional[str] = None) -> torch.Tensor:
+    """the two resize kernels on images that are already packed in device memory (no host work, no copy); filter None is the
+    bilinear entry point mpreid_resize_bilinear_u8, a name of RESIZE_FILTERS goes through mpreid_resize_u8"""
     dev = _lib.require_gpu()
     L = _lib.load()
     B, oh, ow = packed.count, int(out_hw[0]), int(out_hw[1])
     dst = torch.empty((B, oh, ow, 3), dtype=torch.uint8, device=dev)
     ws = _workspace("resize", L.mpreid_resize_workspace_bytes(B, packed.max_h, ow), dev)
-    _lib.check(L.mpreid_resize_bilinear_u8(_ptr(packed.data), _ptr(packed.offsets), _ptr(packed.hw), B, packed.max_h, oh, ow,
-                                           _ptr(dst), _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_resize_bilinear_u8")
+    if filter is None:
+        _lib.check(L.mpreid_resize_bilinear_u8(_ptr(packed.data), _ptr(packed.offsets), _ptr(packed.hw), B, packed.max_h, oh, ow,
+                                               _ptr(dst), _ptr(ws), ws.numel(), _lib.stream_ptr()), "mpreid_resize_bilinear_u8")
+    else:
+        if filter not in RESIZE_FILTERS:
+            raise ValueError(f"resize_u8: filter {filter!r} is none of {sorted(RESIZE_FILTERS)}")
+        _lib.check(L.mpreid_resize_u8(_ptr(packed.data), _ptr(packed.offsets), _ptr(packed.hw), B, packed.max_h, oh, ow,
+                                      RESIZE_FILTERS[filter], _ptr(dst), _ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "mpreid_resize_u8")
     return dst
+
+
+def upload_raw_images(images) -> PackedRawImages:
+    """decoded uint8 [h, w, 3] images of any sizes -> PackedRawImages: ONE H2D copy of the packed bytes through the pinned
+    staging buffers"""
+    dev = _lib.require_gpu()
+    arrs, hw, offsets, total = raw_image_layout(images)
+    packed, slot = _stager.stage(total)
+    np.concatenate([a.reshape(-1) for a in arrs], out=packed.numpy())
+    src = packed.to(dev, non_blocking=True)
+    _stager.copied(slot)
+    return PackedRawImages(src, torch.from_numpy(offsets).to(dev), torch.from_numpy(hw).to(dev), len(arrs), int(hw[:, 0].max()))
 
 
 def resize_bilinear_u8(images, out_hw) -> torch.Tensor:
@@ -617,14 +640,96 @@ def resize_bilinear_u8(images, out_hw) -> torch.Tensor:
     copy of the packed bytes (pinned staging), two kernels."""
     if isinstance(images, PackedRawImages):
         return resize_packed_u8(images, out_hw)
+    return resize_packed_u8(upload_raw_images(images), out_hw)
+
+
+def resize_u8(images, out_hw, filter: str = "bilinear") -> torch.Tensor:
+    """resize_bilinear_u8 with a filter: "bilinear" gives its bytes, "bicubic" is T.Resize(cfg.INPUT.SIZE_TRAIN, interpolation=3)
+    of train_transforms (datasets/make_dataloader_uniprompt.py:54), bit-exact with PIL.Image.resize(BICUBIC)."""
+    if filter not in RESIZE_FILTERS:
+        raise ValueError(f"resize_u8: filter {filter!r} is none of {sorted(RESIZE_FILTERS)}")
+    if not isinstance(images, PackedRawImages):
+        images = upload_raw_images(images)
+    return resize_packed_u8(images, out_hw, filter)
+
+
+def train_augment(img_u8: torch.Tensor, pad: int, params, sample_ids, seed: int, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5),
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mpreid_train_augment_f32 on a resized uint8 [B, H, W, 3] device batch: flip, pad + crop, ToTensor, Normalize and the erase
+    box of each image as its row of params (int32 [B, 8]: flip, crop_top, crop_left, erase_top, erase_left, erase_h, erase_w, 0)
+    says -> fp32 [B, 3, H, W].  The noise in a box depends on (seed, sample_ids[b], box) only."""
     dev = _lib.require_gpu()
-    arrs, hw, offsets, total = raw_image_layout(images)
-    packed, slot = _stager.stage(total)
-    np.concatenate([a.reshape(-1) for a in arrs], out=packed.numpy())
-    src = packed.to(dev, non_blocking=True)
-    _stager.copied(slot)
-    return resize_packed_u8(PackedRawImages(src, torch.from_numpy(offsets).to(dev), torch.from_numpy(hw).to(dev),
-                                            len(arrs), int(hw[:, 0].max())), out_hw)
+    img = img_u8.detach().to(device=dev, dtype=torch.uint8).contiguous()
+    assert img.dim() == 4 and img.shape[3] == 3, img.shape
+    B, H, W = (int(v) for v in img.shape[:3])
+    table = np.ascontiguousarray(params, dtype=np.int32)
+    ids = np.ascontiguousarray(sample_ids, dtype=np.int64)
+    if table.shape != (B, 8) or ids.shape != (B,):
+        raise ValueError(f"train_augment: params is int32 [{B}, 8] and sample_ids int64 [{B}], got {table.shape} and {ids.shape}")
+    if out is None:
+        out = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+    assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, 3, H, W) and out.is_cuda
+    m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    _lib.check(_lib.load().mpreid_train_augment_f32(_ptr(img), B, H, W, int(pad), table.ctypes.data, ids.ctypes.data,
+                                                    int(seed) & 0xFFFFFFFFFFFFFFFF, m, s, _ptr(out), _lib.stream_ptr()),
+               "mpreid_train_augment_f32")
+    return out
+
+
+class TrainAugment:
+    """The reference's train_transforms (datasets/make_dataloader_uniprompt.py:53-62) for decoded uint8 images, on the device:
+    Resize(size_hw, bicubic) -> RandomHorizontalFlip(flip_p) -> Pad(pad) -> RandomCrop(size_hw) -> ToTensor -> Normalize(mean,
+    std) -> timm RandomErasing(erase_p, mode='pixel', max_count=1).  The random decisions are drawn on the host by ``draw`` from
+    the global torch / random generators in the order a num_workers=0 loader draws them, image after image: torch.rand(1) for the
+    flip; two torch.randint(0, 2 pad + 1) for the crop (none when pad == 0); random.random() for the erase decision and, per
+    attempt, random.uniform (area), random.uniform (log aspect) and, on the first box that fits, two random.randint.  The kernels
+    take the decisions as a table: ``apply`` is one packed upload, the bicubic resize and mpreid_train_augment_f32.  The noise in
+    an erase box is Philox4x32-10 keyed by ``seed`` and the image's sample id (include/mpreid.h): N(0, 1), not timm's bits."""
+
+    MIN_AREA, MAX_AREA, MIN_ASPECT, MAX_ASPECT, ATTEMPTS = 0.02, 1.0 / 3.0, 0.3, 1.0 / 0.3, 10
+
+    def __init__(self, size_hw, flip_p: float = 0.5, pad: int = 10, erase_p: float = 0.5, mean=(0.5, 0.5, 0.5),
+                 std=(0.5, 0.5, 0.5), seed: int = 0):
+        self.size_hw = (int(size_hw[0]), int(size_hw[1]))
+        self.flip_p, self.pad, self.erase_p = float(flip_p), int(pad), float(erase_p)
+        self.mean, self.std, self.seed = tuple(float(v) for v in mean), tuple(float(v) for v in std), int(seed)
+        if self.pad < 0 or min(self.size_hw) < 1:
+            raise ValueError("TrainAugment: pad >= 0 and a positive size")
+
+    def _draw_erase(self):
+        import math
+        import random
+        H, W = self.size_hw
+        if random.random() > self.erase_p:
+            return 0, 0, 0, 0
+        lo, hi = math.log(self.MIN_ASPECT), math.log(self.MAX_ASPECT)
+        for _ in range(self.ATTEMPTS):
+            target = random.uniform(self.MIN_AREA, self.MAX_AREA) * (H * W)
+            ar = math.exp(random.uniform(lo, hi))
+            h, w = int(round(math.sqrt(target * ar))), int(round(math.sqrt(target / ar)))
+            if w < W and h < H:
+                top, left = random.randint(0, H - h), random.randint(0, W - w)
+                return (top, left, h, w) if h > 0 and w > 0 else (0, 0, 0, 0)   # an empty box erases nothing
+        return 0, 0, 0, 0
+
+    def draw(self, n: int) -> np.ndarray:
+        """the int32 [n, 8] table of n images, drawn in the reference's order"""
+        table = np.zeros((int(n), 8), dtype=np.int32)
+        for r in table:
+            r[0] = int(bool(torch.rand(1) < self.flip_p))
+            if self.pad > 0:
+                r[1] = int(torch.randint(0, 2 * self.pad + 1, size=(1,)).item())
+                r[2] = int(torch.randint(0, 2 * self.pad + 1, size=(1,)).item())
+            r[3:7] = self._draw_erase()
+        return table
+
+    def apply(self, raw_images, sample_ids, params=None) -> torch.Tensor:
+        """decoded uint8 images (a sequence, or a PackedRawImages) + their sample ids -> fp32 [B, 3, H, W] on the device;
+        params: the table to use instead of draw(B)"""
+        n = len(raw_images)
+        table = self.draw(n) if params is None else params
+        resized = resize_u8(raw_images, self.size_hw, "bicubic")
+        return train_augment(resized, self.pad, table, sample_ids, self.seed, self.mean, self.std)
 
 
 # ----------------------------------------------------------------------------------------------
