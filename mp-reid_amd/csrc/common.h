@@ -58,6 +58,12 @@ static inline int mpreid_check_image_in(const mpreid_image_in *img, mpreid_image
 
 __host__ __device__ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// the 256-byte aligned bump cursor of every workspace layout (towers, re-ranking): take(bytes) -> offset
+struct WsCursor {
+    size_t off = 0;
+    size_t operator()(size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; }
+};
+
 // Timing-ablation switches (MPREID_GEMM_DBG, MPREID_ATT_DBG, MPREID_CAND_DBG, MPREID_JACCARD_DBG: kernels that skip loads,
 // matrix instructions or stores -- WRONG RESULTS by design) are honoured only by a library built with -DMPREID_ABLATION
 // (MPREID_ABLATION=1 python mp-reid_amd/mpreid/build.py); the shipped library ignores them, so a stray environment

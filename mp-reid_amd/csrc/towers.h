@@ -7,12 +7,6 @@
 #pragma once
 #include "common.h"
 
-// the 256-byte aligned bump cursor of every workspace layout of the towers: take(bytes) -> offset
-struct WsCursor {
-    size_t off = 0;
-    size_t operator()(size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; }
-};
-
 // What every tower's kernels ask of (width, heads): 64-wide heads (the attention kernels), a width that is a multiple of
 // 128 up to 1024 (LayerNorm, the GEMM tiles).  Each caller words its own error.
 enum { SHAPE_OK = 0, SHAPE_HEAD_DIM, SHAPE_WIDTH };

@@ -25,7 +25,7 @@ OBJ = os.path.join(os.path.join(os.path.dirname(HERE), "csrc"), "_obj" + ("_" + 
 _REPO = os.path.dirname(os.path.dirname(HERE))
 LIB = (os.path.join(_REPO, "tools", "ablation_lib", "libmpreid_hip_" + _TAG + ".so") if _TAG
        else os.path.join(HERE, "libmpreid_hip.so"))
-SOURCES = ["api.cpp", "distance.hip", "rerank.hip", "gemm_f16.hip", "vit.hip", "attention.hip", "text.hip", "text_grad.hip", "vit_grad.hip", "prompt_train.hip", "optim.hip", "stage2_head.hip", "moe.hip", "moe_grad.hip", "evalrank.hip", "ranklist.hip", "qexpand.hip", "pairstats.hip", "preprocess.hip", "train_aug.hip", "conv_f16.hip", "rn50.hip", "rn50_f32.hip"]
+SOURCES = ["api.cpp", "distance.hip", "rerank.hip", "rerank_neighbours.hip", "rerank_sparse.hip", "rerank_wide.hip", "gemm_f16.hip", "vit.hip", "attention.hip", "text.hip", "text_grad.hip", "vit_grad.hip", "prompt_train.hip", "optim.hip", "stage2_head.hip", "moe.hip", "moe_grad.hip", "evalrank.hip", "ranklist.hip", "qexpand.hip", "pairstats.hip", "preprocess.hip", "train_aug.hip", "conv_f16.hip", "rn50.hip", "rn50_f32.hip"]
 # -ffp-contract=off: the rounding sequence of the re-ranking path is part of the contract
 # (include/mpreid_numerics.h); fused multiply-adds are written as explicit fmaf().
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",

@@ -312,7 +312,7 @@ def column_to_row_blocks(block: torch.Tensor, nq: int, ng_sizes: List[int]) -> t
 #
 # Phases 1-2 have a SPARSE form (default when N >= 2048 and max(k1+1, k2) <= 64): no [N/P][N] distance block per rank --
 # fp16 candidate GEMM of the local rows against all columns, certified exact refinement, on-the-fly distances in the
-# expansion (csrc/rerank.hip); a rank whose rows cannot be certified uses the dense form by itself.
+# expansion (csrc/rerank_sparse.hip through the mpreid_rr_ entry points of csrc/rerank.hip); a rank whose rows cannot be certified uses the dense form by itself.
 #
 # Every row is produced by the same instruction sequence as in the single-GPU call and no floating-point
 # reduction crosses ranks, so the result is bit-identical for any number of ranks

@@ -7,7 +7,7 @@ Same call as the reference (utils/reranking.py:29):
         -> np.ndarray float32 [num_query, num_gallery]
 
 probFea / galFea are torch tensors (any device); local_distmat an optional (nq+ng) x (nq+ng) array.
-The algorithm and every fp16/fp32 rounding point follow the reference (see csrc/rerank.hip); the
+The algorithm and every fp16/fp32 rounding point follow the reference (see csrc/rerank.h and the rerank_*.hip files); the
 dense N x N float16 ``V`` of the reference is replaced by sparse rows, which changes no result.
 
 Any k1 >= 0 / k2 >= 1 is answered, as by the reference: the fast algorithms have two limits (include/mpreid.h
